@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- MVFNet-R50 8x8 hot path on MI355X.
 
-    python bench.py [--mode train|infer] [--gpus N] [--steps K] [--warmup W] [--dtype f32|bf16] [--clips B]
+    python bench.py [--mode train|infer] [--gpus N] [--steps K] [--warmup W] [--dtype f32|bf16] [--clips B] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain call sets up, runs W warm-up steps, times K steps and prints one JSON line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step` = milliseconds per timed step, ...).  `--full` adds everything else, after the timed region: the roofline passes, the CPU
+baseline with the eager comparators, `other_configs` and, with more than one rank, the replica self-check.  `--dump-outputs DIR` writes what
+the last timed step computed as DIR/<name>.npy (see dump_outputs()).
 
 BASELINE.json's metric is "clips/sec (fwd+bwd) MVFNet-R50 8x8 224^2".  One "step" (default --mode train) = one full
 training iteration of the reference's hot path over one batch of synthetic clips already resident in HBM:
@@ -17,7 +22,7 @@ fp32 (what the reference's own fp16 mode keeps in fp32).  `--dtype f32` runs the
 Clips are independent units: N GPUs hold N replicas and N disjoint batches (weak scaling); the only collective is the
 gradient all-reduce of the training step.  The timed region is bracketed by barrier + synchronize, MAX over ranks.
 
-Extra objects in the JSON line
+Extra objects in the JSON line (--full)
   roofline      dominant kernel (implicit-GEMM conv `conv_igemm_kernel`: forward convs + data-gradient convs):
                 algorithmic FLOP of its launches in one step / their summed HIP-event durations (instrumented passes on
                 the launch stream, outside the timed region) vs the dense MFMA peak of the dtype; `wgrad` sub-object
@@ -65,8 +70,13 @@ def parse():
                          "10 clips x 3 crops of 256^2 per video, fcn_testing head, average_clips='prob', one video per step")
     ap.add_argument("--frames", type=int, default=8, help="frames per clip (T); 16 with --depth 101 --clips 16 is configs[3]")
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the roofline passes, the CPU baseline + eager comparators, other_configs and (multi-rank) "
+                         "the replica self-check; the --no-* switches below still drop parts of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, < 64 MB in all; rank 0)")
     ap.add_argument("--dtype", choices=["f32", "bf16"], default=None,
                     help="activation / packed-weight storage (fp32 accumulate, statistics, gradients, master weights). Default: bf16 for "
                          "--mode train (BASELINE.json configs[2]), f32 for --mode infer (configs[1])")
@@ -82,13 +92,13 @@ def parse():
                          "autocast(bf16)+channels_last on this GPU, cudnn.benchmark=False; ~70 s each on a fresh box, bounded by --eager-seconds)")
     ap.add_argument("--eager-seconds", type=float, default=150.0, help="wall-clock bound per eager comparator run")
     ap.add_argument("--streams", type=int, default=2, help="infer: independent clip-group launch chains (HIP streams)")
-    ap.add_argument("--per-layer", action="store_true", help="print a per-launch timing table to stderr")
+    ap.add_argument("--per-layer", action="store_true", help="print a per-launch timing table to stderr (from the roofline passes of --full)")
     ap.add_argument("--host-input", action="store_true",
                     help="train mode: every step's batch starts in (pinned) HOST memory and is uploaded by runner.DevicePrefetcher one batch ahead "
                          "on a copy stream, as a data-loader-fed run does (reference: MMDistributedDataParallel.scatter, parallel/distributed.py:40-62); "
                          "the JSON line then carries `host_input` with the H2D bytes per step.  `value` of the default run stays the HBM-resident one")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="default 1-GPU train run only: skip the short runs of BASELINE.json's other configurations (configs[1] fp32 inference, "
+                    help="--full 1-GPU train run at the headline shape only: skip the short runs of BASELINE.json's other configurations (configs[1] fp32 inference, "
                          "configs[3] R101 16x4 bf16 train, configs[4] 30-clip video) that are appended as `other_configs` AFTER the timed region")
     ap.add_argument("--other-seconds", type=float, default=150.0, help="wall-clock bound for each of those runs")
     ap.add_argument("--cpu-child", type=int, default=0, help=argparse.SUPPRESS)      # cpu_baseline's bounded os.cpu_count()-thread measurement (own process)
@@ -738,8 +748,8 @@ def other_configs(seconds):
             out[name] = {"skipped": "%.0f s of the %.0f s wall budget used (slow host); profiles/r06_final_numbers.txt has this configuration" % (_elapsed(), WALL_BUDGET)}
             continue
         # ([r6] 5 warm-up steps: a train engine replays its launch plan from the fifth step on -- two eager steps, two recorded ones)
-        cmd = [sys.executable, os.path.abspath(__file__), "--steps", "10" if "train" in flags else "5", "--warmup", "5" if "train" in flags else "2", "--no-cpu-baseline",
-               "--no-eager-compare", "--no-other-configs"] + flags
+        cmd = [sys.executable, os.path.abspath(__file__), "--steps", "10" if "train" in flags else "5", "--warmup", "5" if "train" in flags else "2", "--full",
+               "--no-cpu-baseline", "--no-eager-compare", "--no-other-configs"] + flags
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=seconds, env=dict(os.environ, BENCH_CHILD="1"))
             line = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
@@ -814,11 +824,46 @@ def cpu_child(depth, threads, train):
         print(json.dumps({"threads": threads, "value": round(2.0 / sorted(ts)[len(ts) // 2], 3), "timed_runs": len(ts), "note": None}), flush=True)
 
 
+DUMP_SAMPLE = 1 << 22        # elements of the fixed sample taken from each flat parameter-sized buffer (16 MB of fp32 each)
+DUMP_LIMIT = 64 << 20        # bytes, all files together
+
+
+def dump_outputs(outdir, out, eng):
+    """What the last timed step handed its caller, as float32 .npy files in `outdir`.
+    train: `loss` (the step's return value), `grad_norm` (eng.norm_out: total gradient norm, clip coefficient), and a fixed sample
+    (numpy default_rng(0), DUMP_SAMPLE sorted indices of the flat buffers, the same for every run of one configuration) of the updated
+    fp32 master weights `params_sample` and of the step's gradients `grads_sample` -- the whole flat buffers are ~97 MB each at R50.
+    infer / video: `scores` (the class scores the forward returns)."""
+    import numpy as np
+    arrays = {}
+    if eng is not None:
+        arrays["loss"] = out
+        arrays["grad_norm"] = eng.norm_out
+        n = eng.flat_grads.numel()
+        idx = np.sort(np.random.default_rng(0).choice(n, size=min(DUMP_SAMPLE, n), replace=False))
+        idx = torch.from_numpy(idx).to(eng.flat_grads.device)
+        if eng.flat_params is not None:
+            arrays["params_sample"] = eng.flat_params.index_select(0, idx)
+        arrays["grads_sample"] = eng.flat_grads.index_select(0, idx)
+    else:
+        arrays["scores"] = out
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_LIMIT))
+    os.makedirs(outdir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(outdir, k + ".npy"), a)
+    return sorted(arrays)
+
+
 def main():
     global T_FRAMES, SIZE, VIDEO
     args = parse()
     if args.cpu_child:
         return cpu_child(args.depth, args.cpu_child, args.mode == "train")
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
     if args.dtype is None:
         args.dtype = "bf16" if args.mode == "train" else "f32"
     T_FRAMES = args.frames
@@ -839,6 +884,9 @@ def main():
     backend = os.environ.get("BENCH_BACKEND", "nccl")
     local = local % torch.cuda.device_count() if backend != "nccl" else local
     torch.cuda.set_device(local)
+    # the train step's dropout masks come from torch's default generators, and the CUDA one is seeded at random in every process: seeded
+    # here, so that the same arguments give the same inputs and the same step in every run (--dump-outputs compares builds output for output)
+    torch.manual_seed(1234 + rank)
     dist = None
     if world > 1 or os.environ.get("BENCH_FORCE_DIST") == "1":      # the env switch exercises the RCCL path on a 1-GPU box
         import torch.distributed as dist
@@ -921,8 +969,10 @@ def main():
         rank_ms = [float(x.item()) / args.steps * 1e3 for x in every]
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, eng if train else None)
     replicas = None
-    if dist is not None and train:
+    if args.full and dist is not None and train:
         replicas = verify_replicas(dist, eng, step, world)
 
     if rank == 0:
@@ -956,17 +1006,17 @@ def main():
             res["replicas"] = replicas
         if video:
             res["videos_per_s"] = round(value / 30.0, 2)
-        if train:
+        if args.full and train:
             res["roofline"] = roofline_train(eng, imgs, labels, args.dtype, args.per_layer, ms)
-        else:
+        elif args.full:
             res["roofline"] = roofline_infer(model, imgs, args.dtype, args.per_layer)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             eager = None
             if train and not args.no_eager_compare:
                 # (the engine's buffers stay allocated: 288 GB of HBM hold both; the timed region is long over)
                 eager = eager_comparators(args.depth, args.clips, T_FRAMES, SIZE, args.eager_seconds, value, args.dtype)
             res["cpu_baseline"] = cpu_baseline(args.depth, args.cpu_seconds, args.mode, args.clips, eager)
-        if world == 1 and train and args.depth == 50 and T_FRAMES == 8 and args.clips == 32 and not args.no_other_configs:
+        if args.full and world == 1 and train and args.depth == 50 and T_FRAMES == 8 and args.clips == 32 and not args.no_other_configs:
             res["other_configs"] = other_configs(args.other_seconds)
             # the fp32 engine against the eager fp32 comparator of THIS run (the reference's shipped precision, like for like)
             try:

@@ -288,7 +288,7 @@ def test_bench_runs_its_rccl_path_with_one_rank():
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, BENCH_FORCE_DIST="1", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
-    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--steps", "2", "--warmup", "1", "--clips", "8", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--steps", "2", "--warmup", "1", "--clips", "8", "--full", "--no-cpu-baseline",
                         "--no-other-configs", "--no-eager-compare"], capture_output=True, text=True, timeout=500, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -311,7 +311,7 @@ def test_bench_multi_rank_path_with_two_ranks_on_one_gpu():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--clips", "4"]
+           os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--clips", "4", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=800, env=env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-2500:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -35,7 +35,7 @@ def main():
                 env = dict(os.environ, **{var[4:]: v})
             else:
                 env = dict(os.environ, MVF_POLICY=(base + "," if base else "") + "%s=%s" % (var.lower(), v))
-            cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-other-configs", "--no-eager-compare"] + extra
+            cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-other-configs", "--no-eager-compare"] + extra
             p = subprocess.run(cmd, capture_output=True, text=True, env=env)
             line = [l for l in p.stdout.splitlines() if l.startswith("{")]
             if p.returncode or not line:
