@@ -216,6 +216,17 @@ int mvf_stem_prep(const float* x_nchw, int n, int c, int h, int w, int pad, int 
 int mvf_frames_prep_u8(const unsigned char* frames_hwc, int n, int hs, int ws, const int* window, int h, int w,
                        const float* mean3, const float* std3, int to_rgb, int div_255, int pad, int wp, void* out_stem,
                        float* out_nchw, int dtype, void* stream);
+/* mvf_frames_prep_u8 with a bilinear resample in front of the crop [Resize / RandomResizedCrop augmentations.py:13-68, 600-661]:
+ * rows = device int32 (n, 11), one row per frame: (hs_i, ws_i, by, bx, bh, bw, rh, rw, oy, ox, flip).  Frame i's image is
+ * frames_hwc[i, :hs_i, :ws_i] of the (n, hs, ws, 3) batch (padded to the largest frame); its patch [by, by+bh) x [bx, bx+bw), already
+ * clipped to the image, is resized to rh x rw with cv2 INTER_LINEAR CV_8U arithmetic (exactly 2x down in both axes: INTER_AREA's
+ * rounded 2x2 mean, as cv2 switches), and resized[oy:oy+h, ox:ox+w], mirrored when flip != 0, continues exactly as in
+ * mvf_frames_prep_u8.  A row with bh == rh and bw == rw gives mvf_frames_prep_u8's output for the window (by+oy, bx+ox, flip), bit
+ * for bit.  rows must be non-NULL; their contents are NOT checked here (the caller validates them: out-of-range rows read out of
+ * bounds).  Same outputs, dtypes and host-side mean3 / std3 as mvf_frames_prep_u8. */
+int mvf_frames_resample_u8(const unsigned char* frames_hwc, int n, int hs, int ws, const int* rows, int h, int w,
+                           const float* mean3, const float* std3, int to_rgb, int div_255, int pad, int wp, void* out_stem,
+                           float* out_nchw, int dtype, void* stream);
 
 /* MaxPool2d(3, stride 2, pad 1) on NHWC (resnet.py:431,484). */
 int mvf_maxpool3x3s2_nhwc(const void* x, int n, int h, int w, int c, void* y, int dtype, void* stream);

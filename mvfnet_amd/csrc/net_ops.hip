@@ -68,6 +68,82 @@ __global__ void frames_prep_kernel(const unsigned char* frames, int n, int hs, i
     }
 }
 
+// The same, with a bilinear resample in front of the window: per frame one int32 row of RS_COLS
+// (hs_i, ws_i, by, bx, bh, bw, rh, rw, oy, ox, flip): the patch [by, by+bh) x [bx, bx+bw) of frame i is resized to rh x rw with cv2
+// INTER_LINEAR CV_8U arithmetic (resize.cpp: fp64 source coordinate rounded to fp32, 11-bit weights each rounded on its own, x taps
+// zeroed at the border, y rows clamped, the vectorised row blend ((H0>>4)*b0>>16) + ((H1>>4)*b1>>16) + 2 >> 2; exactly 2x down in
+// both axes is cv2's INTER_AREA switch, the rounded 2x2 mean), then resized[oy:oy+h, ox:ox+w] goes through frames_prep_kernel's crop
+// arithmetic from the uint8 value on.  Rows are validated on the host (preprocess.ResamplingFramePipeline).
+// Block = one (frame, padded output row): the row's descriptor, source rows and y weights are block-uniform; lanes run along x
+// (two source rows, byte loads of neighbouring pixels), one 8/16-byte store per pixel as stem_prep_kernel.
+constexpr int RS_COLS = 11;
+template <typename ET>
+__global__ void frames_resample_kernel(const unsigned char* frames, int hs, int ws, const int* rows, int h, int w, FramePrep fp,
+                                       int pad, int hp, int wp, ET* out_stem, float* out_nchw) {
+#pragma clang fp contract(off)
+    const int orow = blockIdx.x, img = orow / hp, yo = orow - img * hp;
+    const int ih = yo - pad;
+    const bool rok = ih >= 0 && ih < h;
+    const int* r = rows + (long)img * RS_COLS;
+    const int by = r[2], bx = r[3], bh = r[4], bw = r[5], rh = r[6], rw = r[7], oy = r[8], ox = r[9], flip = r[10];
+    const bool area2 = bh == 2 * rh && bw == 2 * rw;
+    const int dy = oy + (rok ? ih : 0);
+    int y0, y1, b0 = 0, b1 = 0;
+    if (area2) {
+        y0 = 2 * dy;
+        y1 = y0 + 1;
+    } else {
+        const double scy = 1.0 / ((double)rh / bh);
+        float fy = (float)((dy + 0.5) * scy - 0.5);
+        const int sy = (int)floorf(fy);
+        fy -= (float)sy;
+        b0 = __float2int_rn((1.f - fy) * 2048.f);
+        b1 = __float2int_rn(fy * 2048.f);
+        y0 = min(max(sy, 0), bh - 1);
+        y1 = min(max(sy + 1, 0), bh - 1);
+    }
+    const unsigned char* s0 = frames + (((long)img * hs + by + y0) * ws + bx) * 3;
+    const unsigned char* s1 = frames + (((long)img * hs + by + y1) * ws + bx) * 3;
+    const double scx = 1.0 / ((double)rw / bw);
+    for (int xo = threadIdx.x; xo < wp; xo += blockDim.x) {
+        const int iw = xo - pad;
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        if (rok && iw >= 0 && iw < w) {
+            const int dx = ox + (flip ? w - 1 - iw : iw);
+            int px[3];
+            if (area2) {
+                const unsigned char *p0 = s0 + dx * 6, *p1 = s1 + dx * 6;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) px[k] = (p0[k] + p0[k + 3] + p1[k] + p1[k + 3] + 2) >> 2;
+            } else {
+                float fx = (float)((dx + 0.5) * scx - 0.5);
+                int sx = (int)floorf(fx);
+                fx -= (float)sx;
+                if (sx < 0) sx = 0, fx = 0.f;
+                if (sx >= bw - 1) sx = bw - 1, fx = 0.f;
+                const int a0 = __float2int_rn((1.f - fx) * 2048.f), a1 = __float2int_rn(fx * 2048.f);
+                const int x0 = sx * 3, x1 = min(sx + 1, bw - 1) * 3;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const int h0 = s0[x0 + k] * a0 + s0[x1 + k] * a1, h1 = s1[x0 + k] * a0 + s1[x1 + k] * a1;
+                    px[k] = min((((h0 >> 4) * b0 >> 16) + ((h1 >> 4) * b1 >> 16) + 2) >> 2, 255);
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                float f = (float)px[fp.to_rgb ? 2 - k : k];
+                if (fp.div_255) f = __fdiv_rn(f, 255.f);
+                v[k] = __fmul_rn(__fsub_rn(f, fp.mean[k]), fp.stdinv[k]);
+            }
+            if (out_nchw) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) out_nchw[(((long)img * 3 + k) * h + ih) * w + iw] = v[k];
+            }
+        }
+        if (out_stem) st4(out_stem + ((long)orow * wp + xo) * 4, make_float4(v[0], v[1], v[2], v[3]));
+    }
+}
+
 // MaxPool2d(3, 2, 1) NHWC; thread = (output pixel, 4 channels).  The nine window loads are UNCONDITIONAL on clamped coordinates (a
 // clamped tap re-reads a pixel that is inside the window anyway, so the maximum is unchanged): a load inside an `if` is waited
 // for on the spot, nine serial round trips per output instead of one.
@@ -233,6 +309,35 @@ int mvf_frames_prep_u8(const unsigned char* frames_hwc, int n, int hs, int ws, c
                            p, hp, wpp, (float*)out_stem, out_nchw);
     else
         hipLaunchKernelGGL(frames_prep_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, frames_hwc, n, hs, ws, window, h, w, fp,
+                           p, hp, wpp, (bf16_t*)out_stem, out_nchw);
+    MVF_LAUNCH_CHECK();
+    return MVF_OK;
+}
+
+int mvf_frames_resample_u8(const unsigned char* frames_hwc, int n, int hs, int ws, const int* rows, int h, int w,
+                           const float* mean3, const float* std3, int to_rgb, int div_255, int pad, int wp, void* out_stem,
+                           float* out_nchw, int dtype, void* stream) {
+    MVF_REQUIRE(frames_hwc && rows && mean3 && std3 && (out_stem || out_nchw) && n > 0 && hs > 0 && ws > 0 && h > 0 && w > 0 && pad >= 0,
+                MVF_EINVAL, "frames_resample_u8: bad argument");
+    MVF_REQUIRE(!out_stem || wp >= w + 2 * pad, MVF_EINVAL, "frames_resample_u8: wp=%d < w + 2*pad", wp);
+    MVF_REQUIRE(dtype == MVF_F32 || dtype == MVF_BF16, MVF_EINVAL, "frames_resample_u8: bad dtype");
+    FramePrep fp;
+    for (int k = 0; k < 3; ++k) {
+        MVF_REQUIRE(std3[k] != 0.f, MVF_EINVAL, "frames_resample_u8: std[%d] is zero", k);
+        fp.mean[k] = mean3[k];
+        fp.stdinv[k] = (float)(1.0 / (double)std3[k]);      // the reference multiplies by 1 / float64(std)
+    }
+    fp.to_rgb = to_rgb;
+    fp.div_255 = div_255;
+    const int p = out_stem ? pad : 0, wpp = out_stem ? wp : w;
+    const int hp = h + 2 * p;
+    MVF_REQUIRE((long)n * hp < (1L << 31), MVF_ESHAPE, "frames_resample_u8: too many rows");
+    const dim3 grid(n * hp);
+    if (dtype == MVF_F32)
+        hipLaunchKernelGGL(frames_resample_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, frames_hwc, hs, ws, rows, h, w, fp,
+                           p, hp, wpp, (float*)out_stem, out_nchw);
+    else
+        hipLaunchKernelGGL(frames_resample_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, frames_hwc, hs, ws, rows, h, w, fp,
                            p, hp, wpp, (bf16_t*)out_stem, out_nchw);
     MVF_LAUNCH_CHECK();
     return MVF_OK;

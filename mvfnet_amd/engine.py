@@ -271,7 +271,7 @@ class BackboneEngine(object):
                 continue
             st.wait_stream(cur)
             with torch.cuda.stream(st):
-                self._forward_one(x[lo:hi], None, None if window is None else window.reshape(-1, 3)[lo:hi], out=feat[lo:hi])
+                self._forward_one(x[lo:hi], None, None if window is None else window.reshape(-1, window.shape[-1])[lo:hi], out=feat[lo:hi])
             used.append(st)
         for st in used:
             cur.wait_stream(st)

@@ -4,9 +4,15 @@ does crop window -> flip -> Normalize -> FormatShape -> stem layout (`mvf_frames
 
 Mirrors the reference's pipeline steps in names and argument meaning: `img_norm_cfg = dict(mean, std, to_rgb)` of the configs
 (config_zoo R50 8x8: mean [123.675, 116.28, 103.53], std [58.395, 57.12, 57.375], to_rgb True), `Flip(flip_ratio)`'s boolean,
-`CenterCrop` / `ThreeCrop(crop_size)` offsets (augmentations.py:196-228, 342-396, 465-540).  Decoding, resizing and the random
-scale-jitter crop stay on the host."""
+`CenterCrop` / `ThreeCrop(crop_size)` offsets (augmentations.py:196-228, 342-396, 465-540).
+
+`ResamplingFramePipeline` adds the resize in front of the crop (`mvf_frames_resample_u8`): `Resize` (keep_ratio or an exact size),
+`RandomResizedCrop`'s box and bilinear resample (cv2 INTER_LINEAR arithmetic), so the host ships frames as decoded, at their own
+resolution, with one int32 row per frame (`train_rows` / `val_rows` / `test_rows`, `collate_frames`).  Decoding is the only step left
+on the host."""
 import ctypes
+import math
+import random
 
 import torch
 
@@ -98,6 +104,198 @@ class FramePipeline(object):
         check(lib.mvf_frames_prep_u8(f.data_ptr(), n, hs, ws, win.data_ptr() if win is not None else None, h, w, self.mean, self.std,
                                      int(self.to_rgb), int(self.div_255), pad, wp, out.data_ptr(), None, _DT[dtype],
                                      torch.cuda.current_stream().cuda_stream), "mvf_frames_prep_u8")
+        return out
+
+
+# ---- resize geometry (host side; reference augmentations.py:13-68 Resize, :600-661 RandomResizedCrop, mmcv 0.4.3 imrescale / imcrop) --
+RESAMPLE_COLS = 11          # (hs_i, ws_i, by, bx, bh, bw, rh, rw, oy, ox, flip): see include/mvfnet_hip.h mvf_frames_resample_u8
+
+
+def rescale_size(h, w, scale):
+    """The output size of mmcv 0.4.3 `imrescale(img, scale)` for an h x w image, in mmcv's (new_w, new_h) order: a number is the
+    factor itself; a tuple gives f = min(max(scale) / max(h, w), min(scale) / min(h, w)); then (int(w * f + 0.5), int(h * f + 0.5)).
+    Third-party code restated (mmcv is not in the build container): parity unpinned; the scale the reference hands it is pinned by
+    tests/golden/make_resize_golden.py."""
+    if isinstance(scale, (int, float)):
+        if scale <= 0:
+            raise ValueError("Invalid scale %s, must be positive." % (scale,))
+        f = float(scale)
+    else:
+        f = min(max(scale) / max(h, w), min(scale) / min(h, w))
+    return int(w * float(f) + 0.5), int(h * float(f) + 0.5)
+
+
+def resized_hw(hs, ws, scale, keep_ratio=True):
+    """(rh, rw) of `Resize(scale, keep_ratio)` (augmentations.py:37-61): imrescale's size, or the exact (w, h) `scale` handed to imresize."""
+    if keep_ratio:
+        rw, rh = rescale_size(hs, ws, scale)
+    else:
+        rw, rh = int(scale[0]), int(scale[1])
+    if rh < 1 or rw < 1:
+        raise ValueError("Resize(%s) of a %dx%d frame is empty" % (scale, hs, ws))
+    return rh, rw
+
+
+def random_resized_crop_box(h, w, scale=(0.08, 1.0), ratio=(3. / 4., 4. / 3.), rng=random):
+    """RandomResizedCrop.get_params + the box __call__ hands to mmcv.imcrop (augmentations.py:612-651), quirks kept: Python's `random`
+    (`rng`: the module or a random.Random), 10 attempts of uniform, uniform, random [, randint, randint when the box fits]; the crop's
+    width is tested against the image HEIGHT and its height against the WIDTH (shape[0] / shape[1]); the centre-square fallback; the box
+    [x1, y1, x1 + crop_w - 1, y1 + crop_h - 1], which the axis swap can make overhang the frame, clipped to the image as mmcv.imcrop
+    does.  -> the clipped patch (by, bx, bh, bw)."""
+    for _ in range(10):
+        area = h * w
+        target_area = rng.uniform(*scale) * area
+        aspect_ratio = rng.uniform(*ratio)
+        cw = int(round(math.sqrt(target_area * aspect_ratio)))
+        ch = int(round(math.sqrt(target_area / aspect_ratio)))
+        if rng.random() < 0.5:
+            cw, ch = ch, cw
+        if cw <= h and ch <= w:
+            x1 = rng.randint(0, w - ch)
+            y1 = rng.randint(0, h - cw)
+            break
+    else:
+        cw = ch = min(h, w)
+        x1, y1 = (w - cw) // 2, (h - cw) // 2
+    x2, y2 = x1 + cw - 1, y1 + ch - 1
+    x1, x2 = (max(min(v, w - 1), 0) for v in (x1, x2))         # mmcv.bbox_clip
+    y1, y2 = (max(min(v, h - 1), 0) for v in (y1, y2))
+    if x2 < x1 or y2 < y1:
+        raise ValueError("RandomResizedCrop drew an empty box on a %dx%d frame" % (h, w))
+    return y1, x1, y2 - y1 + 1, x2 - x1 + 1
+
+
+def _hw(size):
+    """cfg sizes are (w, h) or an int -> (h, w)."""
+    return (size, size) if isinstance(size, int) else (int(size[1]), int(size[0]))
+
+
+def _table(rows):
+    import numpy as np
+    return np.asarray(rows, dtype=np.int32).reshape(-1, RESAMPLE_COLS)
+
+
+def resize_rows(hs, ws, n_frames, scale, keep_ratio=True):
+    """Rows for `Resize(scale, keep_ratio)` alone: every frame resized whole, the output is the whole resized image (crop = (rh, rw))."""
+    rh, rw = resized_hw(hs, ws, scale, keep_ratio)
+    return _table([(hs, ws, 0, 0, hs, ws, rh, rw, 0, 0, 0)] * n_frames)
+
+
+def train_rows(hs, ws, n_frames, input_size=224, scale=(0.08, 1.0), ratio=(3. / 4., 4. / 3.), flip_ratio=0.5, rng=random, np_rng=None):
+    """The shipped train recipe RandomResizedCrop(input_size) -> Flip(flip_ratio) for one clip of n_frames hs x ws frames, draws in the
+    reference's order: get_params on `rng` (Python's random), then Flip's one np.random draw (`np_rng`, default the global numpy
+    generator).  One box and one flip for the whole clip.  -> (n_frames, 11) int32."""
+    by, bx, bh, bw = random_resized_crop_box(hs, ws, scale, ratio, rng)
+    rh, rw = _hw(input_size)
+    flip = int(flip_flag(flip_ratio, np_rng))
+    return _table([(hs, ws, by, bx, bh, bw, rh, rw, 0, 0, flip)] * n_frames)
+
+
+def val_rows(hs, ws, n_frames, scale=(float("inf"), 256), crop_size=224, keep_ratio=True):
+    """The shipped val recipe Resize(scale, keep_ratio) -> CenterCrop(crop_size) (augmentations.py:445-452 offsets on the resized size).
+    The recipe's Flip(flip_ratio=0) never mirrors (it still consumes one np.random draw in the reference; none is drawn here)."""
+    rh, rw = resized_hw(hs, ws, scale, keep_ratio)
+    ch, cw = _hw(crop_size)
+    if ch > rh or cw > rw:
+        raise ValueError("CenterCrop %dx%d larger than the resized %dx%d frame" % (ch, cw, rh, rw))
+    return _table([(hs, ws, 0, 0, hs, ws, rh, rw, (rh - ch) // 2, (rw - cw) // 2, 0)] * n_frames)
+
+
+def test_rows(hs, ws, n_frames, scale=(float("inf"), 256), crop_size=256, keep_ratio=True):
+    """The shipped test recipe Resize(scale, keep_ratio) -> ThreeCrop(crop_size): 3 * n_frames rows, crop-major and frame-minor as
+    ThreeCrop stacks its img_group (three_crop_windows); the caller repeats the clip's frames three times."""
+    rh, rw = resized_hw(hs, ws, scale, keep_ratio)
+    ch, cw = _hw(crop_size)
+    if ch > rh or cw > rw:
+        raise ValueError("ThreeCrop %dx%d larger than the resized %dx%d frame" % (ch, cw, rh, rw))
+    return _table([(hs, ws, 0, 0, hs, ws, rh, rw, y0, x0, 0) for (y0, x0, _) in three_crop_windows(n_frames, rh, rw, ch, cw)])
+
+
+test_rows.__test__ = False          # a row builder, not a pytest test
+
+
+def collate_frames(groups, pad_to=None):
+    """groups: a list of (frames, rows) per clip -- frames (T, h_b, w_b, 3) uint8 (numpy or a CPU tensor), rows its (T, 11) table --
+    -> (frames (B, T, Hs, Ws, 3) uint8, rows (B * T, 11) int32), CPU tensors.  Clips of different resolutions share one dense tensor,
+    zero padded to the largest (or to `pad_to` = (Hs, Ws), so a prefetcher's persistent buffers keep their shape); every row keeps its
+    own frame's (hs_i, ws_i)."""
+    import numpy as np
+    fr = [torch.as_tensor(np.asarray(f)) for f, _ in groups]
+    rows = [torch.as_tensor(np.asarray(r, dtype=np.int32)).reshape(-1, RESAMPLE_COLS) for _, r in groups]
+    if not fr:
+        raise ValueError("collate_frames: no clips")
+    t = fr[0].shape[0]
+    for f, r in zip(fr, rows):
+        if f.dtype != torch.uint8 or f.dim() != 4 or f.shape[-1] != 3 or f.shape[0] != t:
+            raise ValueError("collate_frames: every clip must be (T=%d, h, w, 3) uint8, got %s %s" % (t, f.dtype, tuple(f.shape)))
+        if r.shape[0] != t or bool((r[:, 0] != f.shape[1]).any()) or bool((r[:, 1] != f.shape[2]).any()):
+            raise ValueError("collate_frames: rows do not describe their %s frames" % (tuple(f.shape),))
+    hs, ws = (max(f.shape[1] for f in fr), max(f.shape[2] for f in fr)) if pad_to is None else (int(pad_to[0]), int(pad_to[1]))
+    if any(f.shape[1] > hs or f.shape[2] > ws for f in fr):
+        raise ValueError("collate_frames: a clip is larger than pad_to=%s" % (pad_to,))
+    out = torch.zeros(len(fr), t, hs, ws, 3, dtype=torch.uint8)
+    for b, f in enumerate(fr):
+        out[b, :, :f.shape[1], :f.shape[2]] = f
+    return out, torch.cat(rows).contiguous()
+
+
+class ResamplingFramePipeline(FramePipeline):
+    """FramePipeline with the resize in front of the crop: per-frame int32 rows (hs_i, ws_i, by, bx, bh, bw, rh, rw, oy, ox, flip)
+    (train_rows / val_rows / test_rows / resize_rows) instead of (y0, x0, flip) windows; same constructor, `crop_hw`, `to_nchw` and
+    `to_stem` interface, so the engines take it through `input_pipeline` / `window=`.  The frames may be smaller than the crop."""
+
+    def center_window(self, n, hs, ws, flip=False, device="cuda"):
+        """Rows of CenterCrop without a resize (augmentations.py:447-452)."""
+        h, w = self.crop_hw
+        row = [hs, ws, 0, 0, hs, ws, hs, ws, (hs - h) // 2, (ws - w) // 2, int(bool(flip))]
+        return torch.tensor([row] * n, dtype=torch.int32, device=device)
+
+    def _frames(self, frames):
+        if frames.dtype != torch.uint8 or frames.shape[-1] != 3 or not frames.is_cuda:
+            raise TypeError("ResamplingFramePipeline expects a CUDA uint8 tensor (..., H, W, 3) of decoded frames, got %s %s" % (frames.dtype, tuple(frames.shape)))
+        return frames.reshape((-1,) + tuple(frames.shape[-3:])).contiguous()
+
+    def _window(self, rows, n, hs, ws):
+        if rows is None:
+            raise ValueError("ResamplingFramePipeline needs one (hs_i, ws_i, by, bx, bh, bw, rh, rw, oy, ox, flip) row per frame")
+        rows = torch.as_tensor(rows).to(device="cuda", dtype=torch.int32).reshape(-1, RESAMPLE_COLS).contiguous()
+        if rows.shape[0] != n:
+            raise ValueError("rows: %d rows for %d frames" % (rows.shape[0], n))
+        h, w = self.crop_hw
+        fh, fw, by, bx, bh, bw, rh, rw, oy, ox, flip = rows.to(torch.int64).unbind(1)
+        bad = ((fh < 1) | (fh > hs) | (fw < 1) | (fw > ws)
+               | (by < 0) | (bx < 0) | (bh < 1) | (bw < 1) | (by + bh > fh) | (bx + bw > fw)
+               | (oy < 0) | (ox < 0) | (oy + h > rh) | (ox + w > rw)
+               | ((flip != 0) & (flip != 1)))
+        if bool(bad.any()):
+            i = int(bad.nonzero()[0, 0])
+            raise ValueError("row %d %s: the patch must lie in its %dx%d-padded frame and the %dx%d crop in the resized patch"
+                             % (i, rows[i].tolist(), hs, ws, h, w))
+        return rows
+
+    def to_nchw(self, frames, rows):
+        """-> (n, 3, h, w) fp32, what the reference's Resize / RandomResizedCrop + crop + Flip + Normalize + FormatShape produce."""
+        f = self._frames(frames)
+        n, hs, ws = f.shape[:3]
+        r = self._window(rows, n, hs, ws)
+        h, w = self.crop_hw
+        out = torch.empty(n, 3, h, w, dtype=torch.float32, device=f.device)
+        check(lib.mvf_frames_resample_u8(f.data_ptr(), n, hs, ws, r.data_ptr(), h, w, self.mean, self.std, int(self.to_rgb),
+                                         int(self.div_255), 0, w, None, out.data_ptr(), 0,
+                                         torch.cuda.current_stream().cuda_stream), "mvf_frames_resample_u8")
+        return out
+
+    def to_stem(self, frames, rows, pad, wp, dtype, out=None):
+        """-> (n, h + 2 pad, wp, 4) `dtype`, the stem conv's operand (FramePipeline.to_stem), with the resample in front."""
+        f = self._frames(frames)
+        n, hs, ws = f.shape[:3]
+        r = self._window(rows, n, hs, ws)
+        h, w = self.crop_hw
+        if out is None:
+            out = torch.empty(n, h + 2 * pad, wp, 4, dtype=dtype, device=f.device)
+        check(lib.mvf_frames_resample_u8(f.data_ptr(), n, hs, ws, r.data_ptr(), h, w, self.mean, self.std, int(self.to_rgb),
+                                         int(self.div_255), pad, wp, out.data_ptr(), None, _DT[dtype],
+                                         torch.cuda.current_stream().cuda_stream), "mvf_frames_resample_u8")
         return out
 
 

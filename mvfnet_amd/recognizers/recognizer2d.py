@@ -90,7 +90,9 @@ class Recognizer2D(nn.Module):
     def set_input_pipeline(self, pipeline):
         """Feed the model DECODED uint8 frames -- `img_group` (B, frames, Hs, Ws, 3) uint8 plus an optional `window=` (frames, 3)
         int32 of per-frame (y0, x0, flip) -- instead of the normalised fp32 tensor: `pipeline` is a preprocess.FramePipeline
-        (the config's img_norm_cfg + crop size); crop, flip, Normalize and FormatShape then run inside the stem's input kernel."""
+        (the config's img_norm_cfg + crop size); crop, flip, Normalize and FormatShape then run inside the stem's input kernel.
+        With a preprocess.ResamplingFramePipeline, `window=` is the (frames, 11) int32 row table (train_rows / val_rows / test_rows,
+        collate_frames) and Resize / RandomResizedCrop run in that kernel too: frames of any resolution, zero padded to one Hs x Ws."""
         self.input_pipeline = pipeline
         self.backbone.input_pipeline = pipeline
         return self
