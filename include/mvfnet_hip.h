@@ -227,6 +227,17 @@ int mvf_frames_prep_u8(const unsigned char* frames_hwc, int n, int hs, int ws, c
 int mvf_frames_resample_u8(const unsigned char* frames_hwc, int n, int hs, int ws, const int* rows, int h, int w,
                            const float* mean3, const float* std3, int to_rgb, int div_255, int pad, int wp, void* out_stem,
                            float* out_nchw, int dtype, void* stream);
+/* mvf_frames_resample_u8 with a per-frame affine colour transform between the resample and Normalize [ColorJitter
+ * augmentations.py:238-339: brightness, contrast, saturation, hue and the PCA lighting term are all affine in the pixel and nothing
+ * clips, so one frame's whole jitter is q = M p + b].  color = device fp32 (n, 12), one row per frame: M[0][0..2], M[1][0..2],
+ * M[2][0..2], b[0..2], indices in the STORED channel order of the frame (before to_rgb); preprocess.color_jitter_table composes it.
+ * p[k] = float(resampled uint8 px[k]); q[c] = ((M[c][0]*p[0] + M[c][1]*p[1]) + M[c][2]*p[2]) + b[c], every product and sum rounded to
+ * fp32 on its own (no FMA); then f = q[to_rgb ? 2 - k : k] continues as in mvf_frames_prep_u8.  M = I gives p + b rounded once, the
+ * reference's float32 `img + bgr`.  color == NULL gives mvf_frames_resample_u8's output, bit for bit.  The coefficients are NOT
+ * checked here (the caller refuses non-finite ones).  Everything else as mvf_frames_resample_u8. */
+int mvf_frames_resample_color_u8(const unsigned char* frames_hwc, int n, int hs, int ws, const int* rows, const float* color, int h, int w,
+                                 const float* mean3, const float* std3, int to_rgb, int div_255, int pad, int wp, void* out_stem,
+                                 float* out_nchw, int dtype, void* stream);
 
 /* MaxPool2d(3, stride 2, pad 1) on NHWC (resnet.py:431,484). */
 int mvf_maxpool3x3s2_nhwc(const void* x, int n, int h, int w, int c, void* y, int dtype, void* stream);

@@ -76,12 +76,21 @@ __global__ void frames_prep_kernel(const unsigned char* frames, int n, int hs, i
 // arithmetic from the uint8 value on.  Rows are validated on the host (preprocess.ResamplingFramePipeline).
 // Block = one (frame, padded output row): the row's descriptor, source rows and y weights are block-uniform; lanes run along x
 // (two source rows, byte loads of neighbouring pixels), one 8/16-byte store per pixel as stem_prep_kernel.
-constexpr int RS_COLS = 11;
-template <typename ET>
-__global__ void frames_resample_kernel(const unsigned char* frames, int hs, int ws, const int* rows, int h, int w, FramePrep fp,
-                                       int pad, int hp, int wp, ET* out_stem, float* out_nchw) {
+// COLOR: the frame's ColorJitter (augmentations.py:238-339; every branch is affine in the pixel and nothing clips) sits between the
+// resample and Normalize as q = M p + b on the resampled uint8 triple in STORED channel order: color = (n, 12) fp32 rows
+// M[0][0..2], M[1][0..2], M[2][0..2], b[0..2], block-uniform like the int row, read once per block.  Every product and sum is rounded
+// to fp32 on its own, summed left to right, so M = I gives p + b rounded once (the reference's float32 `img + bgr`).
+constexpr int RS_COLS = 11, CJ_COLS = 12;
+template <typename ET, bool COLOR>
+__global__ void frames_resample_kernel(const unsigned char* frames, int hs, int ws, const int* rows, const float* color, int h, int w,
+                                       FramePrep fp, int pad, int hp, int wp, ET* out_stem, float* out_nchw) {
 #pragma clang fp contract(off)
     const int orow = blockIdx.x, img = orow / hp, yo = orow - img * hp;
+    float cm[CJ_COLS];
+    if constexpr (COLOR) {
+#pragma unroll
+        for (int k = 0; k < CJ_COLS; ++k) cm[k] = color[(long)img * CJ_COLS + k];
+    }
     const int ih = yo - pad;
     const bool rok = ih >= 0 && ih < h;
     const int* r = rows + (long)img * RS_COLS;
@@ -129,9 +138,18 @@ __global__ void frames_resample_kernel(const unsigned char* frames, int hs, int 
                     px[k] = min((((h0 >> 4) * b0 >> 16) + ((h1 >> 4) * b1 >> 16) + 2) >> 2, 255);
                 }
             }
+            float q[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) q[k] = (float)px[k];
+            if constexpr (COLOR) {
+                const float p0 = q[0], p1 = q[1], p2 = q[2];
+#pragma unroll
+                for (int k = 0; k < 3; ++k)            // plain operators: the contract(off) above covers them, not the bodies of inlined intrinsics
+                    q[k] = ((cm[3 * k] * p0 + cm[3 * k + 1] * p1) + cm[3 * k + 2] * p2) + cm[9 + k];
+            }
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
-                float f = (float)px[fp.to_rgb ? 2 - k : k];
+                float f = q[fp.to_rgb ? 2 - k : k];
                 if (fp.div_255) f = __fdiv_rn(f, 255.f);
                 v[k] = __fmul_rn(__fsub_rn(f, fp.mean[k]), fp.stdinv[k]);
             }
@@ -269,6 +287,43 @@ inline int grid_for(long total, int per_block = 256, int cap = 256 * 32) {
     return (int)std::min<long>((total + per_block - 1) / per_block, cap);
 }
 
+// mvf_frames_resample_u8 (color == nullptr) and mvf_frames_resample_color_u8: one validation, one launch
+int frames_resample(const char* who, const unsigned char* frames_hwc, int n, int hs, int ws, const int* rows, const float* color, int h, int w,
+                    const float* mean3, const float* std3, int to_rgb, int div_255, int pad, int wp, void* out_stem, float* out_nchw,
+                    int dtype, void* stream) {
+    MVF_REQUIRE(frames_hwc && rows && mean3 && std3 && (out_stem || out_nchw) && n > 0 && hs > 0 && ws > 0 && h > 0 && w > 0 && pad >= 0,
+                MVF_EINVAL, "%s: bad argument", who);
+    MVF_REQUIRE(!out_stem || wp >= w + 2 * pad, MVF_EINVAL, "%s: wp=%d < w + 2*pad", who, wp);
+    MVF_REQUIRE(dtype == MVF_F32 || dtype == MVF_BF16, MVF_EINVAL, "%s: bad dtype", who);
+    FramePrep fp;
+    for (int k = 0; k < 3; ++k) {
+        MVF_REQUIRE(std3[k] != 0.f, MVF_EINVAL, "%s: std[%d] is zero", who, k);
+        fp.mean[k] = mean3[k];
+        fp.stdinv[k] = (float)(1.0 / (double)std3[k]);      // the reference multiplies by 1 / float64(std)
+    }
+    fp.to_rgb = to_rgb;
+    fp.div_255 = div_255;
+    const int p = out_stem ? pad : 0, wpp = out_stem ? wp : w;
+    const int hp = h + 2 * p;
+    MVF_REQUIRE((long)n * hp < (1L << 31), MVF_ESHAPE, "%s: too many rows", who);
+    const dim3 grid(n * hp);
+    const hipStream_t st = (hipStream_t)stream;
+    if (dtype == MVF_F32 && !color)
+        hipLaunchKernelGGL((frames_resample_kernel<float, false>), grid, dim3(256), 0, st, frames_hwc, hs, ws, rows, color, h, w, fp, p, hp, wpp,
+                           (float*)out_stem, out_nchw);
+    else if (dtype == MVF_F32)
+        hipLaunchKernelGGL((frames_resample_kernel<float, true>), grid, dim3(256), 0, st, frames_hwc, hs, ws, rows, color, h, w, fp, p, hp, wpp,
+                           (float*)out_stem, out_nchw);
+    else if (!color)
+        hipLaunchKernelGGL((frames_resample_kernel<bf16_t, false>), grid, dim3(256), 0, st, frames_hwc, hs, ws, rows, color, h, w, fp, p, hp, wpp,
+                           (bf16_t*)out_stem, out_nchw);
+    else
+        hipLaunchKernelGGL((frames_resample_kernel<bf16_t, true>), grid, dim3(256), 0, st, frames_hwc, hs, ws, rows, color, h, w, fp, p, hp, wpp,
+                           (bf16_t*)out_stem, out_nchw);
+    MVF_LAUNCH_CHECK();
+    return MVF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -317,30 +372,15 @@ int mvf_frames_prep_u8(const unsigned char* frames_hwc, int n, int hs, int ws, c
 int mvf_frames_resample_u8(const unsigned char* frames_hwc, int n, int hs, int ws, const int* rows, int h, int w,
                            const float* mean3, const float* std3, int to_rgb, int div_255, int pad, int wp, void* out_stem,
                            float* out_nchw, int dtype, void* stream) {
-    MVF_REQUIRE(frames_hwc && rows && mean3 && std3 && (out_stem || out_nchw) && n > 0 && hs > 0 && ws > 0 && h > 0 && w > 0 && pad >= 0,
-                MVF_EINVAL, "frames_resample_u8: bad argument");
-    MVF_REQUIRE(!out_stem || wp >= w + 2 * pad, MVF_EINVAL, "frames_resample_u8: wp=%d < w + 2*pad", wp);
-    MVF_REQUIRE(dtype == MVF_F32 || dtype == MVF_BF16, MVF_EINVAL, "frames_resample_u8: bad dtype");
-    FramePrep fp;
-    for (int k = 0; k < 3; ++k) {
-        MVF_REQUIRE(std3[k] != 0.f, MVF_EINVAL, "frames_resample_u8: std[%d] is zero", k);
-        fp.mean[k] = mean3[k];
-        fp.stdinv[k] = (float)(1.0 / (double)std3[k]);      // the reference multiplies by 1 / float64(std)
-    }
-    fp.to_rgb = to_rgb;
-    fp.div_255 = div_255;
-    const int p = out_stem ? pad : 0, wpp = out_stem ? wp : w;
-    const int hp = h + 2 * p;
-    MVF_REQUIRE((long)n * hp < (1L << 31), MVF_ESHAPE, "frames_resample_u8: too many rows");
-    const dim3 grid(n * hp);
-    if (dtype == MVF_F32)
-        hipLaunchKernelGGL(frames_resample_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, frames_hwc, hs, ws, rows, h, w, fp,
-                           p, hp, wpp, (float*)out_stem, out_nchw);
-    else
-        hipLaunchKernelGGL(frames_resample_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, frames_hwc, hs, ws, rows, h, w, fp,
-                           p, hp, wpp, (bf16_t*)out_stem, out_nchw);
-    MVF_LAUNCH_CHECK();
-    return MVF_OK;
+    return frames_resample("frames_resample_u8", frames_hwc, n, hs, ws, rows, nullptr, h, w, mean3, std3, to_rgb, div_255, pad, wp, out_stem,
+                           out_nchw, dtype, stream);
+}
+
+int mvf_frames_resample_color_u8(const unsigned char* frames_hwc, int n, int hs, int ws, const int* rows, const float* color, int h, int w,
+                                 const float* mean3, const float* std3, int to_rgb, int div_255, int pad, int wp, void* out_stem,
+                                 float* out_nchw, int dtype, void* stream) {
+    return frames_resample("frames_resample_color_u8", frames_hwc, n, hs, ws, rows, color, h, w, mean3, std3, to_rgb, div_255, pad, wp,
+                           out_stem, out_nchw, dtype, stream);
 }
 
 int mvf_maxpool3x3s2_nhwc(const void* x, int n, int h, int w, int c, void* y, int dtype, void* stream) {

@@ -9,7 +9,13 @@ Mirrors the reference's pipeline steps in names and argument meaning: `img_norm_
 `ResamplingFramePipeline` adds the resize in front of the crop (`mvf_frames_resample_u8`): `Resize` (keep_ratio or an exact size),
 `RandomResizedCrop`'s box and bilinear resample (cv2 INTER_LINEAR arithmetic), so the host ships frames as decoded, at their own
 resolution, with one int32 row per frame (`train_rows` / `val_rows` / `test_rows`, `collate_frames`).  Decoding is the only step left
-on the host."""
+on the host.
+
+`JitterFramePipeline` adds the TSN-style fine-tuning recipe (`mvf_frames_resample_color_u8`): `ColorJitter` as one affine colour
+transform per frame between the resample and Normalize (`color_jitter_table`: 12 floats, the reference's draws in its order), and the
+geometry of `MultiScaleCrop`, `TenCrop`, `RandomRescaledCrop` and a bare `CenterCrop` as the same 11-column rows
+(`multi_scale_crop_rows` / `ten_crop_rows` / `random_rescaled_crop_rows` / `center_crop_rows`); `jitter_rows` packs both into one
+23-column int32 table that travels through `window=` (`collate_jitter_frames`)."""
 import ctypes
 import math
 import random
@@ -214,14 +220,15 @@ def test_rows(hs, ws, n_frames, scale=(float("inf"), 256), crop_size=256, keep_r
 test_rows.__test__ = False          # a row builder, not a pytest test
 
 
-def collate_frames(groups, pad_to=None):
+def collate_frames(groups, pad_to=None, cols=None):
     """groups: a list of (frames, rows) per clip -- frames (T, h_b, w_b, 3) uint8 (numpy or a CPU tensor), rows its (T, 11) table --
     -> (frames (B, T, Hs, Ws, 3) uint8, rows (B * T, 11) int32), CPU tensors.  Clips of different resolutions share one dense tensor,
     zero padded to the largest (or to `pad_to` = (Hs, Ws), so a prefetcher's persistent buffers keep their shape); every row keeps its
-    own frame's (hs_i, ws_i)."""
+    own frame's (hs_i, ws_i).  `cols` (default 11) is the tables' column count: 23 for jitter_rows tables (collate_jitter_frames)."""
     import numpy as np
+    cols = RESAMPLE_COLS if cols is None else int(cols)
     fr = [torch.as_tensor(np.asarray(f)) for f, _ in groups]
-    rows = [torch.as_tensor(np.asarray(r, dtype=np.int32)).reshape(-1, RESAMPLE_COLS) for _, r in groups]
+    rows = [torch.as_tensor(np.asarray(r, dtype=np.int32)).reshape(-1, cols) for _, r in groups]
     if not fr:
         raise ValueError("collate_frames: no clips")
     t = fr[0].shape[0]
@@ -296,6 +303,222 @@ class ResamplingFramePipeline(FramePipeline):
         check(lib.mvf_frames_resample_u8(f.data_ptr(), n, hs, ws, r.data_ptr(), h, w, self.mean, self.std, int(self.to_rgb),
                                          int(self.div_255), pad, wp, out.data_ptr(), None, _DT[dtype],
                                          torch.cuda.current_stream().cuda_stream), "mvf_frames_resample_u8")
+        return out
+
+
+# ---- TSN-style recipe (host side; reference augmentations.py:71-192 MultiScaleCrop, :238-339 ColorJitter, :544-596 TenCrop, ----------
+# ---- :672-707 RandomRescaledCrop, :428-457 CenterCrop) ------------------------------------------------------------------------------
+COLOR_COLS = 12             # M[0][0..2], M[1][0..2], M[2][0..2], b[0..2]: see include/mvfnet_hip.h mvf_frames_resample_color_u8
+JITTER_COLS = RESAMPLE_COLS + COLOR_COLS
+
+
+def fix_offsets(more_fix_crop, image_w, image_h, crop_w, crop_h):
+    """MultiScaleCrop.fill_fix_offset (augmentations.py:160-183): (x, y) of the 5 fixed crops (corners, centre) or, with more_fix_crop,
+    13 (plus the edge centres and the quarter points), in the reference's order; steps are floored quarters of the slack."""
+    ws, hs = (image_w - crop_w) // 4, (image_h - crop_h) // 4
+    ret = [(0, 0), (4 * ws, 0), (0, 4 * hs), (4 * ws, 4 * hs), (2 * ws, 2 * hs)]
+    if more_fix_crop:
+        ret += [(0, 2 * hs), (4 * ws, 2 * hs), (2 * ws, 4 * hs), (2 * ws, 0), (ws, hs), (3 * ws, hs), (ws, 3 * hs), (3 * ws, 3 * hs)]
+    return ret
+
+
+def multi_scale_crop_box(h, w, input_size, scales=None, max_distort=1, fix_crop=True, more_fix_crop=True, rng=random):
+    """MultiScaleCrop._sample_crop_size + the box __call__ hands to mmcv.imcrop (augmentations.py:106-157) for an h x w frame, draws on
+    Python's `random` (`rng`) in the reference's order: `choice` over the (crop_w, crop_h) pairs whose scale levels differ by at most
+    max_distort -- sizes int(min(h, w) * scale), snapped to the input size when within 3 of it -- then `choice` over fix_offsets, or
+    randint(0, w - crop_w), randint(0, h - crop_h) without fix_crop.  The box [x, y, x + crop_w - 1, y + crop_h - 1] is clipped to the
+    image as mmcv.imcrop does (a snapped size can exceed the frame).  -> the clipped patch (by, bx, bh, bw)."""
+    in_w, in_h = (input_size, input_size) if isinstance(input_size, int) else (int(input_size[0]), int(input_size[1]))
+    base = min(w, h)
+    sizes = [int(base * x) for x in (scales if scales is not None else [1, .875, .75, .66])]
+    crop_h = [in_h if abs(x - in_h) < 3 else x for x in sizes]
+    crop_w = [in_w if abs(x - in_w) < 3 else x for x in sizes]
+    pairs = [(cw, ch) for i, ch in enumerate(crop_h) for j, cw in enumerate(crop_w) if abs(i - j) <= max_distort]
+    cw, ch = rng.choice(pairs)
+    if not fix_crop:
+        x1 = rng.randint(0, w - cw)
+        y1 = rng.randint(0, h - ch)
+    else:
+        x1, y1 = rng.choice(fix_offsets(more_fix_crop, w, h, cw, ch))
+    x2, y2 = x1 + cw - 1, y1 + ch - 1
+    x1, x2 = (max(min(v, w - 1), 0) for v in (x1, x2))         # mmcv.bbox_clip
+    y1, y2 = (max(min(v, h - 1), 0) for v in (y1, y2))
+    return y1, x1, y2 - y1 + 1, x2 - x1 + 1
+
+
+def multi_scale_crop_rows(hs, ws, n_frames, input_size=224, scales=None, max_distort=1, fix_crop=True, more_fix_crop=True, flip_ratio=0.5,
+                          rng=random, np_rng=None):
+    """The TSN train recipe MultiScaleCrop(input_size, ...) -> Flip(flip_ratio) for one clip of n_frames hs x ws frames: the box on `rng`
+    (Python's random), then Flip's one np.random draw (`np_rng`); one box and one flip per clip, the patch resized to input_size.
+    -> (n_frames, 11) int32."""
+    by, bx, bh, bw = multi_scale_crop_box(hs, ws, input_size, scales, max_distort, fix_crop, more_fix_crop, rng)
+    rh, rw = _hw(input_size)
+    flip = int(flip_flag(flip_ratio, np_rng))
+    return _table([(hs, ws, by, bx, bh, bw, rh, rw, 0, 0, flip)] * n_frames)
+
+
+def ten_crop_rows(hs, ws, n_frames, crop_size=224, scale=None, keep_ratio=True):
+    """TenCrop(crop_size) (augmentations.py:563-591): 10 * n_frames rows -- for each of the five fix_offsets(False, ...) positions (four
+    corners, centre) the clip's plain crops, then the same crops mirrored; no resize, or `Resize(scale, keep_ratio)` in front when
+    `scale` is given (as test_rows).  The caller repeats the clip's frames ten times."""
+    rh, rw = (hs, ws) if scale is None else resized_hw(hs, ws, scale, keep_ratio)
+    ch, cw = _hw(crop_size)
+    if ch > rh or cw > rw:
+        raise ValueError("TenCrop %dx%d larger than the %dx%d frame" % (ch, cw, rh, rw))
+    return _table([(hs, ws, 0, 0, hs, ws, rh, rw, y0, x0, flip) for (x0, y0) in fix_offsets(False, rw, rh, cw, ch)
+                   for flip in (0, 1) for _ in range(n_frames)])
+
+
+def random_rescaled_crop_rows(hs, ws, n_frames, input_size, scale=(256, 320), rng=random):
+    """RandomRescaledCrop(input_size, scale) (augmentations.py:682-699), its axis naming kept: randint(*scale) is the short edge,
+    imrescale by the float factor max(edge / hs, edge / ws); then `w, h, _ = img.shape` makes "w" the ROW count, so randint(0, rows -
+    input_size[0]) offsets the rows and randint(0, cols - input_size[1]) the columns, and the output is input_size[0] rows by
+    input_size[1] columns (build the pipeline with crop_size=(input_size[1], input_size[0]) when they differ).  Draws on `rng`."""
+    n0, n1 = (input_size, input_size) if isinstance(input_size, int) else (int(input_size[0]), int(input_size[1]))
+    edge = float(rng.randint(*scale))
+    rw, rh = rescale_size(hs, ws, max(edge / hs, edge / ws))
+    oy = rng.randint(0, rh - n0)
+    ox = rng.randint(0, rw - n1)
+    return _table([(hs, ws, 0, 0, hs, ws, rh, rw, oy, ox, 0)] * n_frames)
+
+
+def center_crop_rows(hs, ws, n_frames, crop_size):
+    """CenterCrop(crop_size) with no Resize in front (augmentations.py:445-452)."""
+    ch, cw = _hw(crop_size)
+    if ch > hs or cw > ws:
+        raise ValueError("CenterCrop %dx%d larger than the %dx%d frame" % (ch, cw, hs, ws))
+    return _table([(hs, ws, 0, 0, hs, ws, hs, ws, (hs - ch) // 2, (ws - cw) // 2, 0)] * n_frames)
+
+
+_EIGVAL = (55.46, 4.794, 1.148)
+_EIGVEC = ((-0.5675, 0.7192, 0.4009), (-0.5808, -0.0045, -0.8140), (-0.5836, -0.6948, 0.4203))
+_TYIQ = ((0.299, 0.587, 0.114), (0.596, -0.274, -0.321), (0.211, -0.523, 0.311))
+_ITYIQ = ((1.0, 0.956, 0.621), (1.0, -0.272, -0.647), (1.0, -1.107, 1.705))
+
+
+def color_identity(n_frames):
+    """(n_frames, 12) float32 rows of the identity colour transform: M = I, b = 0."""
+    import numpy as np
+    return np.tile(np.concatenate([np.eye(3).reshape(-1), np.zeros(3)]).astype(np.float32), (n_frames, 1))
+
+
+def color_jitter_table(n_frames, color_space_aug=False, alphastd=0.1, eigval=None, eigvec=None, rng=random, np_rng=None):
+    """ColorJitter(color_space_aug, alphastd, eigval, eigvec).__call__ (augmentations.py:306-333) for one clip of n_frames frames as one
+    affine map q = M p + b per frame, p the (B, G, R) pixel in stored order -> (n_frames, 12) float32 rows M[0], M[1], M[2], b.
+    Every step of the reference is affine and nothing clips:
+      brightness  + float32(delta);  contrast  * float32(alpha);
+      saturation  alpha * p + (1 - alpha) * (0.299 p0 + 0.587 p1 + 0.114 p2), the grey weights on the channels in STORED order;
+      hue         p @ t, t = float32((ityiq @ bt @ tyiq).T), u, w = cos / sin(alpha * pi), alpha from (-18, 18) with no degree conversion;
+      lighting    + float32(eigvec * alpha @ eigval)[::-1], always.
+    Draws in the reference's order: with color_space_aug three `np.random.uniform` (`np_rng`) and one `random.uniform` (`rng`) per clip,
+    then per frame on `rng` the brightness coin, the order coin and one coin per step in the chosen order (contrast, saturation, hue --
+    or saturation, hue, contrast); last `np.random.normal(0, alphastd, size=3)`.  Composed in float64, rounded once to float32."""
+    import numpy as np
+    np_rng = np_rng if np_rng is not None else np.random
+    eigval = np.asarray(_EIGVAL if eigval is None else eigval, dtype=np.float64)
+    eigvec = np.asarray(_EIGVEC if eigvec is None else eigvec, dtype=np.float64)
+    maps = [(np.eye(3), np.zeros(3)) for _ in range(n_frames)]
+    if color_space_aug:
+        delta = float(np.float32(np_rng.uniform(-32, 32)))
+        c_alpha = float(np.float32(np_rng.uniform(0.6, 1.4)))
+        s_alpha = float(np_rng.uniform(0.6, 1.4))
+        h_alpha = rng.uniform(-18, 18)
+        grey = np.array([0.299, 0.587, 0.114], dtype=np.float32).astype(np.float64)
+        u, w = np.cos(h_alpha * np.pi), np.sin(h_alpha * np.pi)
+        bt = np.array([[1.0, 0.0, 0.0], [0.0, u, -w], [0.0, w, u]])
+        t = np.dot(np.dot(np.array(_ITYIQ), bt), np.array(_TYIQ)).T.astype(np.float32).astype(np.float64)
+        steps = {"contrast": c_alpha * np.eye(3), "saturation": s_alpha * np.eye(3) + (1.0 - s_alpha) * np.outer(np.ones(3), grey),
+                 "hue": t.T}                                   # (p @ t)[c] = sum_k t[k][c] p[k]
+        for i in range(n_frames):
+            m, b = maps[i]
+            if rng.uniform(0, 1) > 0.5:
+                b = b + delta
+            order = ("contrast", "saturation", "hue") if rng.uniform(0, 1) > 0.5 else ("saturation", "hue", "contrast")
+            for name in order:
+                if rng.uniform(0, 1) > 0.5:
+                    m, b = np.dot(steps[name], m), np.dot(steps[name], b)
+            maps[i] = (m, b)
+    alpha = np_rng.normal(0, alphastd, size=(3,))
+    bgr = np.array(np.dot(eigvec * alpha, eigval)).astype(np.float32)[::-1].astype(np.float64)
+    return np.stack([np.concatenate([m.reshape(-1), b + bgr]) for m, b in maps]).astype(np.float32)
+
+
+def jitter_rows(rows, color=None):
+    """(n, 11) int32 geometry rows + (n, 12) float32 colour rows (default: color_identity) -> ONE (n, 23) int32 table, the colour
+    coefficients as their fp32 bit patterns, so that geometry and colour travel together through `window=` and `collate_jitter_frames`."""
+    import numpy as np
+    rows = _table(rows)
+    color = color_identity(rows.shape[0]) if color is None else np.ascontiguousarray(np.asarray(color, dtype=np.float32)).reshape(-1, COLOR_COLS)
+    if color.shape[0] != rows.shape[0]:
+        raise ValueError("jitter_rows: %d colour rows for %d geometry rows" % (color.shape[0], rows.shape[0]))
+    if not np.isfinite(color).all():
+        raise ValueError("jitter_rows: colour coefficients must be finite")
+    return np.concatenate([rows, color.view(np.int32)], axis=1)
+
+
+def split_jitter_rows(table):
+    """The inverse of jitter_rows on the host: (n, 23) int32 -> ((n, 11) int32, (n, 12) float32), bit for bit."""
+    import numpy as np
+    table = np.ascontiguousarray(np.asarray(table, dtype=np.int32)).reshape(-1, JITTER_COLS)
+    return table[:, :RESAMPLE_COLS].copy(), table[:, RESAMPLE_COLS:].copy().view(np.float32)
+
+
+def collate_jitter_frames(groups, pad_to=None):
+    """collate_frames for jitter_rows tables: groups of (frames, (T, 23) table); an (T, 11) table is taken as "no jitter".
+    -> (frames (B, T, Hs, Ws, 3) uint8, rows (B * T, 23) int32), CPU tensors."""
+    import numpy as np
+    full = []
+    for f, r in groups:
+        r = np.asarray(r, dtype=np.int32)
+        full.append((f, jitter_rows(r) if r.shape[-1] == RESAMPLE_COLS else r))
+    return collate_frames(full, pad_to, cols=JITTER_COLS)
+
+
+class JitterFramePipeline(ResamplingFramePipeline):
+    """ResamplingFramePipeline with ColorJitter between the resample and Normalize (mvf_frames_resample_color_u8): rows are ONE int32
+    table of 23 columns per frame, the 11 geometry columns followed by the 12 colour coefficients' fp32 bit patterns (jitter_rows), so
+    the engines carry it through `input_pipeline` / `window=` as they carry the 11-column table.  11-column rows mean "no jitter" and
+    give ResamplingFramePipeline's output bit for bit.  Same constructor, `crop_hw`, `to_nchw` and `to_stem`."""
+
+    def _split(self, rows, n, hs, ws):
+        if rows is None:
+            raise ValueError("JitterFramePipeline needs one 23-column (or 11-column) int32 row per frame")
+        rows = torch.as_tensor(rows).to(device="cuda", dtype=torch.int32)
+        cols = rows.shape[-1] if rows.dim() > 1 else 0
+        if cols == RESAMPLE_COLS:
+            return self._window(rows, n, hs, ws), None
+        if cols != JITTER_COLS:
+            raise ValueError("JitterFramePipeline rows must have %d or %d columns, got %s" % (JITTER_COLS, RESAMPLE_COLS, tuple(rows.shape)))
+        rows = rows.reshape(-1, JITTER_COLS)
+        geo = self._window(rows[:, :RESAMPLE_COLS], n, hs, ws)
+        color = rows[:, RESAMPLE_COLS:].contiguous().view(torch.float32)
+        if not bool(torch.isfinite(color).all()):
+            raise ValueError("JitterFramePipeline: colour coefficients must be finite")
+        return geo, color
+
+    def to_nchw(self, frames, rows):
+        """-> (n, 3, h, w) fp32, what the reference's crop / resize + Flip + ColorJitter + Normalize + FormatShape produce."""
+        f = self._frames(frames)
+        n, hs, ws = f.shape[:3]
+        r, col = self._split(rows, n, hs, ws)
+        h, w = self.crop_hw
+        out = torch.empty(n, 3, h, w, dtype=torch.float32, device=f.device)
+        check(lib.mvf_frames_resample_color_u8(f.data_ptr(), n, hs, ws, r.data_ptr(), col.data_ptr() if col is not None else None, h, w,
+                                               self.mean, self.std, int(self.to_rgb), int(self.div_255), 0, w, None, out.data_ptr(), 0,
+                                               torch.cuda.current_stream().cuda_stream), "mvf_frames_resample_color_u8")
+        return out
+
+    def to_stem(self, frames, rows, pad, wp, dtype, out=None):
+        """-> (n, h + 2 pad, wp, 4) `dtype`, the stem conv's operand (FramePipeline.to_stem), with the resample and the jitter in front."""
+        f = self._frames(frames)
+        n, hs, ws = f.shape[:3]
+        r, col = self._split(rows, n, hs, ws)
+        h, w = self.crop_hw
+        if out is None:
+            out = torch.empty(n, h + 2 * pad, wp, 4, dtype=dtype, device=f.device)
+        check(lib.mvf_frames_resample_color_u8(f.data_ptr(), n, hs, ws, r.data_ptr(), col.data_ptr() if col is not None else None, h, w,
+                                               self.mean, self.std, int(self.to_rgb), int(self.div_255), pad, wp, out.data_ptr(), None,
+                                               _DT[dtype], torch.cuda.current_stream().cuda_stream), "mvf_frames_resample_color_u8")
         return out
 
 

@@ -92,7 +92,8 @@ class Recognizer2D(nn.Module):
         int32 of per-frame (y0, x0, flip) -- instead of the normalised fp32 tensor: `pipeline` is a preprocess.FramePipeline
         (the config's img_norm_cfg + crop size); crop, flip, Normalize and FormatShape then run inside the stem's input kernel.
         With a preprocess.ResamplingFramePipeline, `window=` is the (frames, 11) int32 row table (train_rows / val_rows / test_rows,
-        collate_frames) and Resize / RandomResizedCrop run in that kernel too: frames of any resolution, zero padded to one Hs x Ws."""
+        collate_frames) and Resize / RandomResizedCrop run in that kernel too: frames of any resolution, zero padded to one Hs x Ws.
+        With a preprocess.JitterFramePipeline, `window=` is the (frames, 23) int32 table of jitter_rows (geometry + ColorJitter's map)."""
         self.input_pipeline = pipeline
         self.backbone.input_pipeline = pipeline
         return self
