@@ -238,6 +238,16 @@ int mvf_frames_resample_u8(const unsigned char* frames_hwc, int n, int hs, int w
 int mvf_frames_resample_color_u8(const unsigned char* frames_hwc, int n, int hs, int ws, const int* rows, const float* color, int h, int w,
                                  const float* mean3, const float* std3, int to_rgb, int div_255, int pad, int wp, void* out_stem,
                                  float* out_nchw, int dtype, void* stream);
+/* mvf_frames_resample_color_u8 with a frame index in front, so that several output images share one decoded frame [whole-video testing:
+ * SampleFrames(num_clips) clips that overlap or clamp, ThreeCrop / TenCrop augmentations.py:465-596]: frames_hwc = (n_src, hs, ws, 3),
+ * src_index = device int32 (n_out,), rows = (n_out, 11), color = (n_out, 12) or NULL; output image i is cut from frame src_index[i],
+ * whose real size is row i's (hs_i, ws_i); the outputs hold n_out images.  The arithmetic per pixel is mvf_frames_resample_color_u8's:
+ * the result equals that export run on the gathered batch frames_hwc[src_index], bit for bit, and src_index == NULL means i -> i
+ * (n_src must equal n_out then).  The index contents are NOT checked here (the caller validates 0 <= src_index[i] < n_src, as for the
+ * rows: an out-of-range index reads out of bounds).  Everything else as mvf_frames_resample_color_u8. */
+int mvf_frames_gather_resample_u8(const unsigned char* frames_hwc, int n_src, int hs, int ws, const int* src_index, int n_out, const int* rows,
+                                  const float* color, int h, int w, const float* mean3, const float* std3, int to_rgb, int div_255, int pad,
+                                  int wp, void* out_stem, float* out_nchw, int dtype, void* stream);
 
 /* MaxPool2d(3, stride 2, pad 1) on NHWC (resnet.py:431,484). */
 int mvf_maxpool3x3s2_nhwc(const void* x, int n, int h, int w, int c, void* y, int dtype, void* stream);

@@ -80,10 +80,13 @@ __global__ void frames_prep_kernel(const unsigned char* frames, int n, int hs, i
 // resample and Normalize as q = M p + b on the resampled uint8 triple in STORED channel order: color = (n, 12) fp32 rows
 // M[0][0..2], M[1][0..2], M[2][0..2], b[0..2], block-uniform like the int row, read once per block.  Every product and sum is rounded
 // to fp32 on its own, summed left to right, so M = I gives p + b rounded once (the reference's float32 `img + bgr`).
+// src_index (mvf_frames_gather_resample_u8): output image `img` is cut from frame src_index[img] instead of frame img, so the crops and
+// clips of a video share its decoded frames; block-uniform like the row (blockIdx only: a scalar load), read once per block, and it
+// enters nothing but the two source-row base addresses.  NULL = img.
 constexpr int RS_COLS = 11, CJ_COLS = 12;
 template <typename ET, bool COLOR>
-__global__ void frames_resample_kernel(const unsigned char* frames, int hs, int ws, const int* rows, const float* color, int h, int w,
-                                       FramePrep fp, int pad, int hp, int wp, ET* out_stem, float* out_nchw) {
+__global__ void frames_resample_kernel(const unsigned char* frames, int hs, int ws, const int* src_index, const int* rows, const float* color,
+                                       int h, int w, FramePrep fp, int pad, int hp, int wp, ET* out_stem, float* out_nchw) {
 #pragma clang fp contract(off)
     const int orow = blockIdx.x, img = orow / hp, yo = orow - img * hp;
     float cm[CJ_COLS];
@@ -111,8 +114,9 @@ __global__ void frames_resample_kernel(const unsigned char* frames, int hs, int 
         y0 = min(max(sy, 0), bh - 1);
         y1 = min(max(sy + 1, 0), bh - 1);
     }
-    const unsigned char* s0 = frames + (((long)img * hs + by + y0) * ws + bx) * 3;
-    const unsigned char* s1 = frames + (((long)img * hs + by + y1) * ws + bx) * 3;
+    const int src = src_index ? src_index[img] : img;
+    const unsigned char* s0 = frames + (((long)src * hs + by + y0) * ws + bx) * 3;
+    const unsigned char* s1 = frames + (((long)src * hs + by + y1) * ws + bx) * 3;
     const double scx = 1.0 / ((double)rw / bw);
     for (int xo = threadIdx.x; xo < wp; xo += blockDim.x) {
         const int iw = xo - pad;
@@ -287,12 +291,14 @@ inline int grid_for(long total, int per_block = 256, int cap = 256 * 32) {
     return (int)std::min<long>((total + per_block - 1) / per_block, cap);
 }
 
-// mvf_frames_resample_u8 (color == nullptr) and mvf_frames_resample_color_u8: one validation, one launch
-int frames_resample(const char* who, const unsigned char* frames_hwc, int n, int hs, int ws, const int* rows, const float* color, int h, int w,
-                    const float* mean3, const float* std3, int to_rgb, int div_255, int pad, int wp, void* out_stem, float* out_nchw,
-                    int dtype, void* stream) {
-    MVF_REQUIRE(frames_hwc && rows && mean3 && std3 && (out_stem || out_nchw) && n > 0 && hs > 0 && ws > 0 && h > 0 && w > 0 && pad >= 0,
+// mvf_frames_resample_u8 (color == nullptr), mvf_frames_resample_color_u8 and mvf_frames_gather_resample_u8 (n = output images, of
+// n_src source frames): one validation, one launch
+int frames_resample(const char* who, const unsigned char* frames_hwc, int n_src, int n, int hs, int ws, const int* src_index, const int* rows,
+                    const float* color, int h, int w, const float* mean3, const float* std3, int to_rgb, int div_255, int pad, int wp,
+                    void* out_stem, float* out_nchw, int dtype, void* stream) {
+    MVF_REQUIRE(frames_hwc && rows && mean3 && std3 && (out_stem || out_nchw) && n_src > 0 && n > 0 && hs > 0 && ws > 0 && h > 0 && w > 0 && pad >= 0,
                 MVF_EINVAL, "%s: bad argument", who);
+    MVF_REQUIRE(src_index || n_src == n, MVF_EINVAL, "%s: n_src=%d != n_out=%d without src_index", who, n_src, n);
     MVF_REQUIRE(!out_stem || wp >= w + 2 * pad, MVF_EINVAL, "%s: wp=%d < w + 2*pad", who, wp);
     MVF_REQUIRE(dtype == MVF_F32 || dtype == MVF_BF16, MVF_EINVAL, "%s: bad dtype", who);
     FramePrep fp;
@@ -309,17 +315,17 @@ int frames_resample(const char* who, const unsigned char* frames_hwc, int n, int
     const dim3 grid(n * hp);
     const hipStream_t st = (hipStream_t)stream;
     if (dtype == MVF_F32 && !color)
-        hipLaunchKernelGGL((frames_resample_kernel<float, false>), grid, dim3(256), 0, st, frames_hwc, hs, ws, rows, color, h, w, fp, p, hp, wpp,
-                           (float*)out_stem, out_nchw);
+        hipLaunchKernelGGL((frames_resample_kernel<float, false>), grid, dim3(256), 0, st, frames_hwc, hs, ws, src_index, rows, color, h, w, fp, p,
+                           hp, wpp, (float*)out_stem, out_nchw);
     else if (dtype == MVF_F32)
-        hipLaunchKernelGGL((frames_resample_kernel<float, true>), grid, dim3(256), 0, st, frames_hwc, hs, ws, rows, color, h, w, fp, p, hp, wpp,
-                           (float*)out_stem, out_nchw);
+        hipLaunchKernelGGL((frames_resample_kernel<float, true>), grid, dim3(256), 0, st, frames_hwc, hs, ws, src_index, rows, color, h, w, fp, p,
+                           hp, wpp, (float*)out_stem, out_nchw);
     else if (!color)
-        hipLaunchKernelGGL((frames_resample_kernel<bf16_t, false>), grid, dim3(256), 0, st, frames_hwc, hs, ws, rows, color, h, w, fp, p, hp, wpp,
-                           (bf16_t*)out_stem, out_nchw);
+        hipLaunchKernelGGL((frames_resample_kernel<bf16_t, false>), grid, dim3(256), 0, st, frames_hwc, hs, ws, src_index, rows, color, h, w, fp, p,
+                           hp, wpp, (bf16_t*)out_stem, out_nchw);
     else
-        hipLaunchKernelGGL((frames_resample_kernel<bf16_t, true>), grid, dim3(256), 0, st, frames_hwc, hs, ws, rows, color, h, w, fp, p, hp, wpp,
-                           (bf16_t*)out_stem, out_nchw);
+        hipLaunchKernelGGL((frames_resample_kernel<bf16_t, true>), grid, dim3(256), 0, st, frames_hwc, hs, ws, src_index, rows, color, h, w, fp, p,
+                           hp, wpp, (bf16_t*)out_stem, out_nchw);
     MVF_LAUNCH_CHECK();
     return MVF_OK;
 }
@@ -372,15 +378,22 @@ int mvf_frames_prep_u8(const unsigned char* frames_hwc, int n, int hs, int ws, c
 int mvf_frames_resample_u8(const unsigned char* frames_hwc, int n, int hs, int ws, const int* rows, int h, int w,
                            const float* mean3, const float* std3, int to_rgb, int div_255, int pad, int wp, void* out_stem,
                            float* out_nchw, int dtype, void* stream) {
-    return frames_resample("frames_resample_u8", frames_hwc, n, hs, ws, rows, nullptr, h, w, mean3, std3, to_rgb, div_255, pad, wp, out_stem,
+    return frames_resample("frames_resample_u8", frames_hwc, n, n, hs, ws, nullptr, rows, nullptr, h, w, mean3, std3, to_rgb, div_255, pad, wp, out_stem,
                            out_nchw, dtype, stream);
 }
 
 int mvf_frames_resample_color_u8(const unsigned char* frames_hwc, int n, int hs, int ws, const int* rows, const float* color, int h, int w,
                                  const float* mean3, const float* std3, int to_rgb, int div_255, int pad, int wp, void* out_stem,
                                  float* out_nchw, int dtype, void* stream) {
-    return frames_resample("frames_resample_color_u8", frames_hwc, n, hs, ws, rows, color, h, w, mean3, std3, to_rgb, div_255, pad, wp,
-                           out_stem, out_nchw, dtype, stream);
+    return frames_resample("frames_resample_color_u8", frames_hwc, n, n, hs, ws, nullptr, rows, color, h, w, mean3, std3, to_rgb, div_255, pad,
+                           wp, out_stem, out_nchw, dtype, stream);
+}
+
+int mvf_frames_gather_resample_u8(const unsigned char* frames_hwc, int n_src, int hs, int ws, const int* src_index, int n_out, const int* rows,
+                                  const float* color, int h, int w, const float* mean3, const float* std3, int to_rgb, int div_255, int pad,
+                                  int wp, void* out_stem, float* out_nchw, int dtype, void* stream) {
+    return frames_resample("frames_gather_resample_u8", frames_hwc, n_src, n_out, hs, ws, src_index, rows, color, h, w, mean3, std3, to_rgb,
+                           div_255, pad, wp, out_stem, out_nchw, dtype, stream);
 }
 
 int mvf_maxpool3x3s2_nhwc(const void* x, int n, int h, int w, int c, void* y, int dtype, void* stream) {

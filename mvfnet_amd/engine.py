@@ -227,10 +227,17 @@ class BackboneEngine(object):
         window = getattr(self, "input_window", None) if u8 else None
         ns = getattr(self, "streams", 1)
         T = n_segment or self._n_segment()
-        clips = x_nchw.shape[0] // max(T, 1)
-        if ns > 1 and stages is None and clips >= 2 * ns and x_nchw.shape[0] % T == 0:
+        n = self.n_images(x_nchw, window)
+        clips = n // max(T, 1)
+        if ns > 1 and stages is None and clips >= 2 * ns and n % T == 0:
             return self._forward_multi(x_nchw, ns, T, window)
         return self._forward_one(x_nchw, stages, window)
+
+    def n_images(self, x, window):
+        """Images the input makes: its leading dimension, or -- uint8 frames with a gather table (preprocess.GatherFramePipeline: several
+        images share a decoded frame) -- the table's row count."""
+        n_out = getattr(self.input_pipeline, "n_out", None) if x.dtype == torch.uint8 else None
+        return n_out(x, window) if n_out is not None else x.shape[0]
 
     def _n_segment(self):
         for b in self.blocks:
@@ -254,7 +261,10 @@ class BackboneEngine(object):
             self._pool = []
             for _ in range(ns):                      # chains on streams that share a hardware queue would just run in turn
                 self._pool.append(concurrent_stream(cur, avoid=self._pool))
-        clips = x.shape[0] // T
+        n = self.n_images(x, window)
+        # a gather table names its source frames: every chain gets the whole frame tensor and its own slice of the table
+        gather = x.dtype == torch.uint8 and window is not None and getattr(self.input_pipeline, "gathers", lambda rows: False)(window)
+        clips = n // T
         per = (clips + ns - 1) // ns
         # every chain's last conv writes its clips straight into one feature tensor (allocated on the caller's stream): no
         # concatenation copy afterwards
@@ -263,7 +273,7 @@ class BackboneEngine(object):
         else:
             hin, win = x.shape[2], x.shape[3]
         hf, wf, cf = self.feature_shape(hin, win)
-        feat = torch.empty(x.shape[0], hf, wf, cf, dtype=self.dtype, device=x.device)
+        feat = torch.empty(n, hf, wf, cf, dtype=self.dtype, device=x.device)
         used = []
         for i, st in enumerate(self._pool):
             lo, hi = i * per * T, min((i + 1) * per, clips) * T
@@ -271,7 +281,7 @@ class BackboneEngine(object):
                 continue
             st.wait_stream(cur)
             with torch.cuda.stream(st):
-                self._forward_one(x[lo:hi], None, None if window is None else window.reshape(-1, window.shape[-1])[lo:hi], out=feat[lo:hi])
+                self._forward_one(x if gather else x[lo:hi], None, None if window is None else window.reshape(-1, window.shape[-1])[lo:hi], out=feat[lo:hi])
             used.append(st)
         for st in used:
             cur.wait_stream(st)
@@ -282,7 +292,7 @@ class BackboneEngine(object):
         if x_nchw.dtype == torch.uint8:              # decoded (nt, Hs, Ws, 3) frames: crop / flip / normalise fused into the stem prep
             if self.input_pipeline is None:
                 raise RuntimeError("uint8 frames need engine.input_pipeline = preprocess.FramePipeline(...)")
-            nt = x_nchw.shape[0]
+            nt = self.n_images(x_nchw, window)
             h, w = self.input_pipeline.crop_hw
             hp, wp = h + 2 * pad, (w + 2 * pad + 2 + 1) // 2 * 2
             xp = self.input_pipeline.to_stem(x_nchw, window, pad, wp, self.dtype)
@@ -327,6 +337,14 @@ class HeadEngine(object):
         return self.fc.bias.detach().to(device=self.device, dtype=torch.float32).contiguous() if self.fc.bias is not None else None
 
     def scores(self, feat, num_seg):
+        return self._pool_fc(feat, num_seg)[1]
+
+    def features(self, feat, num_seg):
+        """TSNClsHead(extract_feat=True) (tsn_clshead.py:88-98, :110-112): the consensus of the pooled features, (clips, in_channels) fp32
+        -- the mean over the clip's num_seg * h * w positions, which is the buffer mvf_head_pool_fc pools into before its FC."""
+        return self._pool_fc(feat, num_seg)[0]
+
+    def _pool_fc(self, feat, num_seg):
         nt, h, w, c = feat.shape
         if c != self.c or nt % num_seg:
             raise ValueError("head: features %s do not match in_channels=%d / num_seg=%d" % (tuple(feat.shape), self.c, num_seg))
@@ -336,7 +354,7 @@ class HeadEngine(object):
         wgt, bias = self.w, self.b            # kept alive until the launch is queued
         check(lib.mvf_head_pool_fc(_p(feat), clips, num_seg, h * w, c, _p(wgt), _p(bias), self.classes, _p(pooled), _p(out),
                                    _DT[feat.dtype], _stream()), "mvf_head_pool_fc")
-        return out
+        return pooled, out
 
     def average(self, scores, average_clips):
         if average_clips not in self.KINDS:

@@ -8,6 +8,9 @@ forward(x, num_seg): spatial average pool -> (dropout) -> new_fc -> reshape(-1, 
 segments (tsn_clshead.py:71-98); with fcn_testing the 1x1x1 Conv3d + mean[T,H,W] branch (:99-117).  Both are
 "mean over the clip's T*H*W positions, then FC" up to fp rounding (pooling, consensus and FC are linear;
 SURVEY.md 2.2 measured 1e-5), which is how the HIP head kernel computes them in eval mode.
+
+extract_feat=True (the reference's feature_extractor.py entry point; tsn_clshead.py:89-90, :110-112): eval-mode forward returns that mean
+itself, (clips, in_channels) fp32, for both branches; in training mode it is refused.
 """
 import torch
 import torch.nn as nn
@@ -24,8 +27,8 @@ class TSNClsHead(nn.Module):
         if spatial_type != "avg" or consensus_cfg.get("type") != "avg" or consensus_cfg.get("dim", 1) != 1:
             raise NotImplementedError("TSNClsHead: only spatial_type='avg' with the 'avg' consensus over dim 1 is built "
                                       "(the MVFNet configuration)")
-        if with_avg_pool or extract_feat or temporal_feature_size != 1 or spatial_feature_size != 1:
-            raise NotImplementedError("TSNClsHead: with_avg_pool / extract_feat / feature sizes != 1 are not built")
+        if with_avg_pool or temporal_feature_size != 1 or spatial_feature_size != 1:
+            raise NotImplementedError("TSNClsHead: with_avg_pool / feature sizes != 1 are not built")
         self.spatial_type, self.spatial_size = spatial_type, spatial_size
         self.consensus_type = "avg"
         self.dropout_ratio, self.in_channels, self.num_classes, self.init_std = dropout_ratio, in_channels, num_classes, init_std
@@ -58,7 +61,10 @@ class TSNClsHead(nn.Module):
         self._engine = None
 
     def forward(self, x, num_seg):
-        """x: (N*T, C, h, w) features [or (clips, C, T, h, w) with fcn_testing] -> (clips, num_classes) scores."""
+        """x: (N*T, C, h, w) features [or (clips, C, T, h, w) with fcn_testing] -> (clips, num_classes) scores, or with extract_feat the
+        (clips, in_channels) consensus of the pooled features."""
+        if self.extract_feat and self.training:
+            raise NotImplementedError("TSNClsHead: extract_feat=True is an eval-mode path (feature extraction); call .eval() first")
         if not x.is_cuda:
             raise RuntimeError("TSNClsHead: mvfnet_amd runs on MI355X tensors only; no CPU fallback (tests use oracle/)")
         if self.training and self.dropout is not None and torch.is_grad_enabled():
@@ -70,6 +76,8 @@ class TSNClsHead(nn.Module):
             feat = x.permute(0, 2, 3, 1)                     # logical NCHW -> physical NHWC (no copy if channels-last)
         if not feat.is_contiguous():
             feat = feat.contiguous()
+        if self.extract_feat:
+            return self.engine().features(feat, num_seg)
         return self.engine().scores(feat, num_seg)
 
     def loss(self, cls_score, labels):

@@ -15,7 +15,11 @@ on the host.
 transform per frame between the resample and Normalize (`color_jitter_table`: 12 floats, the reference's draws in its order), and the
 geometry of `MultiScaleCrop`, `TenCrop`, `RandomRescaledCrop` and a bare `CenterCrop` as the same 11-column rows
 (`multi_scale_crop_rows` / `ten_crop_rows` / `random_rescaled_crop_rows` / `center_crop_rows`); `jitter_rows` packs both into one
-23-column int32 table that travels through `window=` (`collate_jitter_frames`)."""
+23-column int32 table that travels through `window=` (`collate_jitter_frames`).
+
+`GatherFramePipeline` adds whole-video testing from ONE upload of a video's distinct decoded frames (`mvf_frames_gather_resample_u8`): a
+trailing `src` column (12 or 24 columns, `gather_rows`) names the source frame every output image is cut from, so the clips of
+`SampleFrames(num_clips)` that share or repeat frames and the crops of `ThreeCrop` / `TenCrop` read the same bytes (`video_test_table`)."""
 import ctypes
 import math
 import random
@@ -520,6 +524,124 @@ class JitterFramePipeline(ResamplingFramePipeline):
                                                self.mean, self.std, int(self.to_rgb), int(self.div_255), pad, wp, out.data_ptr(), None,
                                                _DT[dtype], torch.cuda.current_stream().cuda_stream), "mvf_frames_resample_color_u8")
         return out
+
+
+# ---- whole-video testing: several output images per decoded frame --------------------------------------------------------------------
+def gather_rows(rows, src):
+    """(n, 11) or (n, 23) int32 rows + (n,) source-frame numbers -> ONE (n, 12) or (n, 24) int32 table, `src` as the trailing column:
+    output image i is cut from frame src[i] of the frames handed to GatherFramePipeline (row i describes THAT frame: its hs_i, ws_i)."""
+    import numpy as np
+    rows = np.asarray(rows, dtype=np.int32)
+    if rows.ndim != 2 or rows.shape[1] not in (RESAMPLE_COLS, JITTER_COLS):
+        raise ValueError("gather_rows: rows must have %d or %d columns, got %s" % (RESAMPLE_COLS, JITTER_COLS, rows.shape))
+    src = np.asarray(src).reshape(-1)
+    if src.shape[0] != rows.shape[0]:
+        raise ValueError("gather_rows: %d source indices for %d rows" % (src.shape[0], rows.shape[0]))
+    if src.size and (src.min() < 0 or src.max() > np.iinfo(np.int32).max):
+        raise ValueError("gather_rows: source indices must be non-negative int32")
+    return np.concatenate([rows, src.astype(np.int32)[:, None]], axis=1)
+
+
+def split_gather_rows(table):
+    """The inverse of gather_rows on the host: (n, 12) or (n, 24) int32 -> ((n, 11) or (n, 23) int32, (n,) int32 src)."""
+    import numpy as np
+    table = np.asarray(table, dtype=np.int32)
+    if table.ndim != 2 or table.shape[1] not in (RESAMPLE_COLS + 1, JITTER_COLS + 1):
+        raise ValueError("split_gather_rows: the table must have %d or %d columns, got %s" % (RESAMPLE_COLS + 1, JITTER_COLS + 1, table.shape))
+    return table[:, :-1].copy(), table[:, -1].copy()
+
+
+def video_test_table(frame_inds, hs, ws, rows_fn=test_rows, **recipe):
+    """One video's test-time input from its DISTINCT frames.  frame_inds: what sample_frame_inds(..., test_mode=True) returned (clip-major,
+    frame-minor; clips may share frames, clamped indices repeat); hs x ws: the decoded frame size; rows_fn(hs, ws, n_frames, **recipe):
+    the geometry of the recipe over the whole sampled list -- test_rows (Resize + ThreeCrop, the shipped test recipe), val_rows (Resize +
+    CenterCrop), ten_crop_rows, center_crop_rows, resize_rows.
+    -> (the sorted distinct frame numbers to decode, the (crops * len(frame_inds), 12) gather table).  Oversampling crops are crop-major
+    over the WHOLE sampled list and frame-minor inside it (augmentations.py:512-530, :544-596), so image k * len(frame_inds) + j is crop k
+    of sampled frame j and reshaping the outputs to (-1, n_segment) yields the reference's clips; its src is the position of
+    frame_inds[j] among the distinct frames."""
+    import numpy as np
+    frame_inds = np.asarray(frame_inds).reshape(-1)
+    if frame_inds.size == 0:
+        raise ValueError("video_test_table: no frame indices")
+    distinct, inverse = np.unique(frame_inds, return_inverse=True)
+    rows = rows_fn(hs, ws, frame_inds.size, **recipe)
+    if rows.shape[0] % frame_inds.size:
+        raise ValueError("video_test_table: %d rows for %d sampled frames" % (rows.shape[0], frame_inds.size))
+    return distinct, gather_rows(rows, np.tile(inverse.reshape(-1), rows.shape[0] // frame_inds.size))
+
+
+class GatherFramePipeline(JitterFramePipeline):
+    """JitterFramePipeline whose output images name their source frame (mvf_frames_gather_resample_u8): the table is the 11- or 23-column
+    table plus one trailing `src` column (gather_rows, video_test_table), one row per OUTPUT image, and `frames` are the n_src distinct
+    decoded frames; image i is cut from frames[src_i].  An 11- or 23-column table means "no gather" (one image per frame) and gives
+    JitterFramePipeline's output bit for bit.  Same constructor, `crop_hw`, `to_nchw` and `to_stem`; `n_out` tells the engines how many
+    images a (frames, table) pair makes."""
+
+    @staticmethod
+    def _cols(rows):
+        return int(rows.shape[-1]) if rows is not None and hasattr(rows, "shape") and len(rows.shape) > 1 else 0
+
+    def gathers(self, rows):
+        """True when `rows` carries the src column (12 or 24 columns)."""
+        return self._cols(rows) in (RESAMPLE_COLS + 1, JITTER_COLS + 1)
+
+    def n_out(self, frames, rows):
+        """The number of images (frames, rows) produce: the table's row count with a src column, the frame count otherwise."""
+        if self.gathers(rows):
+            return int(rows.reshape(-1, rows.shape[-1]).shape[0])
+        n = 1
+        for d in frames.shape[:-3]:
+            n *= int(d)
+        return n
+
+    def _gather(self, rows, n_src, hs, ws):
+        if rows is None:
+            raise ValueError("GatherFramePipeline needs one int32 row per output image (gather_rows / video_test_table)")
+        rows = torch.as_tensor(rows).to(device="cuda", dtype=torch.int32)
+        cols = self._cols(rows)
+        if cols not in (RESAMPLE_COLS + 1, JITTER_COLS + 1):
+            raise ValueError("GatherFramePipeline rows must have %d or %d columns (or %d / %d: no gather), got %s"
+                             % (RESAMPLE_COLS + 1, JITTER_COLS + 1, RESAMPLE_COLS, JITTER_COLS, tuple(rows.shape)))
+        rows = rows.reshape(-1, cols)
+        n = rows.shape[0]
+        if n < 1:
+            raise ValueError("GatherFramePipeline: an empty table")
+        src = rows[:, -1].contiguous()
+        bad = (src < 0) | (src >= n_src)
+        if bool(bad.any()):
+            i = int(bad.nonzero()[0, 0])
+            raise ValueError("row %d: source frame %d is not one of the %d frames" % (i, int(src[i]), n_src))
+        geo, color = self._split(rows[:, :-1], n, hs, ws)      # every frame shares the hs x ws padded extent: the parent's patch check holds per src
+        return geo, color, src
+
+    def _run(self, frames, rows, pad, wp, dtype, out=None, nchw=False):
+        f = self._frames(frames)
+        n_src, hs, ws = f.shape[:3]
+        r, col, src = self._gather(rows, n_src, hs, ws)
+        n, (h, w) = r.shape[0], self.crop_hw
+        shape = (n, 3, h, w) if nchw else (n, h + 2 * pad, wp, 4)
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=f.device)
+        elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous():
+            raise ValueError("GatherFramePipeline: the output buffer %s %s does not hold the table's %d images %s" % (out.dtype, tuple(out.shape), n, shape))
+        check(lib.mvf_frames_gather_resample_u8(f.data_ptr(), n_src, hs, ws, src.data_ptr(), n, r.data_ptr(), col.data_ptr() if col is not None else None,
+                                                h, w, self.mean, self.std, int(self.to_rgb), int(self.div_255), pad, wp,
+                                                None if nchw else out.data_ptr(), out.data_ptr() if nchw else None, _DT[dtype],
+                                                torch.cuda.current_stream().cuda_stream), "mvf_frames_gather_resample_u8")
+        return out
+
+    def to_nchw(self, frames, rows):
+        """-> (n_out, 3, h, w) fp32: JitterFramePipeline.to_nchw of frames[src] with the table's other columns."""
+        if self._cols(rows) in (RESAMPLE_COLS, JITTER_COLS):
+            return super().to_nchw(frames, rows)
+        return self._run(frames, rows, 0, self.crop_hw[1], torch.float32, nchw=True)
+
+    def to_stem(self, frames, rows, pad, wp, dtype, out=None):
+        """-> (n_out, h + 2 pad, wp, 4) `dtype`, the stem conv's operand (FramePipeline.to_stem) for the table's images."""
+        if self._cols(rows) in (RESAMPLE_COLS, JITTER_COLS):
+            return super().to_stem(frames, rows, pad, wp, dtype, out=out)
+        return self._run(frames, rows, pad, wp, dtype, out=out)
 
 
 # ---- frame-index arithmetic (host side; reference codes/datasets/pipelines/loading.py:11-131) ------------------------------------

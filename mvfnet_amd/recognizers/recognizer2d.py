@@ -93,7 +93,10 @@ class Recognizer2D(nn.Module):
         (the config's img_norm_cfg + crop size); crop, flip, Normalize and FormatShape then run inside the stem's input kernel.
         With a preprocess.ResamplingFramePipeline, `window=` is the (frames, 11) int32 row table (train_rows / val_rows / test_rows,
         collate_frames) and Resize / RandomResizedCrop run in that kernel too: frames of any resolution, zero padded to one Hs x Ws.
-        With a preprocess.JitterFramePipeline, `window=` is the (frames, 23) int32 table of jitter_rows (geometry + ColorJitter's map)."""
+        With a preprocess.JitterFramePipeline, `window=` is the (frames, 23) int32 table of jitter_rows (geometry + ColorJitter's map).
+        With a preprocess.GatherFramePipeline (forward_test only), `img_group` holds a video's DISTINCT decoded frames and `window=` is the
+        (images, 12) or (images, 24) int32 table of gather_rows / video_test_table: one row per output image, its trailing `src` column
+        naming the frame the image is cut from, so clips and oversampling crops share one upload; 11 / 23 columns mean "no gather"."""
         self.input_pipeline = pipeline
         self.backbone.input_pipeline = pipeline
         return self
@@ -117,9 +120,16 @@ class Recognizer2D(nn.Module):
     def forward_train(self, imgs, labels, **kwargs):
         """imgs [B, T, 3, H, W], labels [B, 1] -> {'loss_cls': scalar tensor} (reference recognizer2d.py:132-149).
         The returned loss supports .backward(): gradients land in the parameters' .grad (copies of the engine's flat gradient
-        buffer; after engine.attach_grads() the .grad tensors ARE views of it), as the reference's DistOptimizerHook expects."""
+        buffer; after engine.attach_grads() the .grad tensors ARE views of it), as the reference's DistOptimizerHook expects.
+        A gather table (preprocess.gather_rows: a `src` column) is refused with a ValueError: training makes one image per frame."""
         if not imgs.is_cuda:
             raise RuntimeError("Recognizer2D: mvfnet_amd runs on MI355X tensors only; no CPU fallback (tests use oracle/)")
+        pipe, window = getattr(self, "input_pipeline", None), kwargs.get("window")
+        if window is not None and getattr(pipe, "gathers", lambda rows: False)(window):
+            raise ValueError("Recognizer2D.forward_train: a gather table (src column, %d columns) is a test-time input -- training makes one "
+                             "image per frame; use the 11- / 23-column table" % window.shape[-1])
+        if self.with_cls_head and getattr(self.cls_head, "extract_feat", False):
+            raise NotImplementedError("Recognizer2D.forward_train: cls_head.extract_feat=True is an eval-mode path (feature extraction)")
         # BatchNorms in eval mode (backbone norm_eval=True / frozen stages / partial_norm, reference resnet.py:496-527) normalise with
         # their running statistics and keep them; parameters excluded from training (frozen_stages: a prefix of model.parameters();
         # norm_frozen / partial_norm: BatchNorm weights / biases in scattered places) are skipped by the optimizer kernel
@@ -143,7 +153,7 @@ class Recognizer2D(nn.Module):
                 x = imgs.reshape((-1, self.in_channels) + tuple(imgs.shape[3:]))
             feat = self.extract_feat(x)                                   # (B*frames, 2048, h, w), channels-last
             if self.with_cls_head:
-                num_seg = self.module_cfg["n_segment"] if self.module_cfg else x.shape[0] // imgs.shape[0]
+                num_seg = self.module_cfg["n_segment"] if self.module_cfg else self.backbone.engine().n_images(x, kwargs.get("window")) // imgs.shape[0]
                 # with fcn_testing the reference reshapes to (clips, C, T, h, w) and runs a 1x1x1 conv + mean; the head
                 # kernel computes the same mean-then-FC directly from the channels-last features
                 cls_score = self.cls_head(feat, num_seg)
