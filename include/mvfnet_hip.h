@@ -248,6 +248,31 @@ int mvf_frames_resample_color_u8(const unsigned char* frames_hwc, int n, int hs,
 int mvf_frames_gather_resample_u8(const unsigned char* frames_hwc, int n_src, int hs, int ws, const int* src_index, int n_out, const int* rows,
                                   const float* color, int h, int w, const float* mean3, const float* std3, int to_rgb, int div_255, int pad,
                                   int wp, void* out_stem, float* out_nchw, int dtype, void* stream);
+/* mvf_frames_gather_resample_u8 for decoder-native YUV 4:2:0 frames (what every video decoder produces; the packed frames the other
+ * exports take are a CPU colour conversion on top of it, at twice the bytes).  frames = (n_src, 3 * hs / 2, pitch) bytes, hs and pitch even,
+ * pitch >= ws:
+ *   layout 0 = I420: hs luma rows of pitch bytes, then the U plane (hs / 2 rows of pitch / 2 bytes), then the V plane likewise;
+ *   layout 1 = NV12: hs luma rows of pitch bytes, then hs / 2 rows of pitch bytes of interleaved U, V pairs.
+ * A frame stands for the packed (hs, ws, 3) uint8 frame with, at luma pixel (y, x) and the chroma sample (y >> 1, x >> 1) (replicated, not
+ * interpolated; absolute frame coordinates, so odd by / bx are fine), in int32 with an arithmetic shift:
+ *   y' = max(0, Y - y_off) * CY
+ *   R = sat8((y' + (1 << 19) + CVR * (V - 128)) >> 20)
+ *   G = sat8((y' + (1 << 19) - CVG * (V - 128) - CUG * (U - 128)) >> 20)
+ *   B = sat8((y' + (1 << 19) + CUB * (U - 128)) >> 20)
+ * every constant rint(c * 2^20) of the decimal coefficient c:
+ *   standard 0 = BT.601 limited: y_off 16, cY 1.164,    cVR 1.596,    cVG 0.813,    cUG 0.391,    cUB 2.018
+ *   standard 1 = BT.601 full:    y_off 0,  cY 1.0,      cVR 1.402,    cVG 0.714136, cUG 0.344136, cUB 1.772     (yuvj420p)
+ *   standard 2 = BT.709 limited: y_off 16, cY 1.164384, cVR 1.792741, cVG 0.532909, cUG 0.213249, cUB 2.112402
+ * (this table's conversion, within 1 of the rounded float definition; NOT bit-equal to any particular decoder library's).  order = the
+ * stored channel order of that packed frame: 0 = BGR (what the raw-frame path stores), 1 = RGB.  The four taps of the resample (or the four
+ * pixels of the exact-2x area mean) are converted, and everything after them -- blend, colour map in stored order, to_rgb, div_255,
+ * Normalize, both outputs -- is mvf_frames_gather_resample_u8's: the result equals that export run on the converted packed frames, bit for
+ * bit.  rows' (hs_i, ws_i) may be odd (a frame of odd size lies in even-sized planes, chroma ceil(hs_i / 2) x ceil(ws_i / 2)).  Odd hs or
+ * pitch, pitch < ws and an unknown layout / standard / order return MVF_EINVAL; rows and src_index are NOT checked here, as above. */
+int mvf_frames_yuv420_gather_resample_u8(const unsigned char* frames, int n_src, int hs, int ws, int pitch, int layout, int standard, int order,
+                                         const int* src_index, int n_out, const int* rows, const float* color, int h, int w, const float* mean3,
+                                         const float* std3, int to_rgb, int div_255, int pad, int wp, void* out_stem, float* out_nchw, int dtype,
+                                         void* stream);
 
 /* MaxPool2d(3, stride 2, pad 1) on NHWC (resnet.py:431,484). */
 int mvf_maxpool3x3s2_nhwc(const void* x, int n, int h, int w, int c, void* y, int dtype, void* stream);

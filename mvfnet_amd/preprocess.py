@@ -19,7 +19,11 @@ geometry of `MultiScaleCrop`, `TenCrop`, `RandomRescaledCrop` and a bare `Center
 
 `GatherFramePipeline` adds whole-video testing from ONE upload of a video's distinct decoded frames (`mvf_frames_gather_resample_u8`): a
 trailing `src` column (12 or 24 columns, `gather_rows`) names the source frame every output image is cut from, so the clips of
-`SampleFrames(num_clips)` that share or repeat frames and the crops of `ThreeCrop` / `TenCrop` read the same bytes (`video_test_table`)."""
+`SampleFrames(num_clips)` that share or repeat frames and the crops of `ThreeCrop` / `TenCrop` read the same bytes (`video_test_table`).
+
+`Yuv420FramePipeline` takes the frames as a video decoder produces them (`mvf_frames_yuv420_gather_resample_u8`): planar YUV 4:2:0, I420
+or NV12, half the bytes of the packed frames; the colour conversion (BT.601 limited / full range, BT.709) runs in the kernel in front of
+the resample's taps, so the CPU conversion the reference's decoders do is gone too (`collate_yuv_frames`)."""
 import ctypes
 import math
 import random
@@ -641,6 +645,163 @@ class GatherFramePipeline(JitterFramePipeline):
         """-> (n_out, h + 2 pad, wp, 4) `dtype`, the stem conv's operand (FramePipeline.to_stem) for the table's images."""
         if self._cols(rows) in (RESAMPLE_COLS, JITTER_COLS):
             return super().to_stem(frames, rows, pad, wp, dtype, out=out)
+        return self._run(frames, rows, pad, wp, dtype, out=out)
+
+
+# ---- decoder-native YUV 4:2:0 frames ---------------------------------------------------------------------------------------------------
+YUV_LAYOUTS = {"i420": 0, "nv12": 1}
+YUV_STANDARDS = {"bt601": 0, "bt601-full": 1, "bt709": 2}
+YUV_ORDERS = {"bgr": 0, "rgb": 1}
+
+
+def _enum(name, value, table):
+    """A name of `table` or its number -> the number."""
+    if isinstance(value, str):
+        if value.lower() not in table:
+            raise ValueError("%s must be one of %s (or %s), got %r" % (name, sorted(table), sorted(table.values()), value))
+        return table[value.lower()]
+    if isinstance(value, bool) or int(value) != value or int(value) not in table.values():
+        raise ValueError("%s must be one of %s (or %s), got %r" % (name, sorted(table), sorted(table.values()), value))
+    return int(value)
+
+
+def _yuv_planes(frames, who):
+    """One clip's frames as (Y (T, h, w), U, V (T, ceil(h / 2), ceil(w / 2))) uint8 CPU tensors: the three planes as given, or cut from a
+    (T, 3 * h / 2, w) I420 array (what `frame.to_ndarray(format='yuv420p')` returns, stacked; h and w even)."""
+    import numpy as np
+    if isinstance(frames, (tuple, list)):
+        if len(frames) != 3:
+            raise ValueError("%s: a clip is (Y, U, V) planes or one (T, 3 * h / 2, w) I420 array" % who)
+        y, u, v = (torch.as_tensor(np.asarray(p)) for p in frames)
+    else:
+        f = torch.as_tensor(np.asarray(frames))
+        if f.dim() != 3 or f.shape[1] % 3 or f.shape[2] % 2:
+            raise ValueError("%s: an I420 clip must be (T, 3 * h / 2, w) with h and w even, got %s" % (who, tuple(f.shape)))
+        t, h, w = f.shape[0], f.shape[1] // 3 * 2, f.shape[2]
+        flat, q = f.reshape(t, -1), (h // 2) * (w // 2)
+        y = flat[:, :h * w].reshape(t, h, w)
+        u = flat[:, h * w:h * w + q].reshape(t, h // 2, w // 2)
+        v = flat[:, h * w + q:].reshape(t, h // 2, w // 2)
+    if y.dim() != 3 or any(p.dtype != torch.uint8 for p in (y, u, v)):
+        raise ValueError("%s: planes must be uint8 (T, h, w) / (T, ceil(h / 2), ceil(w / 2))" % who)
+    t, h, w = y.shape
+    chroma = (t, (h + 1) // 2, (w + 1) // 2)
+    if tuple(u.shape) != chroma or tuple(v.shape) != chroma:
+        raise ValueError("%s: a %dx%d luma plane needs %s chroma planes, got %s and %s" % (who, h, w, chroma, tuple(u.shape), tuple(v.shape)))
+    return y, u, v
+
+
+def collate_yuv_frames(groups, layout, pad_to=None, cols=None):
+    """collate_frames for YUV 4:2:0 clips.  groups: a list of (frames, rows) per clip -- frames the clip's (Y (T, h_b, w_b), U, V (T,
+    ceil(h_b / 2), ceil(w_b / 2))) uint8 planes (numpy or CPU tensors; h_b, w_b may be odd) or one (T, 3 * h_b / 2, w_b) I420 array, rows its
+    (T, cols) table -- -> (frames (B, T, 3 * Hs / 2, Ws) uint8 in `layout` ('i420' | 'nv12') at pitch Ws, rows (B * T, cols) int32), CPU
+    tensors for Yuv420FramePipeline.  Hs x Ws is the largest clip (or `pad_to` = (Hs, Ws)) rounded up to even; every clip's planes are
+    copied into the zero padded planes at the padded pitch and every row keeps its own frame's (hs_i, ws_i).  `cols` defaults to 11."""
+    import numpy as np
+    lay = _enum("layout", layout, YUV_LAYOUTS)
+    cols = RESAMPLE_COLS if cols is None else int(cols)
+    if not groups:
+        raise ValueError("collate_yuv_frames: no clips")
+    planes = [_yuv_planes(f, "collate_yuv_frames") for f, _ in groups]
+    rows = [torch.as_tensor(np.asarray(r, dtype=np.int32)).reshape(-1, cols) for _, r in groups]
+    t = planes[0][0].shape[0]
+    for (y, _, _), r in zip(planes, rows):
+        if y.shape[0] != t:
+            raise ValueError("collate_yuv_frames: every clip must have T=%d frames, got %d" % (t, y.shape[0]))
+        if r.shape[0] != t or bool((r[:, 0] != y.shape[1]).any()) or bool((r[:, 1] != y.shape[2]).any()):
+            raise ValueError("collate_yuv_frames: rows do not describe their %s luma planes" % (tuple(y.shape),))
+    hs, ws = (max(y.shape[1] for y, _, _ in planes), max(y.shape[2] for y, _, _ in planes)) if pad_to is None else (int(pad_to[0]), int(pad_to[1]))
+    if any(y.shape[1] > hs or y.shape[2] > ws for y, _, _ in planes):
+        raise ValueError("collate_yuv_frames: a clip is larger than pad_to=%s" % (pad_to,))
+    hs, ws = hs + hs % 2, ws + ws % 2
+    out = torch.zeros(len(planes), t, hs * 3 // 2, ws, dtype=torch.uint8)
+    luma = out[:, :, :hs]
+    chroma, q = out.view(len(planes), t, -1)[:, :, hs * ws:], (hs // 2) * (ws // 2)      # views of `out`: chroma rows are pitch / 2 samples
+    if lay == 0:
+        cu, cv = (c.view(len(planes), t, hs // 2, ws // 2) for c in (chroma[:, :, :q], chroma[:, :, q:]))
+    else:
+        uv = chroma.view(len(planes), t, hs // 2, ws // 2, 2)
+        cu, cv = uv[..., 0], uv[..., 1]
+    for b, (y, u, v) in enumerate(planes):
+        luma[b, :, :y.shape[1], :y.shape[2]] = y
+        cu[b, :, :u.shape[1], :u.shape[2]] = u
+        cv[b, :, :v.shape[1], :v.shape[2]] = v
+    return out, torch.cat(rows).contiguous()
+
+
+class Yuv420FramePipeline(GatherFramePipeline):
+    """GatherFramePipeline for decoder-native YUV 4:2:0 frames (mvf_frames_yuv420_gather_resample_u8): `frames` is a CUDA uint8 tensor
+    (..., 3 * Hs / 2, pitch), one I420 or NV12 image per frame (include/mvfnet_hip.h; collate_yuv_frames builds it), half the bytes of the
+    packed frames; the colour conversion runs in the kernel, in front of the resample's taps.  Constructor extras: `layout` 'i420' | 'nv12';
+    `standard` 'bt601' (limited range, the default) | 'bt601-full' (yuvj420p) | 'bt709' or 0 / 1 / 2; `order` 'bgr' (default: what the
+    raw-frame path stores) | 'rgb', the stored channel order the frames stand for -- ColorJitter's map and `to_rgb` apply to it as they do
+    to packed frames; `pitch` = the row length in bytes when it exceeds the frame width (a decoder's aligned surfaces: the tensor's last
+    dimension must then be `pitch`, and `width` names the true frame width Ws; default: both are the tensor's last dimension).
+    Takes the 11-, 23-, 12- and 24-column tables (without the src column: one image per frame) and gives, bit for bit, GatherFramePipeline's
+    output for the converted packed frames.  Same `crop_hw`, `to_nchw`, `to_stem`, `n_out`, `gathers` and `center_window`."""
+
+    frame_dims = 2              # trailing dimensions of one frame (packed frames: 3), for the engines' flattening
+
+    def __init__(self, *args, layout="i420", standard=0, order="bgr", pitch=None, width=None, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.layout, self.standard, self.order = _enum("layout", layout, YUV_LAYOUTS), _enum("standard", standard, YUV_STANDARDS), _enum("order", order, YUV_ORDERS)
+        self.pitch = None if pitch is None else int(pitch)
+        self.width = None if width is None else int(width)
+        if self.pitch is not None and (self.pitch < 2 or self.pitch % 2):
+            raise ValueError("Yuv420FramePipeline: pitch=%d must be even" % self.pitch)
+        if self.width is not None and (self.width < 1 or (self.pitch is not None and self.width > self.pitch)):
+            raise ValueError("Yuv420FramePipeline: width=%d must lie in [1, pitch]" % self.width)
+
+    def n_out(self, frames, rows):
+        if self.gathers(rows):
+            return int(rows.reshape(-1, rows.shape[-1]).shape[0])
+        n = 1
+        for d in frames.shape[:-2]:
+            n *= int(d)
+        return n
+
+    def _frames(self, frames):
+        """-> ((n_src, 3 * Hs / 2, pitch) contiguous, Hs, Ws)."""
+        if frames.dtype != torch.uint8 or frames.dim() < 2 or not frames.is_cuda:
+            raise TypeError("Yuv420FramePipeline expects a CUDA uint8 tensor (..., 3 * Hs / 2, pitch) of YUV 4:2:0 frames, got %s %s"
+                            % (frames.dtype, tuple(frames.shape)))
+        rows3, pitch = int(frames.shape[-2]), int(frames.shape[-1])
+        if rows3 < 3 or rows3 % 3 or pitch % 2:
+            raise ValueError("Yuv420FramePipeline: a frame is 3 * Hs / 2 rows of an even pitch, Hs even; got %d x %d" % (rows3, pitch))
+        if self.pitch is not None and pitch != self.pitch:
+            raise ValueError("Yuv420FramePipeline: the frames' rows are %d bytes, not pitch=%d" % (pitch, self.pitch))
+        ws = pitch if self.width is None else self.width
+        if ws > pitch:
+            raise ValueError("Yuv420FramePipeline: width=%d exceeds the frames' %d-byte rows" % (ws, pitch))
+        return frames.reshape(-1, rows3, pitch).contiguous(), rows3 // 3 * 2, ws
+
+    def _run(self, frames, rows, pad, wp, dtype, out=None, nchw=False):
+        f, hs, ws = self._frames(frames)
+        n_src, pitch = f.shape[0], f.shape[2]
+        if self.gathers(rows):
+            r, col, src = self._gather(rows, n_src, hs, ws)
+        else:
+            r, col = self._split(rows, n_src, hs, ws)
+            src = None
+        n, (h, w) = r.shape[0], self.crop_hw
+        shape = (n, 3, h, w) if nchw else (n, h + 2 * pad, wp, 4)
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=f.device)
+        elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous():
+            raise ValueError("Yuv420FramePipeline: the output buffer %s %s does not hold the table's %d images %s" % (out.dtype, tuple(out.shape), n, shape))
+        check(lib.mvf_frames_yuv420_gather_resample_u8(f.data_ptr(), n_src, hs, ws, pitch, self.layout, self.standard, self.order,
+                                                       src.data_ptr() if src is not None else None, n, r.data_ptr(),
+                                                       col.data_ptr() if col is not None else None, h, w, self.mean, self.std, int(self.to_rgb),
+                                                       int(self.div_255), pad, wp, None if nchw else out.data_ptr(), out.data_ptr() if nchw else None,
+                                                       _DT[dtype], torch.cuda.current_stream().cuda_stream), "mvf_frames_yuv420_gather_resample_u8")
+        return out
+
+    def to_nchw(self, frames, rows):
+        """-> (n_out, 3, h, w) fp32: GatherFramePipeline.to_nchw of the converted packed frames."""
+        return self._run(frames, rows, 0, self.crop_hw[1], torch.float32, nchw=True)
+
+    def to_stem(self, frames, rows, pad, wp, dtype, out=None):
+        """-> (n_out, h + 2 pad, wp, 4) `dtype`, the stem conv's operand (FramePipeline.to_stem) for the table's images."""
         return self._run(frames, rows, pad, wp, dtype, out=out)
 
 

@@ -96,7 +96,9 @@ class Recognizer2D(nn.Module):
         With a preprocess.JitterFramePipeline, `window=` is the (frames, 23) int32 table of jitter_rows (geometry + ColorJitter's map).
         With a preprocess.GatherFramePipeline (forward_test only), `img_group` holds a video's DISTINCT decoded frames and `window=` is the
         (images, 12) or (images, 24) int32 table of gather_rows / video_test_table: one row per output image, its trailing `src` column
-        naming the frame the image is cut from, so clips and oversampling crops share one upload; 11 / 23 columns mean "no gather"."""
+        naming the frame the image is cut from, so clips and oversampling crops share one upload; 11 / 23 columns mean "no gather".
+        With a preprocess.Yuv420FramePipeline, `img_group` is (B, frames, 3 * Hs / 2, pitch) uint8, decoder-native I420 or NV12 frames, with
+        any of the tables above; the colour conversion runs in that kernel too."""
         self.input_pipeline = pipeline
         self.backbone.input_pipeline = pipeline
         return self
@@ -147,7 +149,8 @@ class Recognizer2D(nn.Module):
             raise RuntimeError("Recognizer2D: mvfnet_amd runs on MI355X tensors only; no CPU fallback (tests use oracle/)")
         with torch.no_grad():
             if imgs.dtype == torch.uint8:                                 # decoded frames (B, frames, Hs, Ws, 3), see set_input_pipeline
-                x = imgs.reshape((-1,) + tuple(imgs.shape[-3:]))
+                k = getattr(getattr(self, "input_pipeline", None), "frame_dims", 3)      # YUV 4:2:0 frames are (3 * Hs / 2, pitch): 2
+                x = imgs.reshape((-1,) + tuple(imgs.shape[-k:]))
                 self.backbone.engine().input_window = kwargs.get("window")
             else:
                 x = imgs.reshape((-1, self.in_channels) + tuple(imgs.shape[3:]))
