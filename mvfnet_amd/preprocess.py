@@ -1,29 +1,21 @@
 """Device side of the input pipeline: the host ships DECODED uint8 frames (a quarter of the bytes of the
 normalised fp32 tensor the reference's DataLoader + scatter move, codes/core/parallel/distributed.py:40-62) and one HIP kernel
-does crop window -> flip -> Normalize -> FormatShape -> stem layout (`mvf_frames_prep_u8`, include/mvfnet_hip.h).
+(csrc/frames_input.hip, include/mvfnet_hip.h) does resize -> crop -> flip -> ColorJitter -> Normalize -> FormatShape -> stem layout;
+decoding is the only step left on the host.  Names and argument meaning mirror the reference's pipeline steps (augmentations.py):
+`img_norm_cfg = dict(mean, std, to_rgb)`, `Flip(flip_ratio)`'s boolean, the crops' offsets.
 
-Mirrors the reference's pipeline steps in names and argument meaning: `img_norm_cfg = dict(mean, std, to_rgb)` of the configs
-(config_zoo R50 8x8: mean [123.675, 116.28, 103.53], std [58.395, 57.12, 57.375], to_rgb True), `Flip(flip_ratio)`'s boolean,
-`CenterCrop` / `ThreeCrop(crop_size)` offsets (augmentations.py:196-228, 342-396, 465-540).
-
-`ResamplingFramePipeline` adds the resize in front of the crop (`mvf_frames_resample_u8`): `Resize` (keep_ratio or an exact size),
-`RandomResizedCrop`'s box and bilinear resample (cv2 INTER_LINEAR arithmetic), so the host ships frames as decoded, at their own
-resolution, with one int32 row per frame (`train_rows` / `val_rows` / `test_rows`, `collate_frames`).  Decoding is the only step left
-on the host.
-
-`JitterFramePipeline` adds the TSN-style fine-tuning recipe (`mvf_frames_resample_color_u8`): `ColorJitter` as one affine colour
-transform per frame between the resample and Normalize (`color_jitter_table`: 12 floats, the reference's draws in its order), and the
-geometry of `MultiScaleCrop`, `TenCrop`, `RandomRescaledCrop` and a bare `CenterCrop` as the same 11-column rows
-(`multi_scale_crop_rows` / `ten_crop_rows` / `random_rescaled_crop_rows` / `center_crop_rows`); `jitter_rows` packs both into one
-23-column int32 table that travels through `window=` (`collate_jitter_frames`).
-
-`GatherFramePipeline` adds whole-video testing from ONE upload of a video's distinct decoded frames (`mvf_frames_gather_resample_u8`): a
-trailing `src` column (12 or 24 columns, `gather_rows`) names the source frame every output image is cut from, so the clips of
-`SampleFrames(num_clips)` that share or repeat frames and the crops of `ThreeCrop` / `TenCrop` read the same bytes (`video_test_table`).
-
-`Yuv420FramePipeline` takes the frames as a video decoder produces them (`mvf_frames_yuv420_gather_resample_u8`): planar YUV 4:2:0, I420
-or NV12, half the bytes of the packed frames; the colour conversion (BT.601 limited / full range, BT.709) runs in the kernel in front of
-the resample's taps, so the CPU conversion the reference's decoders do is gone too (`collate_yuv_frames`)."""
+Every pipeline class is `to_nchw(frames, table)` (the reference's fp32 tensor) and `to_stem(frames, table, pad, wp, dtype, out=None)`
+(the stem conv's operand) over one int32 table with one row per image, which the engines carry through `window=`:
+  FramePipeline             (y0, x0, flip) crop windows, or None: the frames are already at their final resolution;
+  ResamplingFramePipeline   11 geometry columns (hs_i, ws_i, by, bx, bh, bw, rh, rw, oy, ox, flip): patch -> cv2 INTER_LINEAR resize -> crop,
+                            `Resize` / `RandomResizedCrop` / the crops as `train_rows` / `val_rows` / `test_rows` / ... (`collate_frames`);
+  JitterFramePipeline       11, or 11 + 12 colour columns: ColorJitter's affine map per frame as fp32 bit patterns (`color_jitter_table`,
+                            `jitter_rows`, `collate_jitter_frames`);
+  GatherFramePipeline       11 or 23, or either + 1 `src` column: the image is cut from frames[src], so a video's clips and crops share one
+                            upload of its distinct frames (`gather_rows`, `video_test_table`);
+  Yuv420FramePipeline       the same four tables over decoder-native planar YUV 4:2:0 frames, I420 or NV12, half the bytes of the packed
+                            frames; the colour conversion runs in the kernel (`collate_yuv_frames`).
+A table without the colour or src columns gives the narrower class's output bit for bit."""
 import ctypes
 import math
 import random
@@ -33,6 +25,15 @@ import torch
 from ._lib import check, lib
 
 _DT = {torch.float32: 0, torch.bfloat16: 1}
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _ncols(table):
+    """The column count of a 2-D (or deeper) table; 0 for None, a flat one or anything without a shape."""
+    return int(table.shape[-1]) if table is not None and hasattr(table, "shape") and len(table.shape) > 1 else 0
 
 
 def three_crop_offsets(img_h, img_w, crop_h, crop_w):
@@ -59,7 +60,10 @@ def flip_flag(flip_ratio, rng=None):
 
 
 class FramePipeline(object):
-    """Normalize(mean, std, to_rgb, div_255) + a crop size; per-frame windows (y0, x0, flip) select crop position and mirroring."""
+    """Normalize(mean, std, to_rgb, div_255) + a crop size; per-frame windows (y0, x0, flip) select crop position and mirroring
+    (mvf_frames_prep_u8).  The subclasses change what a table row is (_parse), what a frame is (_source) and the export (_launch)."""
+
+    frame_dims = 3              # trailing dimensions of one frame, for the engines' flattening
 
     def __init__(self, mean=(123.675, 116.28, 103.53), std=(58.395, 57.12, 57.375), to_rgb=True, div_255=False, crop_size=224):
         self.mean = (ctypes.c_float * 3)(*[float(v) for v in mean])
@@ -73,52 +77,54 @@ class FramePipeline(object):
         row = [(hs - h) // 2, (ws - w) // 2, int(bool(flip))]
         return torch.tensor([row] * n, dtype=torch.int32, device=device)
 
-    def _frames(self, frames):
+    def _source(self, frames):
+        """-> (the frames flattened to (n_src, hs, ws, 3) contiguous, n_src, hs, ws)."""
         if frames.dtype != torch.uint8 or frames.shape[-1] != 3 or not frames.is_cuda:
-            raise TypeError("FramePipeline expects a CUDA uint8 tensor (..., H, W, 3) of decoded frames, got %s %s" % (frames.dtype, tuple(frames.shape)))
+            raise TypeError("%s expects a CUDA uint8 tensor (..., H, W, 3) of decoded frames, got %s %s" % (type(self).__name__, frames.dtype, tuple(frames.shape)))
         f = frames.reshape((-1,) + tuple(frames.shape[-3:])).contiguous()
-        h, w = self.crop_hw
-        if h > f.shape[1] or w > f.shape[2]:
-            raise ValueError("crop %dx%d larger than the frames %dx%d" % (h, w, f.shape[1], f.shape[2]))
-        return f
+        return (f,) + tuple(f.shape[:3])
 
-    def _window(self, window, n, hs, ws):
-        if window is None:
-            return None
-        window = window.to(device="cuda", dtype=torch.int32).reshape(-1, 3).contiguous()
-        if window.shape[0] != n:
-            raise ValueError("window needs one (y0, x0, flip) row per frame: %d rows for %d frames" % (window.shape[0], n))
+    def _parse(self, window, n_src, hs, ws):
+        """-> (geo, color, src) device tensors for _launch, None where the table has no such part."""
         h, w = self.crop_hw
+        if h > hs or w > ws:
+            raise ValueError("crop %dx%d larger than the frames %dx%d" % (h, w, hs, ws))
+        if window is None:
+            return None, None, None
+        window = window.to(device="cuda", dtype=torch.int32).reshape(-1, 3).contiguous()
+        if window.shape[0] != n_src:
+            raise ValueError("window needs one (y0, x0, flip) row per frame: %d rows for %d frames" % (window.shape[0], n_src))
         lo, hi = window.min(0).values.tolist(), window.max(0).values.tolist()
         if lo[0] < 0 or lo[1] < 0 or hi[0] + h > hs or hi[1] + w > ws:
             raise ValueError("crop window leaves the %dx%d frame" % (hs, ws))
-        return window
+        return window, None, None
 
-    def to_nchw(self, frames, window=None):
-        """-> (n, 3, h, w) fp32, what the reference's Normalize + FormatShape + ToTensor produce for these frames."""
-        f = self._frames(frames)
-        n, hs, ws = f.shape[:3]
-        win = self._window(window, n, hs, ws)
+    def _launch(self, f, n_src, hs, ws, geo, color, src, n, pad, wp, out_stem, out_nchw, dt):
         h, w = self.crop_hw
-        out = torch.empty(n, 3, h, w, dtype=torch.float32, device=f.device)
-        check(lib.mvf_frames_prep_u8(f.data_ptr(), n, hs, ws, win.data_ptr() if win is not None else None, h, w, self.mean, self.std,
-                                     int(self.to_rgb), int(self.div_255), 0, w, None, out.data_ptr(), 0,
-                                     torch.cuda.current_stream().cuda_stream), "mvf_frames_prep_u8")
-        return out
+        check(lib.mvf_frames_prep_u8(f.data_ptr(), n, hs, ws, _ptr(geo), h, w, self.mean, self.std, int(self.to_rgb), int(self.div_255), pad, wp,
+                                     out_stem, out_nchw, dt, torch.cuda.current_stream().cuda_stream), "mvf_frames_prep_u8")
 
-    def to_stem(self, frames, window, pad, wp, dtype, out=None):
-        """-> (n, h + 2 pad, wp, 4) `dtype`: the zero-padded channels-last operand of the 7x7 stem conv (what mvf_stem_prep makes
-        from the fp32 NCHW tensor), straight from the uint8 frames."""
-        f = self._frames(frames)
-        n, hs, ws = f.shape[:3]
-        win = self._window(window, n, hs, ws)
-        h, w = self.crop_hw
+    def _run(self, frames, table, pad, wp, dtype, out, nchw):
+        f, n_src, hs, ws = self._source(frames)
+        geo, color, src = self._parse(table, n_src, hs, ws)
+        n, (h, w) = n_src if geo is None else geo.shape[0], self.crop_hw
+        shape = (n, 3, h, w) if nchw else (n, h + 2 * pad, wp, 4)
         if out is None:
-            out = torch.empty(n, h + 2 * pad, wp, 4, dtype=dtype, device=f.device)
-        check(lib.mvf_frames_prep_u8(f.data_ptr(), n, hs, ws, win.data_ptr() if win is not None else None, h, w, self.mean, self.std,
-                                     int(self.to_rgb), int(self.div_255), pad, wp, out.data_ptr(), None, _DT[dtype],
-                                     torch.cuda.current_stream().cuda_stream), "mvf_frames_prep_u8")
+            out = torch.empty(shape, dtype=dtype, device=f.device)
+        elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous():
+            raise ValueError("%s: the output buffer %s %s does not hold the table's %d images %s %s"
+                             % (type(self).__name__, out.dtype, tuple(out.shape), n, dtype, shape))
+        self._launch(f, n_src, hs, ws, geo, color, src, n, pad, wp, None if nchw else out.data_ptr(), out.data_ptr() if nchw else None, _DT[dtype])
         return out
+
+    def to_nchw(self, frames, rows=None):
+        """-> (n, 3, h, w) fp32, what the reference's resize / crop + Flip [+ ColorJitter] + Normalize + FormatShape + ToTensor produce."""
+        return self._run(frames, rows, 0, self.crop_hw[1], torch.float32, None, True)
+
+    def to_stem(self, frames, rows, pad, wp, dtype, out=None):
+        """-> (n, h + 2 pad, wp, 4) `dtype`: the zero-padded channels-last operand of the 7x7 stem conv (what mvf_stem_prep makes
+        from the fp32 NCHW tensor), straight from the uint8 frames; into `out` when given."""
+        return self._run(frames, rows, pad, wp, dtype, out, False)
 
 
 # ---- resize geometry (host side; reference augmentations.py:13-68 Resize, :600-661 RandomResizedCrop, mmcv 0.4.3 imrescale / imcrop) --
@@ -257,7 +263,11 @@ def collate_frames(groups, pad_to=None, cols=None):
 class ResamplingFramePipeline(FramePipeline):
     """FramePipeline with the resize in front of the crop: per-frame int32 rows (hs_i, ws_i, by, bx, bh, bw, rh, rw, oy, ox, flip)
     (train_rows / val_rows / test_rows / resize_rows) instead of (y0, x0, flip) windows; same constructor, `crop_hw`, `to_nchw` and
-    `to_stem` interface, so the engines take it through `input_pipeline` / `window=`.  The frames may be smaller than the crop."""
+    `to_stem` interface, so the engines take it through `input_pipeline` / `window=`.  The frames may be smaller than the crop.
+    This class, JitterFramePipeline and GatherFramePipeline share one table parser and one export, mvf_frames_gather_resample_u8 with
+    the colour and src pointers NULL where the table has no such columns; they differ in the column counts they take (_COLS)."""
+
+    _COLS = (RESAMPLE_COLS,)
 
     def center_window(self, n, hs, ws, flip=False, device="cuda"):
         """Rows of CenterCrop without a resize (augmentations.py:447-452)."""
@@ -265,53 +275,50 @@ class ResamplingFramePipeline(FramePipeline):
         row = [hs, ws, 0, 0, hs, ws, hs, ws, (hs - h) // 2, (ws - w) // 2, int(bool(flip))]
         return torch.tensor([row] * n, dtype=torch.int32, device=device)
 
-    def _frames(self, frames):
-        if frames.dtype != torch.uint8 or frames.shape[-1] != 3 or not frames.is_cuda:
-            raise TypeError("ResamplingFramePipeline expects a CUDA uint8 tensor (..., H, W, 3) of decoded frames, got %s %s" % (frames.dtype, tuple(frames.shape)))
-        return frames.reshape((-1,) + tuple(frames.shape[-3:])).contiguous()
-
-    def _window(self, rows, n, hs, ws):
-        if rows is None:
-            raise ValueError("ResamplingFramePipeline needs one (hs_i, ws_i, by, bx, bh, bw, rh, rw, oy, ox, flip) row per frame")
-        rows = torch.as_tensor(rows).to(device="cuda", dtype=torch.int32).reshape(-1, RESAMPLE_COLS).contiguous()
-        if rows.shape[0] != n:
-            raise ValueError("rows: %d rows for %d frames" % (rows.shape[0], n))
+    def _parse(self, table, n_src, hs, ws):
+        name, takes = type(self).__name__, " / ".join(str(c) for c in self._COLS)
+        if table is None:
+            raise ValueError("%s needs one int32 row of %s columns per image: (hs_i, ws_i, by, bx, bh, bw, rh, rw, oy, ox, flip) [+ 12 colour] [+ src]" % (name, takes))
+        t = torch.as_tensor(table).to(device="cuda", dtype=torch.int32)
+        if t.dim() == 1 and len(self._COLS) == 1:                 # a flat table is unambiguous where one width is taken
+            t = t.reshape(-1, self._COLS[0])
+        cols = _ncols(t)
+        if cols not in self._COLS:
+            raise ValueError("%s rows must have %s columns, got %s" % (name, takes, tuple(t.shape)))
+        t = t.reshape(-1, cols)
+        color = src = None
+        if cols in (RESAMPLE_COLS + 1, JITTER_COLS + 1):          # one row per OUTPUT image, cut from frames[src]
+            if t.shape[0] < 1:
+                raise ValueError("%s: an empty table" % name)
+            t, src = t[:, :-1], t[:, -1].contiguous()
+            bad = (src < 0) | (src >= n_src)
+            if bool(bad.any()):
+                i = int(bad.nonzero()[0, 0])
+                raise ValueError("row %d: source frame %d is not one of the %d frames" % (i, int(src[i]), n_src))
+        elif t.shape[0] != n_src:
+            raise ValueError("rows: %d rows for %d frames" % (t.shape[0], n_src))
+        if t.shape[1] == JITTER_COLS:
+            t, color = t[:, :RESAMPLE_COLS], t[:, RESAMPLE_COLS:].contiguous().view(torch.float32)
+        geo = t.contiguous()
         h, w = self.crop_hw
-        fh, fw, by, bx, bh, bw, rh, rw, oy, ox, flip = rows.to(torch.int64).unbind(1)
-        bad = ((fh < 1) | (fh > hs) | (fw < 1) | (fw > ws)
+        fh, fw, by, bx, bh, bw, rh, rw, oy, ox, flip = geo.to(torch.int64).unbind(1)
+        bad = ((fh < 1) | (fh > hs) | (fw < 1) | (fw > ws)        # every frame shares the hs x ws padded extent: the check holds per src
                | (by < 0) | (bx < 0) | (bh < 1) | (bw < 1) | (by + bh > fh) | (bx + bw > fw)
                | (oy < 0) | (ox < 0) | (oy + h > rh) | (ox + w > rw)
                | ((flip != 0) & (flip != 1)))
         if bool(bad.any()):
             i = int(bad.nonzero()[0, 0])
             raise ValueError("row %d %s: the patch must lie in its %dx%d-padded frame and the %dx%d crop in the resized patch"
-                             % (i, rows[i].tolist(), hs, ws, h, w))
-        return rows
+                             % (i, geo[i].tolist(), hs, ws, h, w))
+        if color is not None and not bool(torch.isfinite(color).all()):
+            raise ValueError("%s: colour coefficients must be finite" % name)
+        return geo, color, src
 
-    def to_nchw(self, frames, rows):
-        """-> (n, 3, h, w) fp32, what the reference's Resize / RandomResizedCrop + crop + Flip + Normalize + FormatShape produce."""
-        f = self._frames(frames)
-        n, hs, ws = f.shape[:3]
-        r = self._window(rows, n, hs, ws)
+    def _launch(self, f, n_src, hs, ws, geo, color, src, n, pad, wp, out_stem, out_nchw, dt):
         h, w = self.crop_hw
-        out = torch.empty(n, 3, h, w, dtype=torch.float32, device=f.device)
-        check(lib.mvf_frames_resample_u8(f.data_ptr(), n, hs, ws, r.data_ptr(), h, w, self.mean, self.std, int(self.to_rgb),
-                                         int(self.div_255), 0, w, None, out.data_ptr(), 0,
-                                         torch.cuda.current_stream().cuda_stream), "mvf_frames_resample_u8")
-        return out
-
-    def to_stem(self, frames, rows, pad, wp, dtype, out=None):
-        """-> (n, h + 2 pad, wp, 4) `dtype`, the stem conv's operand (FramePipeline.to_stem), with the resample in front."""
-        f = self._frames(frames)
-        n, hs, ws = f.shape[:3]
-        r = self._window(rows, n, hs, ws)
-        h, w = self.crop_hw
-        if out is None:
-            out = torch.empty(n, h + 2 * pad, wp, 4, dtype=dtype, device=f.device)
-        check(lib.mvf_frames_resample_u8(f.data_ptr(), n, hs, ws, r.data_ptr(), h, w, self.mean, self.std, int(self.to_rgb),
-                                         int(self.div_255), pad, wp, out.data_ptr(), None, _DT[dtype],
-                                         torch.cuda.current_stream().cuda_stream), "mvf_frames_resample_u8")
-        return out
+        check(lib.mvf_frames_gather_resample_u8(f.data_ptr(), n_src, hs, ws, _ptr(src), n, geo.data_ptr(), _ptr(color), h, w, self.mean, self.std,
+                                                int(self.to_rgb), int(self.div_255), pad, wp, out_stem, out_nchw, dt,
+                                                torch.cuda.current_stream().cuda_stream), "mvf_frames_gather_resample_u8")
 
 
 # ---- TSN-style recipe (host side; reference augmentations.py:71-192 MultiScaleCrop, :238-339 ColorJitter, :544-596 TenCrop, ----------
@@ -483,51 +490,12 @@ def collate_jitter_frames(groups, pad_to=None):
 
 
 class JitterFramePipeline(ResamplingFramePipeline):
-    """ResamplingFramePipeline with ColorJitter between the resample and Normalize (mvf_frames_resample_color_u8): rows are ONE int32
+    """ResamplingFramePipeline with ColorJitter between the resample and Normalize: rows are ONE int32
     table of 23 columns per frame, the 11 geometry columns followed by the 12 colour coefficients' fp32 bit patterns (jitter_rows), so
     the engines carry it through `input_pipeline` / `window=` as they carry the 11-column table.  11-column rows mean "no jitter" and
     give ResamplingFramePipeline's output bit for bit.  Same constructor, `crop_hw`, `to_nchw` and `to_stem`."""
 
-    def _split(self, rows, n, hs, ws):
-        if rows is None:
-            raise ValueError("JitterFramePipeline needs one 23-column (or 11-column) int32 row per frame")
-        rows = torch.as_tensor(rows).to(device="cuda", dtype=torch.int32)
-        cols = rows.shape[-1] if rows.dim() > 1 else 0
-        if cols == RESAMPLE_COLS:
-            return self._window(rows, n, hs, ws), None
-        if cols != JITTER_COLS:
-            raise ValueError("JitterFramePipeline rows must have %d or %d columns, got %s" % (JITTER_COLS, RESAMPLE_COLS, tuple(rows.shape)))
-        rows = rows.reshape(-1, JITTER_COLS)
-        geo = self._window(rows[:, :RESAMPLE_COLS], n, hs, ws)
-        color = rows[:, RESAMPLE_COLS:].contiguous().view(torch.float32)
-        if not bool(torch.isfinite(color).all()):
-            raise ValueError("JitterFramePipeline: colour coefficients must be finite")
-        return geo, color
-
-    def to_nchw(self, frames, rows):
-        """-> (n, 3, h, w) fp32, what the reference's crop / resize + Flip + ColorJitter + Normalize + FormatShape produce."""
-        f = self._frames(frames)
-        n, hs, ws = f.shape[:3]
-        r, col = self._split(rows, n, hs, ws)
-        h, w = self.crop_hw
-        out = torch.empty(n, 3, h, w, dtype=torch.float32, device=f.device)
-        check(lib.mvf_frames_resample_color_u8(f.data_ptr(), n, hs, ws, r.data_ptr(), col.data_ptr() if col is not None else None, h, w,
-                                               self.mean, self.std, int(self.to_rgb), int(self.div_255), 0, w, None, out.data_ptr(), 0,
-                                               torch.cuda.current_stream().cuda_stream), "mvf_frames_resample_color_u8")
-        return out
-
-    def to_stem(self, frames, rows, pad, wp, dtype, out=None):
-        """-> (n, h + 2 pad, wp, 4) `dtype`, the stem conv's operand (FramePipeline.to_stem), with the resample and the jitter in front."""
-        f = self._frames(frames)
-        n, hs, ws = f.shape[:3]
-        r, col = self._split(rows, n, hs, ws)
-        h, w = self.crop_hw
-        if out is None:
-            out = torch.empty(n, h + 2 * pad, wp, 4, dtype=dtype, device=f.device)
-        check(lib.mvf_frames_resample_color_u8(f.data_ptr(), n, hs, ws, r.data_ptr(), col.data_ptr() if col is not None else None, h, w,
-                                               self.mean, self.std, int(self.to_rgb), int(self.div_255), pad, wp, out.data_ptr(), None,
-                                               _DT[dtype], torch.cuda.current_stream().cuda_stream), "mvf_frames_resample_color_u8")
-        return out
+    _COLS = (RESAMPLE_COLS, JITTER_COLS)
 
 
 # ---- whole-video testing: several output images per decoded frame --------------------------------------------------------------------
@@ -576,76 +544,23 @@ def video_test_table(frame_inds, hs, ws, rows_fn=test_rows, **recipe):
 
 
 class GatherFramePipeline(JitterFramePipeline):
-    """JitterFramePipeline whose output images name their source frame (mvf_frames_gather_resample_u8): the table is the 11- or 23-column
+    """JitterFramePipeline whose output images name their source frame: the table is the 11- or 23-column
     table plus one trailing `src` column (gather_rows, video_test_table), one row per OUTPUT image, and `frames` are the n_src distinct
     decoded frames; image i is cut from frames[src_i].  An 11- or 23-column table means "no gather" (one image per frame) and gives
     JitterFramePipeline's output bit for bit.  Same constructor, `crop_hw`, `to_nchw` and `to_stem`; `n_out` tells the engines how many
     images a (frames, table) pair makes."""
 
-    @staticmethod
-    def _cols(rows):
-        return int(rows.shape[-1]) if rows is not None and hasattr(rows, "shape") and len(rows.shape) > 1 else 0
+    _COLS = (RESAMPLE_COLS, JITTER_COLS, RESAMPLE_COLS + 1, JITTER_COLS + 1)
 
     def gathers(self, rows):
         """True when `rows` carries the src column (12 or 24 columns)."""
-        return self._cols(rows) in (RESAMPLE_COLS + 1, JITTER_COLS + 1)
+        return _ncols(rows) in (RESAMPLE_COLS + 1, JITTER_COLS + 1)
 
     def n_out(self, frames, rows):
         """The number of images (frames, rows) produce: the table's row count with a src column, the frame count otherwise."""
         if self.gathers(rows):
             return int(rows.reshape(-1, rows.shape[-1]).shape[0])
-        n = 1
-        for d in frames.shape[:-3]:
-            n *= int(d)
-        return n
-
-    def _gather(self, rows, n_src, hs, ws):
-        if rows is None:
-            raise ValueError("GatherFramePipeline needs one int32 row per output image (gather_rows / video_test_table)")
-        rows = torch.as_tensor(rows).to(device="cuda", dtype=torch.int32)
-        cols = self._cols(rows)
-        if cols not in (RESAMPLE_COLS + 1, JITTER_COLS + 1):
-            raise ValueError("GatherFramePipeline rows must have %d or %d columns (or %d / %d: no gather), got %s"
-                             % (RESAMPLE_COLS + 1, JITTER_COLS + 1, RESAMPLE_COLS, JITTER_COLS, tuple(rows.shape)))
-        rows = rows.reshape(-1, cols)
-        n = rows.shape[0]
-        if n < 1:
-            raise ValueError("GatherFramePipeline: an empty table")
-        src = rows[:, -1].contiguous()
-        bad = (src < 0) | (src >= n_src)
-        if bool(bad.any()):
-            i = int(bad.nonzero()[0, 0])
-            raise ValueError("row %d: source frame %d is not one of the %d frames" % (i, int(src[i]), n_src))
-        geo, color = self._split(rows[:, :-1], n, hs, ws)      # every frame shares the hs x ws padded extent: the parent's patch check holds per src
-        return geo, color, src
-
-    def _run(self, frames, rows, pad, wp, dtype, out=None, nchw=False):
-        f = self._frames(frames)
-        n_src, hs, ws = f.shape[:3]
-        r, col, src = self._gather(rows, n_src, hs, ws)
-        n, (h, w) = r.shape[0], self.crop_hw
-        shape = (n, 3, h, w) if nchw else (n, h + 2 * pad, wp, 4)
-        if out is None:
-            out = torch.empty(shape, dtype=dtype, device=f.device)
-        elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous():
-            raise ValueError("GatherFramePipeline: the output buffer %s %s does not hold the table's %d images %s" % (out.dtype, tuple(out.shape), n, shape))
-        check(lib.mvf_frames_gather_resample_u8(f.data_ptr(), n_src, hs, ws, src.data_ptr(), n, r.data_ptr(), col.data_ptr() if col is not None else None,
-                                                h, w, self.mean, self.std, int(self.to_rgb), int(self.div_255), pad, wp,
-                                                None if nchw else out.data_ptr(), out.data_ptr() if nchw else None, _DT[dtype],
-                                                torch.cuda.current_stream().cuda_stream), "mvf_frames_gather_resample_u8")
-        return out
-
-    def to_nchw(self, frames, rows):
-        """-> (n_out, 3, h, w) fp32: JitterFramePipeline.to_nchw of frames[src] with the table's other columns."""
-        if self._cols(rows) in (RESAMPLE_COLS, JITTER_COLS):
-            return super().to_nchw(frames, rows)
-        return self._run(frames, rows, 0, self.crop_hw[1], torch.float32, nchw=True)
-
-    def to_stem(self, frames, rows, pad, wp, dtype, out=None):
-        """-> (n_out, h + 2 pad, wp, 4) `dtype`, the stem conv's operand (FramePipeline.to_stem) for the table's images."""
-        if self._cols(rows) in (RESAMPLE_COLS, JITTER_COLS):
-            return super().to_stem(frames, rows, pad, wp, dtype, out=out)
-        return self._run(frames, rows, pad, wp, dtype, out=out)
+        return math.prod(int(d) for d in frames.shape[:-self.frame_dims])
 
 
 # ---- decoder-native YUV 4:2:0 frames ---------------------------------------------------------------------------------------------------
@@ -740,7 +655,7 @@ class Yuv420FramePipeline(GatherFramePipeline):
     Takes the 11-, 23-, 12- and 24-column tables (without the src column: one image per frame) and gives, bit for bit, GatherFramePipeline's
     output for the converted packed frames.  Same `crop_hw`, `to_nchw`, `to_stem`, `n_out`, `gathers` and `center_window`."""
 
-    frame_dims = 2              # trailing dimensions of one frame (packed frames: 3), for the engines' flattening
+    frame_dims = 2
 
     def __init__(self, *args, layout="i420", standard=0, order="bgr", pitch=None, width=None, **kwargs):
         super().__init__(*args, **kwargs)
@@ -752,16 +667,8 @@ class Yuv420FramePipeline(GatherFramePipeline):
         if self.width is not None and (self.width < 1 or (self.pitch is not None and self.width > self.pitch)):
             raise ValueError("Yuv420FramePipeline: width=%d must lie in [1, pitch]" % self.width)
 
-    def n_out(self, frames, rows):
-        if self.gathers(rows):
-            return int(rows.reshape(-1, rows.shape[-1]).shape[0])
-        n = 1
-        for d in frames.shape[:-2]:
-            n *= int(d)
-        return n
-
-    def _frames(self, frames):
-        """-> ((n_src, 3 * Hs / 2, pitch) contiguous, Hs, Ws)."""
+    def _source(self, frames):
+        """-> (the frames flattened to (n_src, 3 * Hs / 2, pitch) contiguous, n_src, Hs, Ws)."""
         if frames.dtype != torch.uint8 or frames.dim() < 2 or not frames.is_cuda:
             raise TypeError("Yuv420FramePipeline expects a CUDA uint8 tensor (..., 3 * Hs / 2, pitch) of YUV 4:2:0 frames, got %s %s"
                             % (frames.dtype, tuple(frames.shape)))
@@ -773,36 +680,15 @@ class Yuv420FramePipeline(GatherFramePipeline):
         ws = pitch if self.width is None else self.width
         if ws > pitch:
             raise ValueError("Yuv420FramePipeline: width=%d exceeds the frames' %d-byte rows" % (ws, pitch))
-        return frames.reshape(-1, rows3, pitch).contiguous(), rows3 // 3 * 2, ws
+        f = frames.reshape(-1, rows3, pitch).contiguous()
+        return f, f.shape[0], rows3 // 3 * 2, ws
 
-    def _run(self, frames, rows, pad, wp, dtype, out=None, nchw=False):
-        f, hs, ws = self._frames(frames)
-        n_src, pitch = f.shape[0], f.shape[2]
-        if self.gathers(rows):
-            r, col, src = self._gather(rows, n_src, hs, ws)
-        else:
-            r, col = self._split(rows, n_src, hs, ws)
-            src = None
-        n, (h, w) = r.shape[0], self.crop_hw
-        shape = (n, 3, h, w) if nchw else (n, h + 2 * pad, wp, 4)
-        if out is None:
-            out = torch.empty(shape, dtype=dtype, device=f.device)
-        elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous():
-            raise ValueError("Yuv420FramePipeline: the output buffer %s %s does not hold the table's %d images %s" % (out.dtype, tuple(out.shape), n, shape))
-        check(lib.mvf_frames_yuv420_gather_resample_u8(f.data_ptr(), n_src, hs, ws, pitch, self.layout, self.standard, self.order,
-                                                       src.data_ptr() if src is not None else None, n, r.data_ptr(),
-                                                       col.data_ptr() if col is not None else None, h, w, self.mean, self.std, int(self.to_rgb),
-                                                       int(self.div_255), pad, wp, None if nchw else out.data_ptr(), out.data_ptr() if nchw else None,
-                                                       _DT[dtype], torch.cuda.current_stream().cuda_stream), "mvf_frames_yuv420_gather_resample_u8")
-        return out
-
-    def to_nchw(self, frames, rows):
-        """-> (n_out, 3, h, w) fp32: GatherFramePipeline.to_nchw of the converted packed frames."""
-        return self._run(frames, rows, 0, self.crop_hw[1], torch.float32, nchw=True)
-
-    def to_stem(self, frames, rows, pad, wp, dtype, out=None):
-        """-> (n_out, h + 2 pad, wp, 4) `dtype`, the stem conv's operand (FramePipeline.to_stem) for the table's images."""
-        return self._run(frames, rows, pad, wp, dtype, out=out)
+    def _launch(self, f, n_src, hs, ws, geo, color, src, n, pad, wp, out_stem, out_nchw, dt):
+        h, w = self.crop_hw
+        check(lib.mvf_frames_yuv420_gather_resample_u8(f.data_ptr(), n_src, hs, ws, f.shape[2], self.layout, self.standard, self.order, _ptr(src), n,
+                                                       geo.data_ptr(), _ptr(color), h, w, self.mean, self.std, int(self.to_rgb), int(self.div_255),
+                                                       pad, wp, out_stem, out_nchw, dt, torch.cuda.current_stream().cuda_stream),
+              "mvf_frames_yuv420_gather_resample_u8")
 
 
 # ---- frame-index arithmetic (host side; reference codes/datasets/pipelines/loading.py:11-131) ------------------------------------

@@ -121,6 +121,14 @@ def test_pipeline_argument_validation_needs_no_gpu():
         pipe.to_nchw(torch.zeros(2, 72, 64), rows)
 
 
+def test_every_pipeline_class_shares_one_to_nchw_and_one_to_stem():
+    """One run path per ladder: no subclass redefines the pair, so a new layer cannot quietly fork them again."""
+    from mvfnet_amd import preprocess as P
+    for cls in (P.ResamplingFramePipeline, P.JitterFramePipeline, P.GatherFramePipeline, P.Yuv420FramePipeline):
+        assert cls.to_nchw is P.FramePipeline.to_nchw and cls.to_stem is P.FramePipeline.to_stem and cls._run is P.FramePipeline._run
+    assert (P.FramePipeline.frame_dims, P.GatherFramePipeline.frame_dims, P.Yuv420FramePipeline.frame_dims) == (3, 3, 2)
+
+
 def _prototype(name):
     src = open(os.path.join(os.path.dirname(HERE), "include", "mvfnet_hip.h")).read()
     m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, src)
