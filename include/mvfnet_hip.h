@@ -273,6 +273,28 @@ int mvf_frames_yuv420_gather_resample_u8(const unsigned char* frames, int n_src,
                                          const int* src_index, int n_out, const int* rows, const float* color, int h, int w, const float* mean3,
                                          const float* std3, int to_rgb, int div_255, int pad, int wp, void* out_stem, float* out_nchw, int dtype,
                                          void* stream);
+/* mvf_frames_gather_resample_u8 / mvf_frames_yuv420_gather_resample_u8 over frames WHERE AND HOW THE DECODER LEFT THEM: instead of a dense
+ * batch in which every frame shares one padded extent and one row pitch, every output image carries the byte offsets and row pitches of
+ * the planes it is cut from.  frames = one byte buffer of frames_bytes bytes, 1 <= frames_bytes < 2^31 (so offsets fit int32);
+ *   format 0 = packed 3-byte pixels in stored channel order (standard and order are ignored), 1 = I420, 2 = NV12; standard and order as in
+ *   mvf_frames_yuv420_gather_resample_u8.
+ * rows = device int32 (n_out, 11) and color = device fp32 (n_out, 12) or NULL as in mvf_frames_gather_resample_u8, one row per OUTPUT image;
+ * addr = device int32 (n_out, 5), (o0, p0, o1, o2, p1): byte offsets from `frames` and row pitches in bytes of the image row i is cut from:
+ *   format 0: pixel (y, x) at o0 + y * p0 + 3 * x;  o1 = o2 = p1 = 0;
+ *   I420:     luma at o0 + y * p0 + x, U at o1 + (y >> 1) * p1 + (x >> 1), V at o2 + (y >> 1) * p1 + (x >> 1);
+ *   NV12:     luma as I420, U at o1 + (y >> 1) * p1 + 2 * (x >> 1), V one byte after it;  o2 = 0.
+ * Pitches may be odd and may exceed the row; a frame of odd size has chroma planes of ceil(hs_i / 2) x ceil(ws_i / 2) samples.  Rows may name
+ * the same planes -- that is how clips and crops share a decoded frame, so there is no src_index -- and images of one launch may differ in
+ * size, pitch and plane placement.  Addresses are formed in 64-bit arithmetic.  The arithmetic per pixel is the dense exports': for format 0
+ * the result equals mvf_frames_gather_resample_u8 on the dense batch that holds the same frames, for formats 1 and 2
+ * mvf_frames_yuv420_gather_resample_u8 likewise, bit for bit, both outputs and both dtypes; bytes outside the addressed planes never reach
+ * the result.  An unknown format / standard / order / dtype, NULL rows or addr, frames_bytes outside [1, 2^31) and wp < w + 2 * pad return
+ * MVF_EINVAL; the CONTENTS of rows and addr are NOT checked here (the caller validates them, preprocess.check_addresses: a bad offset or
+ * pitch reads out of bounds).  Everything else as mvf_frames_gather_resample_u8. */
+int mvf_frames_addressed_resample_u8(const unsigned char* frames, long long frames_bytes, int format, int standard, int order,
+                                     int n_out, const int* rows, const int* addr, const float* color, int h, int w,
+                                     const float* mean3, const float* std3, int to_rgb, int div_255, int pad, int wp,
+                                     void* out_stem, float* out_nchw, int dtype, void* stream);
 
 /* MaxPool2d(3, stride 2, pad 1) on NHWC (resnet.py:431,484). */
 int mvf_maxpool3x3s2_nhwc(const void* x, int n, int h, int w, int c, void* y, int dtype, void* stream);

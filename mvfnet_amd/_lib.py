@@ -139,6 +139,9 @@ def _load():
     lib.mvf_frames_yuv420_gather_resample_u8.restype = i32
     lib.mvf_frames_yuv420_gather_resample_u8.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, i32, i32, C.POINTER(C.c_float),
                                                          C.POINTER(C.c_float), i32, i32, i32, i32, vp, vp, i32, vp]
+    lib.mvf_frames_addressed_resample_u8.restype = i32
+    lib.mvf_frames_addressed_resample_u8.argtypes = [vp, C.c_longlong, i32, i32, i32, i32, vp, vp, vp, i32, i32, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                                     i32, i32, i32, i32, vp, vp, i32, vp]
     lib.mvf_maxpool3x3s2_nhwc.restype = i32
     lib.mvf_maxpool3x3s2_nhwc.argtypes = [vp, i32, i32, i32, i32, vp, i32, vp]
     lib.mvf_head_pool_fc.restype = i32

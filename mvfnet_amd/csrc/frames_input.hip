@@ -1,6 +1,7 @@
 // The uint8 frame input: decoded frames (packed HWC, or decoder-native YUV 4:2:0) -> the normalised stem operand and / or the reference's
 // fp32 NCHW tensor.  frames_prep_kernel crops; the two resample kernels put cv2's resize, the frame gather and ColorJitter in front of the
-// crop, and share every step but the fetch of their four taps (the __device__ helpers below).
+// crop, and share every step but the fetch of their four taps (the __device__ helpers below).  Where an image's source rows start is the
+// kernels' SRC parameter: DenseSrc (frame index times a constant) or AddressedSrc (offsets and pitches the image's table row carries).
 #include <algorithm>
 #include <math.h>
 #include <type_traits>
@@ -15,7 +16,7 @@ struct FramePrep {
     int to_rgb, div_255;
 };
 
-constexpr int RS_COLS = 11, CJ_COLS = 12;
+constexpr int RS_COLS = 11, CJ_COLS = 12, AD_COLS = 5;
 
 // ---- the steps of a resampled pixel, in order ----------------------------------------------------------------------------------------
 // Row setup (block-uniform).  r = the frame's int32 row (hs_i, ws_i, by, bx, bh, bw, rh, rw, oy, ox, flip): the patch [by, by+bh) x
@@ -155,14 +156,67 @@ __global__ void frames_prep_kernel(const unsigned char* frames, int n, int hs, i
     }
 }
 
-// The resample in front of the crop, packed (n_src, hs, ws, 3) frames.  Block = one (image, padded output row): the row's descriptor,
+// ---- the address step: where the source rows of output image `img` start -------------------------------------------------------------
+// Block-uniform like the geometry row (blockIdx only: scalar loads), read once per block, formed in 64-bit arithmetic; it enters nothing
+// but the row base pointers.  YuvSrc (below) carries the colour standard and, for DenseSrc, the one layout every frame shares.
+struct YuvSrc {
+    int y_off, cy, cvr, cvg, cug, cub;      // rint(c * 2^20) of the standard's decimal coefficients
+    int pitch, cstride, cstep;              // bytes: luma row, chroma row, chroma sample (DenseSrc; AddressedSrc reads cstep alone)
+    long u_off, v_delta, frame_bytes;       // U plane in the frame, V sample - U sample, frame stride (DenseSrc)
+    int swap_rb;                            // stored order BGR: R and B change places after the conversion
+};
+// Frame src_index[img] (NULL = img) of one dense batch in which every frame has the same padded extent and pitch: index times a constant.
+struct DenseSrc {
+    const int* src_index;
+    int hs, ws;
+    __device__ __forceinline__ void packed(const unsigned char* frames, int img, int y0, int y1, const unsigned char*& s0, const unsigned char*& s1) const {
+        const int src = src_index ? src_index[img] : img;
+        s0 = frames + ((long)src * hs + y0) * ws * 3;
+        s1 = frames + ((long)src * hs + y1) * ws * 3;
+    }
+    __device__ __forceinline__ void yuv(const unsigned char* frames, const YuvSrc& ys, int img, int y0, int y1, const unsigned char*& l0,
+                                        const unsigned char*& l1, const unsigned char*& u0, const unsigned char*& u1, const unsigned char*& v0,
+                                        const unsigned char*& v1) const {
+        const int src = src_index ? src_index[img] : img;
+        const unsigned char* fr = frames + (long)src * ys.frame_bytes;
+        l0 = fr + (long)y0 * ys.pitch, l1 = fr + (long)y1 * ys.pitch;
+        u0 = fr + ys.u_off + (long)(y0 >> 1) * ys.cstride, u1 = fr + ys.u_off + (long)(y1 >> 1) * ys.cstride;
+        v0 = u0 + ys.v_delta, v1 = u1 + ys.v_delta;
+    }
+};
+// mvf_frames_addressed_resample_u8: the image's int32 address row (o0, p0, o1, o2, p1) = byte offsets from `frames` and row pitches of the
+// planes it is cut from -- packed: pixels at o0 + y p0 + 3 x; YUV: luma at o0 + y p0 + x, U at o1 + (y >> 1) p1 + cstep (x >> 1), V
+// likewise from o2 (I420) or one byte after U (NV12).  Rows are validated on the host (preprocess.check_addresses).
+struct AddressedSrc {
+    const int* addr;
+    __device__ __forceinline__ void packed(const unsigned char* frames, int img, int y0, int y1, const unsigned char*& s0, const unsigned char*& s1) const {
+        const int* a = addr + (long)img * AD_COLS;
+        const unsigned char* fr = frames + (long)a[0];
+        const long p0 = a[1];
+        s0 = fr + y0 * p0;
+        s1 = fr + y1 * p0;
+    }
+    __device__ __forceinline__ void yuv(const unsigned char* frames, const YuvSrc& ys, int img, int y0, int y1, const unsigned char*& l0,
+                                        const unsigned char*& l1, const unsigned char*& u0, const unsigned char*& u1, const unsigned char*& v0,
+                                        const unsigned char*& v1) const {
+        const int* a = addr + (long)img * AD_COLS;
+        const long o0 = a[0], p0 = a[1], o1 = a[2], o2 = a[3], p1 = a[4];
+        const long c0 = (y0 >> 1) * p1, c1 = (y1 >> 1) * p1;
+        l0 = frames + o0 + y0 * p0, l1 = frames + o0 + y1 * p0;
+        u0 = frames + o1 + c0, u1 = frames + o1 + c1;
+        const bool nv12 = ys.cstep == 2;
+        v0 = nv12 ? u0 + 1 : frames + o2 + c0;
+        v1 = nv12 ? u1 + 1 : frames + o2 + c1;
+    }
+};
+
+// The resample in front of the crop, packed 3-byte pixels.  Block = one (image, padded output row): the row's descriptor,
 // source rows and y weights are block-uniform; lanes run along x (two source rows, byte loads of neighbouring pixels), one 8/16-byte
 // store per pixel as stem_prep_kernel.
-// src_index (mvf_frames_gather_resample_u8): output image `img` is cut from frame src_index[img] instead of frame img, so the crops and
-// clips of a video share its decoded frames; block-uniform like the row (blockIdx only: a scalar load), read once per block, and it
-// enters nothing but the source-row base addresses.  NULL = img.
-template <typename ET, bool COLOR>
-__global__ void frames_resample_kernel(const unsigned char* frames, int hs, int ws, const int* src_index, const int* rows, const float* color,
+// DenseSrc::src_index (mvf_frames_gather_resample_u8): output image `img` is cut from frame src_index[img] instead of frame img, so the
+// crops and clips of a video share its decoded frames.
+template <typename ET, bool COLOR, typename SRC>
+__global__ void frames_resample_kernel(const unsigned char* frames, SRC src, const int* rows, const float* color,
                                        int h, int w, FramePrep fp, int pad, int hp, int wp, ET* out_stem, float* out_nchw) {
     const int orow = blockIdx.x, img = orow / hp, yo = orow - img * hp;
     float cm[CJ_COLS];
@@ -170,9 +224,10 @@ __global__ void frames_resample_kernel(const unsigned char* frames, int hs, int 
     const int ih = yo - pad;
     const bool rok = ih >= 0 && ih < h;
     const RowSetup rs = row_setup(rows + (long)img * RS_COLS, rok, ih);
-    const int src = src_index ? src_index[img] : img;
-    const unsigned char* s0 = frames + (((long)src * hs + rs.by + rs.y0) * ws + rs.bx) * 3;
-    const unsigned char* s1 = frames + (((long)src * hs + rs.by + rs.y1) * ws + rs.bx) * 3;
+    const unsigned char *s0, *s1;
+    src.packed(frames, img, rs.by + rs.y0, rs.by + rs.y1, s0, s1);
+    s0 += rs.bx * 3;
+    s1 += rs.bx * 3;
     for (int xo = threadIdx.x; xo < wp; xo += blockDim.x) {
         const int iw = xo - pad;
         float v[3] = {0.f, 0.f, 0.f};
@@ -190,19 +245,14 @@ __global__ void frames_resample_kernel(const unsigned char* frames, int hs, int 
     }
 }
 
-// The same for decoder-native YUV 4:2:0 frames (mvf_frames_yuv420_gather_resample_u8): a frame is a (3 * hs / 2, pitch) byte image -- hs
-// luma rows, then I420's U and V planes (hs / 2 rows of pitch / 2 bytes each) or NV12's hs / 2 rows of interleaved U, V pairs -- and
-// stands for the packed frame the kernel above would have been given: each of the four taps is converted to the stored triple with the
-// header's 20-bit integer formula, chroma REPLICATED from sample (y >> 1, x >> 1) of the absolute frame coordinate.  The luma / chroma
-// row base addresses are block-uniform (the two layouts differ only in the uniform chroma row stride, sample step and V offset).  The
-// twelve byte loads of a lane are UNCONDITIONAL on clamped coordinates (maxpool_kernel's comment: a load inside an `if` is waited for on
-// the spot) -- a padding lane or row computes a pixel of the crop's border and stores zeros.
-struct YuvSrc {
-    int y_off, cy, cvr, cvg, cug, cub;      // rint(c * 2^20) of the standard's decimal coefficients
-    int pitch, cstride, cstep;              // bytes: luma row, chroma row, chroma sample
-    long u_off, v_delta, frame_bytes;       // U plane in the frame, V sample - U sample, frame stride
-    int swap_rb;                            // stored order BGR: R and B change places after the conversion
-};
+// The same for decoder-native YUV 4:2:0 frames (mvf_frames_yuv420_gather_resample_u8): a DenseSrc frame is a (3 * hs / 2, pitch) byte image
+// -- hs luma rows, then I420's U and V planes (hs / 2 rows of pitch / 2 bytes each) or NV12's hs / 2 rows of interleaved U, V pairs --, an
+// AddressedSrc frame is its three (NV12: two) planes wherever its address row puts them; either stands for the packed frame the kernel
+// above would have been given: each of the four taps is converted to the stored triple with the header's 20-bit integer formula, chroma
+// REPLICATED from sample (y >> 1, x >> 1) of the absolute frame coordinate.  The luma / chroma row base addresses are block-uniform (the
+// two layouts differ only in the uniform chroma row stride, sample step and V offset).  The twelve byte loads of a lane are UNCONDITIONAL
+// on clamped coordinates (maxpool_kernel's comment: a load inside an `if` is waited for on the spot) -- a padding lane or row computes a
+// pixel of the crop's border, inside the image's own planes under either SRC, and stores zeros.
 __device__ __forceinline__ void yuv_to_rgb(int y, int u, int v, const YuvSrc& ys, int* rgb) {
     const int yp = max(0, y - ys.y_off) * ys.cy + (1 << 19);
     u -= 128;
@@ -211,8 +261,8 @@ __device__ __forceinline__ void yuv_to_rgb(int y, int u, int v, const YuvSrc& ys
     rgb[1] = min(max((yp - ys.cvg * v - ys.cug * u) >> 20, 0), 255);
     rgb[2] = min(max((yp + ys.cub * u) >> 20, 0), 255);
 }
-template <typename ET, bool COLOR>
-__global__ void frames_yuv420_resample_kernel(const unsigned char* frames, YuvSrc ys, const int* src_index, const int* rows, const float* color,
+template <typename ET, bool COLOR, typename SRC>
+__global__ void frames_yuv420_resample_kernel(const unsigned char* frames, YuvSrc ys, SRC src, const int* rows, const float* color,
                                               int h, int w, FramePrep fp, int pad, int hp, int wp, ET* out_stem, float* out_nchw) {
     const int orow = blockIdx.x, img = orow / hp, yo = orow - img * hp;
     float cm[CJ_COLS];
@@ -220,11 +270,8 @@ __global__ void frames_yuv420_resample_kernel(const unsigned char* frames, YuvSr
     const int ih = yo - pad;
     const bool rok = ih >= 0 && ih < h;
     const RowSetup rs = row_setup(rows + (long)img * RS_COLS, rok, ih);
-    const int src = src_index ? src_index[img] : img;
-    const unsigned char* fr = frames + (long)src * ys.frame_bytes;
-    const unsigned char *l0 = fr + (long)(rs.by + rs.y0) * ys.pitch, *l1 = fr + (long)(rs.by + rs.y1) * ys.pitch;
-    const unsigned char *u0 = fr + ys.u_off + (long)((rs.by + rs.y0) >> 1) * ys.cstride, *u1 = fr + ys.u_off + (long)((rs.by + rs.y1) >> 1) * ys.cstride;
-    const unsigned char *v0 = u0 + ys.v_delta, *v1 = u1 + ys.v_delta;
+    const unsigned char *l0, *l1, *u0, *u1, *v0, *v1;
+    src.yuv(frames, ys, img, rs.by + rs.y0, rs.by + rs.y1, l0, l1, u0, u1, v0, v1);
     for (int xo = threadIdx.x; xo < wp; xo += blockDim.x) {
         const int iw = xo - pad;
         const bool ok = rok && iw >= 0 && iw < w;
@@ -276,14 +323,12 @@ void with_dtype_color(int dtype, bool color, void* out_stem, F launch) {
     else launch((bf16_t*)out_stem, std::true_type());
 }
 
-// mvf_frames_resample_u8 (color == nullptr), mvf_frames_resample_color_u8, mvf_frames_gather_resample_u8 (n = output images, of
-// n_src source frames) and mvf_frames_yuv420_gather_resample_u8 (yuv != nullptr: the frames are YUV 4:2:0): one validation, one launch
-int frames_resample(const char* who, const unsigned char* frames_hwc, int n_src, int n, int hs, int ws, const int* src_index, const int* rows,
-                    const float* color, int h, int w, const float* mean3, const float* std3, int to_rgb, int div_255, int pad, int wp,
-                    void* out_stem, float* out_nchw, int dtype, void* stream, const YuvSrc* yuv = nullptr) {
-    MVF_REQUIRE(frames_hwc && rows && mean3 && std3 && (out_stem || out_nchw) && n_src > 0 && n > 0 && hs > 0 && ws > 0 && h > 0 && w > 0 && pad >= 0,
-                MVF_EINVAL, "%s: bad argument", who);
-    MVF_REQUIRE(src_index || n_src == n, MVF_EINVAL, "%s: n_src=%d != n_out=%d without src_index", who, n_src, n);
+// Every resample export: one validation, one launch.  `src` is the kernels' address step; yuv != nullptr: the frames are YUV 4:2:0.
+template <typename SRC>
+int frames_resample(const char* who, const unsigned char* frames, const SRC& src, int n, const int* rows, const float* color, int h, int w,
+                    const float* mean3, const float* std3, int to_rgb, int div_255, int pad, int wp, void* out_stem, float* out_nchw, int dtype,
+                    void* stream, const YuvSrc* yuv = nullptr) {
+    MVF_REQUIRE(frames && rows && mean3 && std3 && (out_stem || out_nchw) && n > 0 && h > 0 && w > 0 && pad >= 0, MVF_EINVAL, "%s: bad argument", who);
     MVF_REQUIRE(!out_stem || wp >= w + 2 * pad, MVF_EINVAL, "%s: wp=%d < w + 2*pad", who, wp);
     MVF_REQUIRE(dtype == MVF_F32 || dtype == MVF_BF16, MVF_EINVAL, "%s: bad dtype", who);
     FramePrep fp;
@@ -297,13 +342,42 @@ int frames_resample(const char* who, const unsigned char* frames_hwc, int n_src,
         using ET = std::remove_pointer_t<decltype(out)>;
         constexpr bool COLOR = decltype(col)::value;
         if (yuv)
-            hipLaunchKernelGGL((frames_yuv420_resample_kernel<ET, COLOR>), grid, dim3(256), 0, st, frames_hwc, *yuv, src_index, rows, color, h, w, fp, p, hp,
-                               wpp, out, out_nchw);
+            hipLaunchKernelGGL((frames_yuv420_resample_kernel<ET, COLOR, SRC>), grid, dim3(256), 0, st, frames, *yuv, src, rows, color, h, w, fp, p, hp, wpp,
+                               out, out_nchw);
         else
-            hipLaunchKernelGGL((frames_resample_kernel<ET, COLOR>), grid, dim3(256), 0, st, frames_hwc, hs, ws, src_index, rows, color, h, w, fp, p, hp,
-                               wpp, out, out_nchw);
+            hipLaunchKernelGGL((frames_resample_kernel<ET, COLOR, SRC>), grid, dim3(256), 0, st, frames, src, rows, color, h, w, fp, p, hp, wpp, out,
+                               out_nchw);
     });
     MVF_LAUNCH_CHECK();
+    return MVF_OK;
+}
+
+// mvf_frames_resample_u8 (color == nullptr), mvf_frames_resample_color_u8, mvf_frames_gather_resample_u8 (n = output images, of n_src source
+// frames) and mvf_frames_yuv420_gather_resample_u8: the dense batch's own checks in front of frames_resample
+int frames_resample_dense(const char* who, const unsigned char* frames_hwc, int n_src, int n, int hs, int ws, const int* src_index, const int* rows,
+                          const float* color, int h, int w, const float* mean3, const float* std3, int to_rgb, int div_255, int pad, int wp,
+                          void* out_stem, float* out_nchw, int dtype, void* stream, const YuvSrc* yuv = nullptr) {
+    MVF_REQUIRE(n_src > 0 && hs > 0 && ws > 0, MVF_EINVAL, "%s: bad argument", who);
+    MVF_REQUIRE(src_index || n_src == n || n <= 0, MVF_EINVAL, "%s: n_src=%d != n_out=%d without src_index", who, n_src, n);
+    return frames_resample(who, frames_hwc, DenseSrc{src_index, hs, ws}, n, rows, color, h, w, mean3, std3, to_rgb, div_255, pad, wp, out_stem, out_nchw,
+                           dtype, stream, yuv);
+}
+
+// The header's table of 20-bit conversion constants -> ys; the layout fields are the caller's
+int fill_yuv_standard(const char* who, int standard, int order, YuvSrc* ys) {
+    MVF_REQUIRE(standard >= 0 && standard <= 2, MVF_EINVAL, "%s: unknown standard %d (0 = BT.601 limited, 1 = BT.601 full, 2 = BT.709 limited)", who,
+                standard);
+    MVF_REQUIRE(order == 0 || order == 1, MVF_EINVAL, "%s: unknown order %d (0 = BGR, 1 = RGB)", who, order);
+    // y_off, cY, cVR, cVG, cUG, cUB: the header's table
+    static const double coef[3][6] = {{16, 1.164, 1.596, 0.813, 0.391, 2.018},
+                                      {0, 1.0, 1.402, 0.714136, 0.344136, 1.772},
+                                      {16, 1.164384, 1.792741, 0.532909, 0.213249, 2.112402}};
+    const double* c = coef[standard];
+    const double one = (double)(1 << 20);
+    ys->y_off = (int)c[0];
+    ys->cy = (int)rint(c[1] * one), ys->cvr = (int)rint(c[2] * one), ys->cvg = (int)rint(c[3] * one);
+    ys->cug = (int)rint(c[4] * one), ys->cub = (int)rint(c[5] * one);
+    ys->swap_rb = order == 0;
     return MVF_OK;
 }
 
@@ -336,22 +410,22 @@ int mvf_frames_prep_u8(const unsigned char* frames_hwc, int n, int hs, int ws, c
 int mvf_frames_resample_u8(const unsigned char* frames_hwc, int n, int hs, int ws, const int* rows, int h, int w,
                            const float* mean3, const float* std3, int to_rgb, int div_255, int pad, int wp, void* out_stem,
                            float* out_nchw, int dtype, void* stream) {
-    return frames_resample("frames_resample_u8", frames_hwc, n, n, hs, ws, nullptr, rows, nullptr, h, w, mean3, std3, to_rgb, div_255, pad, wp, out_stem,
-                           out_nchw, dtype, stream);
+    return frames_resample_dense("frames_resample_u8", frames_hwc, n, n, hs, ws, nullptr, rows, nullptr, h, w, mean3, std3, to_rgb, div_255, pad, wp,
+                                 out_stem, out_nchw, dtype, stream);
 }
 
 int mvf_frames_resample_color_u8(const unsigned char* frames_hwc, int n, int hs, int ws, const int* rows, const float* color, int h, int w,
                                  const float* mean3, const float* std3, int to_rgb, int div_255, int pad, int wp, void* out_stem,
                                  float* out_nchw, int dtype, void* stream) {
-    return frames_resample("frames_resample_color_u8", frames_hwc, n, n, hs, ws, nullptr, rows, color, h, w, mean3, std3, to_rgb, div_255, pad,
-                           wp, out_stem, out_nchw, dtype, stream);
+    return frames_resample_dense("frames_resample_color_u8", frames_hwc, n, n, hs, ws, nullptr, rows, color, h, w, mean3, std3, to_rgb, div_255, pad,
+                                 wp, out_stem, out_nchw, dtype, stream);
 }
 
 int mvf_frames_gather_resample_u8(const unsigned char* frames_hwc, int n_src, int hs, int ws, const int* src_index, int n_out, const int* rows,
                                   const float* color, int h, int w, const float* mean3, const float* std3, int to_rgb, int div_255, int pad,
                                   int wp, void* out_stem, float* out_nchw, int dtype, void* stream) {
-    return frames_resample("frames_gather_resample_u8", frames_hwc, n_src, n_out, hs, ws, src_index, rows, color, h, w, mean3, std3, to_rgb,
-                           div_255, pad, wp, out_stem, out_nchw, dtype, stream);
+    return frames_resample_dense("frames_gather_resample_u8", frames_hwc, n_src, n_out, hs, ws, src_index, rows, color, h, w, mean3, std3, to_rgb,
+                                 div_255, pad, wp, out_stem, out_nchw, dtype, stream);
 }
 
 int mvf_frames_yuv420_gather_resample_u8(const unsigned char* frames, int n_src, int hs, int ws, int pitch, int layout, int standard, int order,
@@ -362,28 +436,33 @@ int mvf_frames_yuv420_gather_resample_u8(const unsigned char* frames, int n_src,
     MVF_REQUIRE(hs > 0 && ws > 0 && hs % 2 == 0, MVF_EINVAL, "%s: hs=%d must be positive and even (ws=%d)", who, hs, ws);
     MVF_REQUIRE(pitch % 2 == 0 && pitch >= ws, MVF_EINVAL, "%s: pitch=%d must be even and >= ws=%d", who, pitch, ws);
     MVF_REQUIRE(layout == 0 || layout == 1, MVF_EINVAL, "%s: unknown layout %d (0 = I420, 1 = NV12)", who, layout);
-    MVF_REQUIRE(standard >= 0 && standard <= 2, MVF_EINVAL, "%s: unknown standard %d (0 = BT.601 limited, 1 = BT.601 full, 2 = BT.709 limited)", who,
-                standard);
-    MVF_REQUIRE(order == 0 || order == 1, MVF_EINVAL, "%s: unknown order %d (0 = BGR, 1 = RGB)", who, order);
-    // y_off, cY, cVR, cVG, cUG, cUB: the header's table
-    static const double coef[3][6] = {{16, 1.164, 1.596, 0.813, 0.391, 2.018},
-                                      {0, 1.0, 1.402, 0.714136, 0.344136, 1.772},
-                                      {16, 1.164384, 1.792741, 0.532909, 0.213249, 2.112402}};
-    const double* c = coef[standard];
-    const double one = (double)(1 << 20);
     YuvSrc ys;
-    ys.y_off = (int)c[0];
-    ys.cy = (int)rint(c[1] * one), ys.cvr = (int)rint(c[2] * one), ys.cvg = (int)rint(c[3] * one);
-    ys.cug = (int)rint(c[4] * one), ys.cub = (int)rint(c[5] * one);
+    if (const int rc = fill_yuv_standard(who, standard, order, &ys)) return rc;
     ys.pitch = pitch;
     ys.cstride = layout == 0 ? pitch / 2 : pitch;
     ys.cstep = layout == 0 ? 1 : 2;
     ys.u_off = (long)hs * pitch;
     ys.v_delta = layout == 0 ? (long)(hs / 2) * (pitch / 2) : 1;
     ys.frame_bytes = (long)hs * pitch / 2 * 3;
-    ys.swap_rb = order == 0;
-    return frames_resample(who, frames, n_src, n_out, hs, ws, src_index, rows, color, h, w, mean3, std3, to_rgb, div_255, pad, wp, out_stem, out_nchw,
-                           dtype, stream, &ys);
+    return frames_resample_dense(who, frames, n_src, n_out, hs, ws, src_index, rows, color, h, w, mean3, std3, to_rgb, div_255, pad, wp, out_stem,
+                                 out_nchw, dtype, stream, &ys);
+}
+
+int mvf_frames_addressed_resample_u8(const unsigned char* frames, long long frames_bytes, int format, int standard, int order, int n_out,
+                                     const int* rows, const int* addr, const float* color, int h, int w, const float* mean3, const float* std3,
+                                     int to_rgb, int div_255, int pad, int wp, void* out_stem, float* out_nchw, int dtype, void* stream) {
+    const char* who = "frames_addressed_resample_u8";
+    MVF_REQUIRE(format >= 0 && format <= 2, MVF_EINVAL, "%s: unknown format %d (0 = packed, 1 = I420, 2 = NV12)", who, format);
+    MVF_REQUIRE(frames_bytes >= 1 && frames_bytes < (1LL << 31), MVF_EINVAL, "%s: frames_bytes=%lld must lie in [1, 2^31): offsets are int32", who,
+                frames_bytes);
+    MVF_REQUIRE(addr, MVF_EINVAL, "%s: bad argument (addr is NULL)", who);
+    YuvSrc ys = {};
+    if (format != 0) {
+        if (const int rc = fill_yuv_standard(who, standard, order, &ys)) return rc;
+        ys.cstep = format == 1 ? 1 : 2;
+    }
+    return frames_resample(who, frames, AddressedSrc{addr}, n_out, rows, color, h, w, mean3, std3, to_rgb, div_255, pad, wp, out_stem, out_nchw, dtype,
+                           stream, format != 0 ? &ys : nullptr);
 }
 
 }  // extern "C"

@@ -14,7 +14,11 @@ Every pipeline class is `to_nchw(frames, table)` (the reference's fp32 tensor) a
   GatherFramePipeline       11 or 23, or either + 1 `src` column: the image is cut from frames[src], so a video's clips and crops share one
                             upload of its distinct frames (`gather_rows`, `video_test_table`);
   Yuv420FramePipeline       the same four tables over decoder-native planar YUV 4:2:0 frames, I420 or NV12, half the bytes of the packed
-                            frames; the colour conversion runs in the kernel (`collate_yuv_frames`).
+                            frames; the colour conversion runs in the kernel (`collate_yuv_frames`);
+  AddressedFramePipeline    11 or 23 + 5 address columns (o0, p0, o1, o2, p1): the image is cut from planes at byte offsets of one flat
+                            buffer, each frame at its own size and row pitch, packed or YUV 4:2:0 -- a decoder's surfaces as they lie,
+                            both orientations in one batch without padding, videos of different sizes in one launch (`address_rows`,
+                            `check_addresses`, `collate_addressed_frames`).
 A table without the colour or src columns gives the narrower class's output bit for bit."""
 import ctypes
 import math
@@ -275,7 +279,8 @@ class ResamplingFramePipeline(FramePipeline):
         row = [hs, ws, 0, 0, hs, ws, hs, ws, (hs - h) // 2, (ws - w) // 2, int(bool(flip))]
         return torch.tensor([row] * n, dtype=torch.int32, device=device)
 
-    def _parse(self, table, n_src, hs, ws):
+    def _as_table(self, table):
+        """The table as a CUDA int32 (n, cols) tensor, cols one of _COLS."""
         name, takes = type(self).__name__, " / ".join(str(c) for c in self._COLS)
         if table is None:
             raise ValueError("%s needs one int32 row of %s columns per image: (hs_i, ws_i, by, bx, bh, bw, rh, rw, oy, ox, flip) [+ 12 colour] [+ src]" % (name, takes))
@@ -285,9 +290,36 @@ class ResamplingFramePipeline(FramePipeline):
         cols = _ncols(t)
         if cols not in self._COLS:
             raise ValueError("%s rows must have %s columns, got %s" % (name, takes, tuple(t.shape)))
-        t = t.reshape(-1, cols)
-        color = src = None
-        if cols in (RESAMPLE_COLS + 1, JITTER_COLS + 1):          # one row per OUTPUT image, cut from frames[src]
+        return t.reshape(-1, cols)
+
+    def _geometry(self, t, hs, ws):
+        """(n, 11 or 23) -> (geo, color) checked: every patch in its frame (and the frame in the hs x ws padded extent, when the batch has
+        one), every crop in its resized patch."""
+        color = None
+        if t.shape[1] == JITTER_COLS:
+            t, color = t[:, :RESAMPLE_COLS], t[:, RESAMPLE_COLS:].contiguous().view(torch.float32)
+        geo = t.contiguous()
+        h, w = self.crop_hw
+        fh, fw, by, bx, bh, bw, rh, rw, oy, ox, flip = geo.to(torch.int64).unbind(1)
+        bad = ((fh < 1) | (fw < 1)
+               | (by < 0) | (bx < 0) | (bh < 1) | (bw < 1) | (by + bh > fh) | (bx + bw > fw)
+               | (oy < 0) | (ox < 0) | (oy + h > rh) | (ox + w > rw)
+               | ((flip != 0) & (flip != 1)))
+        if hs is not None:
+            bad = bad | (fh > hs) | (fw > ws)                     # every frame shares the hs x ws padded extent: the check holds per src
+        if bool(bad.any()):
+            i = int(bad.nonzero()[0, 0])
+            where = "its %dx%d-padded frame" % (hs, ws) if hs is not None else "its own hs_i x ws_i frame"
+            raise ValueError("row %d %s: the patch must lie in %s and the %dx%d crop in the resized patch" % (i, geo[i].tolist(), where, h, w))
+        if color is not None and not bool(torch.isfinite(color).all()):
+            raise ValueError("%s: colour coefficients must be finite" % type(self).__name__)
+        return geo, color
+
+    def _parse(self, table, n_src, hs, ws):
+        name = type(self).__name__
+        t = self._as_table(table)
+        src = None
+        if t.shape[1] in (RESAMPLE_COLS + 1, JITTER_COLS + 1):    # one row per OUTPUT image, cut from frames[src]
             if t.shape[0] < 1:
                 raise ValueError("%s: an empty table" % name)
             t, src = t[:, :-1], t[:, -1].contiguous()
@@ -297,21 +329,7 @@ class ResamplingFramePipeline(FramePipeline):
                 raise ValueError("row %d: source frame %d is not one of the %d frames" % (i, int(src[i]), n_src))
         elif t.shape[0] != n_src:
             raise ValueError("rows: %d rows for %d frames" % (t.shape[0], n_src))
-        if t.shape[1] == JITTER_COLS:
-            t, color = t[:, :RESAMPLE_COLS], t[:, RESAMPLE_COLS:].contiguous().view(torch.float32)
-        geo = t.contiguous()
-        h, w = self.crop_hw
-        fh, fw, by, bx, bh, bw, rh, rw, oy, ox, flip = geo.to(torch.int64).unbind(1)
-        bad = ((fh < 1) | (fh > hs) | (fw < 1) | (fw > ws)        # every frame shares the hs x ws padded extent: the check holds per src
-               | (by < 0) | (bx < 0) | (bh < 1) | (bw < 1) | (by + bh > fh) | (bx + bw > fw)
-               | (oy < 0) | (ox < 0) | (oy + h > rh) | (ox + w > rw)
-               | ((flip != 0) & (flip != 1)))
-        if bool(bad.any()):
-            i = int(bad.nonzero()[0, 0])
-            raise ValueError("row %d %s: the patch must lie in its %dx%d-padded frame and the %dx%d crop in the resized patch"
-                             % (i, geo[i].tolist(), hs, ws, h, w))
-        if color is not None and not bool(torch.isfinite(color).all()):
-            raise ValueError("%s: colour coefficients must be finite" % name)
+        geo, color = self._geometry(t, hs, ws)
         return geo, color, src
 
     def _launch(self, f, n_src, hs, ws, geo, color, src, n, pad, wp, out_stem, out_nchw, dt):
@@ -689,6 +707,202 @@ class Yuv420FramePipeline(GatherFramePipeline):
                                                        geo.data_ptr(), _ptr(color), h, w, self.mean, self.std, int(self.to_rgb), int(self.div_255),
                                                        pad, wp, out_stem, out_nchw, dt, torch.cuda.current_stream().cuda_stream),
               "mvf_frames_yuv420_gather_resample_u8")
+
+
+# ---- addressed frames: every image carries the offsets and pitches of its planes --------------------------------------------------------
+ADDR_COLS = 5               # (o0, p0, o1, o2, p1): see include/mvfnet_hip.h mvf_frames_addressed_resample_u8
+FRAME_FORMATS = {"packed": 0, "i420": 1, "nv12": 2}
+
+
+def address_rows(rows, addr):
+    """(n, 11) or (n, 23) int32 rows + (n, 5) int32 address rows (o0, p0, o1, o2, p1) -> ONE (n, 16) or (n, 28) int32 table, the address
+    as the trailing columns: output image i is cut from the planes at those byte offsets and pitches of the buffer handed to
+    AddressedFramePipeline.  A (n, 12) or (n, 24) gather table (gather_rows, video_test_table) is taken with ONE address row per SOURCE
+    frame, (n_src, 5): its `src` column is replaced by addr[src]."""
+    import numpy as np
+    rows, addr = np.asarray(rows, dtype=np.int32), np.asarray(addr)
+    if rows.ndim != 2 or rows.shape[1] not in (RESAMPLE_COLS, JITTER_COLS, RESAMPLE_COLS + 1, JITTER_COLS + 1):
+        raise ValueError("address_rows: rows must have %d, %d, %d or %d columns, got %s"
+                         % (RESAMPLE_COLS, JITTER_COLS, RESAMPLE_COLS + 1, JITTER_COLS + 1, rows.shape))
+    if addr.ndim != 2 or addr.shape[1] != ADDR_COLS:
+        raise ValueError("address_rows: addr must be (n, %d), got %s" % (ADDR_COLS, addr.shape))
+    if addr.size and (addr.min() < np.iinfo(np.int32).min or addr.max() > np.iinfo(np.int32).max):
+        raise ValueError("address_rows: offsets and pitches must fit int32")
+    addr = addr.astype(np.int32)
+    if rows.shape[1] in (RESAMPLE_COLS + 1, JITTER_COLS + 1):
+        rows, src = rows[:, :-1], rows[:, -1]
+        if src.size and (src.min() < 0 or src.max() >= addr.shape[0]):
+            raise ValueError("address_rows: a source frame is not one of the %d addressed frames" % addr.shape[0])
+        addr = addr[src]
+    elif addr.shape[0] != rows.shape[0]:
+        raise ValueError("address_rows: %d address rows for %d rows" % (addr.shape[0], rows.shape[0]))
+    return np.concatenate([rows, addr], axis=1)
+
+
+def split_address_rows(table):
+    """The inverse of address_rows on the host: (n, 16) or (n, 28) int32 -> ((n, 11) or (n, 23) int32, (n, 5) int32 addr)."""
+    import numpy as np
+    table = np.asarray(table, dtype=np.int32)
+    if table.ndim != 2 or table.shape[1] not in (RESAMPLE_COLS + ADDR_COLS, JITTER_COLS + ADDR_COLS):
+        raise ValueError("split_address_rows: the table must have %d or %d columns, got %s"
+                         % (RESAMPLE_COLS + ADDR_COLS, JITTER_COLS + ADDR_COLS, table.shape))
+    return table[:, :-ADDR_COLS].copy(), table[:, -ADDR_COLS:].copy()
+
+
+def check_addresses(rows, addr, format, frames_bytes):
+    """The address rows (n, 5) of images whose geometry rows (n, >= 2: hs_i, ws_i lead) are `rows`, against a buffer of frames_bytes bytes
+    in `format` ('packed' | 'i420' | 'nv12' or 0 / 1 / 2).  Returns silently, or raises ValueError naming the first bad row.  Required:
+    offsets >= 0; pitches >= the plane's row bytes (3 ws_i packed; ws_i luma; ceil(ws_i / 2) I420 chroma, 2 ceil(ws_i / 2) NV12 chroma);
+    the last byte of every plane < frames_bytes; the columns the format does not use 0; 1 <= frames_bytes < 2^31.
+    numpy arrays or tensors; the arithmetic is int64 torch on the tensors' own device (AddressedFramePipeline runs it on the GPU)."""
+    import numpy as np
+    fmt, frames_bytes = _enum("format", format, FRAME_FORMATS), int(frames_bytes)
+    if frames_bytes < 1 or frames_bytes >= (1 << 31):
+        raise ValueError("check_addresses: frames_bytes=%d must lie in [1, 2^31): offsets are int32" % frames_bytes)
+    rows = rows if isinstance(rows, torch.Tensor) else torch.as_tensor(np.asarray(rows))
+    addr = addr if isinstance(addr, torch.Tensor) else torch.as_tensor(np.asarray(addr))
+    if addr.dim() != 2 or addr.shape[1] != ADDR_COLS or rows.dim() != 2 or rows.shape[1] < 2 or rows.shape[0] != addr.shape[0]:
+        raise ValueError("check_addresses: (n, >= 2) geometry rows and (n, %d) address rows, got %s and %s" % (ADDR_COLS, tuple(rows.shape), tuple(addr.shape)))
+    hs, ws = rows[:, 0].to(torch.int64), rows[:, 1].to(torch.int64)
+    o0, p0, o1, o2, p1 = addr.to(device=rows.device, dtype=torch.int64).unbind(1)
+    ch, cw = (hs + 1) // 2, (ws + 1) // 2
+    # (offset, pitch, rows, row bytes) of every plane, and the columns that must be 0
+    if fmt == 0:
+        planes, unused = [(o0, p0, hs, 3 * ws)], (o1, o2, p1)
+    elif fmt == 1:
+        planes, unused = [(o0, p0, hs, ws), (o1, p1, ch, cw), (o2, p1, ch, cw)], ()
+    else:
+        planes, unused = [(o0, p0, hs, ws), (o1, p1, ch, 2 * cw)], (o2,)
+    def any_of(masks):
+        out = torch.zeros_like(hs, dtype=torch.bool)
+        for m in masks:
+            out = out | m
+        return out
+    faults = {"a frame size below 1": (hs < 1) | (ws < 1),
+              "a negative offset": any_of(o < 0 for o, _, _, _ in planes),
+              "a pitch below the plane's row bytes": any_of(p < rb for _, p, _, rb in planes),
+              "a plane that ends past frames_bytes=%d" % frames_bytes: any_of(o + (n - 1) * p + rb > frames_bytes for o, p, n, rb in planes),
+              "a non-zero column the format does not use": any_of(u != 0 for u in unused)}
+    bad = any_of(faults.values())
+    if bool(bad.any()):
+        i = int(bad.nonzero()[0, 0])
+        why = [k for k, v in faults.items() if bool(v[i])]
+        raise ValueError("check_addresses: row %d, a %dx%d %s frame at (o0, p0, o1, o2, p1) = %s: %s"
+                         % (i, int(hs[i]), int(ws[i]), sorted(FRAME_FORMATS, key=FRAME_FORMATS.get)[fmt], addr[i].tolist(), "; ".join(why)))
+
+
+def _round_up(v, a):
+    return (v + a - 1) // a * a
+
+
+def collate_addressed_frames(groups, format, slot_bytes=None, pitch_align=1, plane_align=64, fill=0, cols=None):
+    """collate_frames / collate_yuv_frames without the padding to a bounding box.  groups: a list of (frames, rows) per clip -- for
+    format 'packed' frames (T, h_b, w_b, 3) uint8, for 'i420' / 'nv12' the clip's (Y, U, V) planes or one (T, 3 * h_b / 2, w_b) I420 array
+    (as collate_yuv_frames), rows its (T, cols) table, cols 11 (default) or 23 -- -> (frames (B, T, S) uint8, table (B * T, cols + 5)
+    int32), CPU tensors for AddressedFramePipeline.  Every frame lies in its own slot of S bytes at its OWN size and pitch: row pitches
+    are the row bytes rounded up to `pitch_align`, every plane starts at a multiple of `plane_align` in its slot, and S is the largest
+    frame's byte count rounded up to `plane_align` -- or `slot_bytes`, so a prefetcher's pinned buffers keep their shape (ValueError when a
+    frame does not fit).  The table's offsets count from the start of the whole tensor, which stays dense (B, T, S) so that the engines'
+    B, T logic and the stream split work on it unchanged.  Two orientations of one resolution cost no padding; frames of different areas
+    waste only the difference in area.  Bytes no plane owns are `fill`."""
+    import numpy as np
+    fmt = _enum("format", format, FRAME_FORMATS)
+    cols = RESAMPLE_COLS if cols is None else int(cols)
+    pitch_align, plane_align = int(pitch_align), int(plane_align)
+    if cols not in (RESAMPLE_COLS, JITTER_COLS) or pitch_align < 1 or plane_align < 1:
+        raise ValueError("collate_addressed_frames: cols must be %d or %d and the alignments positive" % (RESAMPLE_COLS, JITTER_COLS))
+    if not groups:
+        raise ValueError("collate_addressed_frames: no clips")
+    clips = []                                                    # per clip: [(plane (T, n, row bytes) uint8, pitch)], ...
+    for f, _ in groups:
+        if fmt == 0:
+            f = torch.as_tensor(np.asarray(f))
+            if f.dtype != torch.uint8 or f.dim() != 4 or f.shape[-1] != 3:
+                raise ValueError("collate_addressed_frames: a packed clip must be (T, h, w, 3) uint8, got %s %s" % (f.dtype, tuple(f.shape)))
+            clips.append((f.shape[1], f.shape[2], [f.reshape(f.shape[0], f.shape[1], -1)]))
+        else:
+            y, u, v = _yuv_planes(f, "collate_addressed_frames")
+            clips.append((y.shape[1], y.shape[2], [y, u, v] if fmt == 1 else [y, torch.stack((u, v), dim=-1).reshape(u.shape[0], u.shape[1], -1)]))
+    rows = [torch.as_tensor(np.asarray(r, dtype=np.int32)).reshape(-1, cols) for _, r in groups]
+    t = clips[0][2][0].shape[0]
+    layouts = []                                                  # per clip: [(offset in the slot, pitch)] per plane, and the frame's bytes
+    for (h, w, planes), r in zip(clips, rows):
+        if planes[0].shape[0] != t:
+            raise ValueError("collate_addressed_frames: every clip must have T=%d frames, got %d" % (t, planes[0].shape[0]))
+        if r.shape[0] != t or bool((r[:, 0] != h).any()) or bool((r[:, 1] != w).any()):
+            raise ValueError("collate_addressed_frames: rows do not describe their %dx%d frames" % (h, w))
+        at, lay = 0, []
+        for pl in planes:
+            pitch = _round_up(pl.shape[2], pitch_align)
+            at = _round_up(at, plane_align)
+            lay.append((at, pitch))
+            at += pl.shape[1] * pitch
+        layouts.append((lay, at))
+    need = _round_up(max(n for _, n in layouts), plane_align)
+    slot = need if slot_bytes is None else int(slot_bytes)
+    if slot < max(n for _, n in layouts):
+        raise ValueError("collate_addressed_frames: a frame of %d bytes does not fit slot_bytes=%d" % (max(n for _, n in layouts), slot))
+    if len(clips) * t * slot >= (1 << 31):
+        raise ValueError("collate_addressed_frames: %d x %d slots of %d bytes exceed the 2^31 bytes int32 offsets address" % (len(clips), t, slot))
+    out = torch.full((len(clips), t, slot), int(fill), dtype=torch.uint8)
+    addr = np.zeros((len(clips), t, ADDR_COLS), dtype=np.int64)
+    base = (np.arange(len(clips) * t, dtype=np.int64) * slot).reshape(len(clips), t)
+    for b, ((h, w, planes), (lay, _)) in enumerate(zip(clips, layouts)):
+        for pl, (at, pitch) in zip(planes, lay):
+            out[b, :, at:at + pl.shape[1] * pitch].view(t, pl.shape[1], pitch)[:, :, :pl.shape[2]] = pl
+        addr[b, :, 0], addr[b, :, 1] = base[b] + lay[0][0], lay[0][1]
+        if fmt != 0:
+            addr[b, :, 2], addr[b, :, 4] = base[b] + lay[1][0], lay[1][1]
+        if fmt == 1:
+            addr[b, :, 3] = base[b] + lay[2][0]
+    table = torch.cat([torch.cat(rows), torch.from_numpy(addr.reshape(-1, ADDR_COLS).astype(np.int32))], dim=1).contiguous()
+    return out, table
+
+
+class AddressedFramePipeline(GatherFramePipeline):
+    """GatherFramePipeline over frames where and how the decoder left them (mvf_frames_addressed_resample_u8): `frames` is ANY contiguous
+    CUDA uint8 tensor, taken as one flat byte buffer (collate_addressed_frames builds a (B, T, S) one), and the table is the 11- or 23-column
+    table plus five trailing address columns (address_rows): (o0, p0, o1, o2, p1), the byte offsets and row pitches of the planes output
+    image i is cut from (include/mvfnet_hip.h).  One row per OUTPUT image; rows may name the same planes (a video's clips and crops), and
+    the frames of one launch may differ in size, pitch and plane placement.  Constructor extras: `format` 'packed' (3-byte pixels in stored
+    channel order, what GatherFramePipeline takes) | 'i420' | 'nv12' or 0 / 1 / 2; `standard` and `order` as Yuv420FramePipeline ('packed'
+    ignores both).  Gives, bit for bit, GatherFramePipeline's (Yuv420FramePipeline's) output on the dense batch that holds the same frames.
+    Every table is checked before the launch: the geometry against each row's own (hs_i, ws_i), the addresses with check_addresses.
+    Same `crop_hw`, `to_nchw`, `to_stem` and `n_out`; `gathers` is true for its tables: they name their source, so the engines hand every
+    stream's chain the whole buffer and a slice of the table."""
+
+    frame_dims = 1
+    _COLS = (RESAMPLE_COLS + ADDR_COLS, JITTER_COLS + ADDR_COLS)
+
+    def __init__(self, *args, format="packed", standard=0, order="bgr", **kwargs):
+        super().__init__(*args, **kwargs)
+        self.format, self.standard, self.order = _enum("format", format, FRAME_FORMATS), _enum("standard", standard, YUV_STANDARDS), _enum("order", order, YUV_ORDERS)
+
+    def gathers(self, rows):
+        """True when `rows` carries the address columns (16 or 28 columns)."""
+        return _ncols(rows) in self._COLS
+
+    def _source(self, frames):
+        """-> (the frames as one flat byte buffer, its byte count, None, None): there is no shared frame extent."""
+        if frames.dtype != torch.uint8 or not frames.is_cuda:
+            raise TypeError("AddressedFramePipeline expects a CUDA uint8 tensor (any shape: one flat byte buffer), got %s %s" % (frames.dtype, tuple(frames.shape)))
+        f = frames.contiguous().reshape(-1)
+        return f, f.numel(), None, None
+
+    def _parse(self, table, frames_bytes, hs, ws):
+        t = self._as_table(table)
+        if t.shape[0] < 1:
+            raise ValueError("AddressedFramePipeline: an empty table")
+        t, addr = t[:, :-ADDR_COLS], t[:, -ADDR_COLS:].contiguous()
+        geo, color = self._geometry(t, None, None)
+        check_addresses(geo, addr, self.format, frames_bytes)
+        return geo, color, addr
+
+    def _launch(self, f, frames_bytes, hs, ws, geo, color, addr, n, pad, wp, out_stem, out_nchw, dt):
+        h, w = self.crop_hw
+        check(lib.mvf_frames_addressed_resample_u8(f.data_ptr(), frames_bytes, self.format, self.standard, self.order, n, geo.data_ptr(), addr.data_ptr(),
+                                                   _ptr(color), h, w, self.mean, self.std, int(self.to_rgb), int(self.div_255), pad, wp, out_stem, out_nchw,
+                                                   dt, torch.cuda.current_stream().cuda_stream), "mvf_frames_addressed_resample_u8")
 
 
 # ---- frame-index arithmetic (host side; reference codes/datasets/pipelines/loading.py:11-131) ------------------------------------

@@ -98,7 +98,13 @@ class Recognizer2D(nn.Module):
         (images, 12) or (images, 24) int32 table of gather_rows / video_test_table: one row per output image, its trailing `src` column
         naming the frame the image is cut from, so clips and oversampling crops share one upload; 11 / 23 columns mean "no gather".
         With a preprocess.Yuv420FramePipeline, `img_group` is (B, frames, 3 * Hs / 2, pitch) uint8, decoder-native I420 or NV12 frames, with
-        any of the tables above; the colour conversion runs in that kernel too."""
+        any of the tables above; the colour conversion runs in that kernel too.
+        With a preprocess.AddressedFramePipeline, `img_group` is (B, frames, S) uint8 -- one slot of S bytes per frame, each frame at its own
+        size and row pitch, packed or YUV 4:2:0 (collate_addressed_frames), or any contiguous uint8 tensor whose first two dimensions are
+        B and the frame count -- and `window=` is the (images, 16) or (images, 28) int32 table of address_rows: one row per output image,
+        its five trailing columns the byte offsets and pitches of the planes the image is cut from.  forward_test takes any row count
+        (clips and crops share planes); forward_train takes exactly B * frames rows, so portrait and landscape clips train in one batch
+        without padding to a common bounding box."""
         self.input_pipeline = pipeline
         self.backbone.input_pipeline = pipeline
         return self
@@ -123,13 +129,20 @@ class Recognizer2D(nn.Module):
         """imgs [B, T, 3, H, W], labels [B, 1] -> {'loss_cls': scalar tensor} (reference recognizer2d.py:132-149).
         The returned loss supports .backward(): gradients land in the parameters' .grad (copies of the engine's flat gradient
         buffer; after engine.attach_grads() the .grad tensors ARE views of it), as the reference's DistOptimizerHook expects.
-        A gather table (preprocess.gather_rows: a `src` column) is refused with a ValueError: training makes one image per frame."""
+        A gather table (preprocess.gather_rows: a `src` column) is refused with a ValueError: training makes one image per frame.  An
+        addressed table (preprocess.address_rows: 16 / 28 columns) names its source too, and is taken when it has exactly B * T rows."""
         if not imgs.is_cuda:
             raise RuntimeError("Recognizer2D: mvfnet_amd runs on MI355X tensors only; no CPU fallback (tests use oracle/)")
         pipe, window = getattr(self, "input_pipeline", None), kwargs.get("window")
         if window is not None and getattr(pipe, "gathers", lambda rows: False)(window):
-            raise ValueError("Recognizer2D.forward_train: a gather table (src column, %d columns) is a test-time input -- training makes one "
-                             "image per frame; use the 11- / 23-column table" % window.shape[-1])
+            from ..preprocess import ADDR_COLS, JITTER_COLS, RESAMPLE_COLS
+            if window.shape[-1] not in (RESAMPLE_COLS + ADDR_COLS, JITTER_COLS + ADDR_COLS):
+                raise ValueError("Recognizer2D.forward_train: a gather table (src column, %d columns) is a test-time input -- training makes one "
+                                 "image per frame; use the 11- / 23-column table" % window.shape[-1])
+            n = int(window.reshape(-1, window.shape[-1]).shape[0])                # an addressed table names its planes: one row per frame
+            if imgs.dim() < 2 or n != imgs.shape[0] * imgs.shape[1]:
+                raise ValueError("Recognizer2D.forward_train: an addressed table of %d rows for frames %s -- training makes one image per "
+                                 "frame, B * T rows" % (n, tuple(imgs.shape)))
         if self.with_cls_head and getattr(self.cls_head, "extract_feat", False):
             raise NotImplementedError("Recognizer2D.forward_train: cls_head.extract_feat=True is an eval-mode path (feature extraction)")
         # BatchNorms in eval mode (backbone norm_eval=True / frozen stages / partial_norm, reference resnet.py:496-527) normalise with
