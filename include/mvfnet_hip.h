@@ -550,6 +550,13 @@ typedef struct mvf_sgd_segment {
 int mvf_sgd_step_segments(float* params, const float* grads, float* momentum_buf, long n, float grad_scale, float max_norm, float lr,
                           float momentum, float weight_decay, int first_step, int nesterov, const mvf_sgd_segment_t* segments, int nseg,
                           float* norm_out, void* ws, size_t ws_bytes, void* stream);
+/* Gradient accumulation over the micro-batches of one optimizer step (the reference's 8 ranks x 12 clips run one after another on one GPU, each micro-batch
+ * under its own BatchNorm statistics; codes/core/dist_utils.py:61-67 sums the same per-rank gradients with an all-reduce): first != 0: acc[i] = g[i] (the
+ * accumulator is never cleared), first == 0: acc[i] = acc[i] + g[i], one fp32 add per element, i in [0, n).  No atomics and a grid that depends only on n and the
+ * operands' alignment: the result is bit-identical from run to run.  acc and g are flat fp32 device arrays that need only 4-byte alignment (views
+ * flat_*[off:] of the engine's buffers) and must not overlap; nothing outside [0, n) is read or written.  n == 0 succeeds without a launch; n < 0 or a NULL
+ * pointer with n > 0 is MVF_EINVAL.  The optimizer then runs on acc with grad_scale = 1 / (micro-batches * world). */
+int mvf_grad_accumulate(float* acc, const float* g, long n, int first, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * [r6] Launch-table replay.  One training step (the reference's batch_processor + DistOptimizerHook.after_train_iter, codes/core/train.py:45-60,

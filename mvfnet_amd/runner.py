@@ -281,6 +281,13 @@ def build_dataloader(dataset, videos_per_gpu, workers_per_gpu=0, dist_mode=False
 
 
 # ------------------------------------------------------------------------------------------------ runner
+def check_accumulate(k):
+    """optimizer_config.accumulate / Runner(accumulate=): micro-batches per optimizer step, an integer >= 1."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+        raise ValueError("accumulate must be an integer >= 1 (micro-batches per optimizer step), got %r" % (k,))
+    return int(k)
+
+
 class Runner(object):
     """Epoch/iteration loop with the reference's hook order: lr update -> forward -> backward -> all-reduce/world ->
     clip -> step -> checkpoint every `ckpt_interval` epochs.  Uses the fused HIP TrainEngine (one flat all-reduce +
@@ -288,8 +295,11 @@ class Runner(object):
 
     def __init__(self, model, work_dir=None, lr=0.015, momentum=0.9, weight_decay=1e-4, max_norm=40.0, lr_steps=(90, 130),
                  warmup_iters=25070, warmup_ratio=0.01, ckpt_interval=10, log_interval=20, logger=print, optimizer=None, dtype=None,
-                 warmup="linear", lr_gamma=0.1):
+                 warmup="linear", lr_gamma=0.1, accumulate=1):
+        """accumulate = k > 1: gradient accumulation -- k loader batches (micro-batches, each under its own BatchNorm statistics) per optimizer step, the
+        reference's 8 x 12-clip recipe on one GPU with videos_per_gpu=12, accumulate=8.  `iter`, the warm-up and the log interval then count OPTIMIZER steps."""
         self.model, self.work_dir = model, work_dir
+        self.accumulate = check_accumulate(accumulate)
         if optimizer is not None:                    # build_optimizer's object: hyper-parameters and param-wise options live there
             self.engine = optimizer.engine
             g = optimizer.param_groups[0]
@@ -315,9 +325,33 @@ class Runner(object):
     def current_lr(self):
         return step_lr(self.base_lr, self.epoch, self.iter, self.lr_steps, self.lr_gamma, self.warmup, self.warmup_iters, self.warmup_ratio)
 
+    def _apply_accumulated(self, rank):
+        lr = self.current_lr()
+        self.engine.apply_accumulated(lr=lr)
+        self.iter += 1
+        if rank == 0 and self.log_interval and self.iter % self.log_interval == 0:
+            self.log("Epoch [%d] iter %d lr %.5f loss_cls %.4f grad_norm %.3f" % (
+                self.epoch + 1, self.iter, lr, float(self.engine.accumulated_loss), float(self.engine.norm_out[0])))
+
+    def _train_epoch_accumulated(self, loader, rank):
+        """One micro-step per loader batch; the optimizer runs after every k-th batch and after the epoch's last one (a shorter trailing group is applied
+        with its real count: nothing is dropped and nothing carries over the epoch boundary, so a checkpoint never sees a partial group)."""
+        pending = 0
+        for data in loader:
+            self.engine.accumulate_step(data["img_group"], data["label"])
+            pending += 1
+            if pending == self.accumulate:
+                self._apply_accumulated(rank)
+                pending = 0
+        if pending:
+            self._apply_accumulated(rank)
+
     def train_epoch(self, loader):
         self.model.train()
         rank, _ = get_dist_info()
+        if self.accumulate > 1:
+            self._train_epoch_accumulated(loader, rank)
+            loader = ()
         for data in loader:
             lr = self.current_lr()
             loss = self.engine.train_step(data["img_group"], data["label"], lr=lr)
@@ -386,10 +420,12 @@ def train_network(model, dataset, cfg, distributed=False, validate=False, logger
     """reference train.py:63-76 + _dist_train / _non_dist_train :159-252: loaders, model on the GPU (parameters broadcast from
     rank 0 when distributed), optimizer from cfg.optimizer, grad clip from cfg.optimizer_config, lr schedule from cfg.lr_config,
     checkpoints from cfg.checkpoint_config, logging interval from cfg.log_config, optional fp16 section, resume_from /
-    load_from, then run cfg.total_epochs.  `dataset`: a torch Dataset of dict(img_group, label) items, a ready loader, or an
+    load_from, then run cfg.total_epochs.  cfg.optimizer_config.accumulate = k (an integer >= 1, default 1) makes one optimizer step of k loader batches
+    (gradient accumulation, Runner(accumulate=k)).  `dataset`: a torch Dataset of dict(img_group, label) items, a ready loader, or an
     iterable of batches (or a list whose first entry is the training one).  `validate` registers the reference's
     DistEvalTopKAccuracyHook(cfg.data.val, interval=cfg.eval_interval, k=(1, 5)) for a Dataset OBJECT under cfg.data.val."""
     cfg = as_config(cfg)
+    accumulate = check_accumulate(_cfg_get(cfg.get("optimizer_config") or {}, "accumulate", 1))      # (refused before anything is built)
     log = (logger.info if logger is not None and hasattr(logger, "info") else (logger or print))
     is_list_of_sets = isinstance(dataset, (list, tuple)) and dataset and not isinstance(dataset[0], dict)     # (a list of dicts = ready batches)
     datasets = dataset if is_list_of_sets else [dataset]
@@ -415,7 +451,7 @@ def train_network(model, dataset, cfg, distributed=False, validate=False, logger
                     lr_steps=[steps] if isinstance(steps, int) else tuple(steps), warmup=_cfg_get(lrc, "warmup"),
                     warmup_iters=_cfg_get(lrc, "warmup_iters", 0), warmup_ratio=_cfg_get(lrc, "warmup_ratio", 0.1),
                     lr_gamma=_cfg_get(lrc, "gamma", 0.1), ckpt_interval=_cfg_get(ck, "interval", 0) or 0,
-                    log_interval=_cfg_get(lg, "interval", 0) or 0, logger=log, optimizer=optimizer)
+                    log_interval=_cfg_get(lg, "interval", 0) or 0, logger=log, optimizer=optimizer, accumulate=accumulate)
     if clip and _cfg_get(clip, "norm_type", 2) != 2:
         raise NotImplementedError("grad_clip norm_type %r: the fused clip is the L2 norm" % _cfg_get(clip, "norm_type"))
     if validate:

@@ -1308,6 +1308,11 @@ class _ParamStore(object):
 
     def apply_sgd(self, lr=None, world=1):
         """clip_grad_norm_(max_norm) + SGD on the flat buffers (gradient scaled by 1 / world): one fused launch sequence."""
+        return self._apply_sgd(self.flat_grads, 1.0 / world, lr)
+
+    def _apply_sgd(self, grads, grad_scale, lr=None):
+        """The optimizer's launch sequence on `grads` (a flat fp32 tensor laid out like flat_grads: flat_grads itself, or the accumulator of
+        TrainEngine.apply_accumulated) scaled by grad_scale."""
         if not self.rehomed:
             raise RuntimeError("apply_sgd: this store does not own its parameters (stand-alone Bottleneck.forward); use the model's train engine or a torch optimizer")
         off = self.trainable_offset()
@@ -1315,7 +1320,7 @@ class _ParamStore(object):
         if n <= 0:
             return None
         ws = self.workspace(lib.mvf_sgd_workspace_bytes(n))
-        args = (_p(self.flat_params[off:]), _p(self.flat_grads[off:]), _p(self.flat_mom[off:]), n, C.c_float(1.0 / world),
+        args = (_p(self.flat_params[off:]), _p(grads[off:]), _p(self.flat_mom[off:]), n, C.c_float(grad_scale),
                 C.c_float(self.max_norm or 0.0), C.c_float(self.lr if lr is None else lr), C.c_float(self.momentum),
                 C.c_float(self.weight_decay), int(self.steps == 0))
         if self.nesterov and not self.param_options and not self._scattered_frozen:
@@ -1460,6 +1465,7 @@ class TrainEngine(_ParamStore):
         # input_window = per-frame (y0, x0, flip) rows for the NEXT forward (None = top-left window, no flip)
         self.input_pipeline, self.input_window = None, None
         self._pack_tables = None
+        self.accumulated_count = 0      # micro-steps summed into flat_acc since the last apply_accumulated (accumulate_step)
 
     def _pack_all(self, kind):
         """All forward (kind 0) or data-gradient (kind 1) weight packs in ONE launch (mvf_pack_conv_weights_batched); the job
@@ -1757,11 +1763,20 @@ class TrainEngine(_ParamStore):
         return loss, plan
 
     def train_step(self, imgs, labels, lr=None):
+        loss = self._forward_backward(imgs, labels, exchange=True)
+        self.step(lr)
+        return loss
+
+    def _forward_backward(self, imgs, labels, exchange):
+        """forward + backward of one step, replayed from a launch plan where one exists.  exchange=True is train_step.  exchange=False is a micro-step of
+        accumulate_step: without a process group the flag changes no launch, so it shares train_step's plans (same key, same recordings); WITH one, a plan
+        recorded by train_step carries the tail bucket's collective, which a micro-step must not issue -- those micro-steps run eagerly, never from a plan."""
         key = self._plan_key(imgs, labels) if imgs.is_cuda else None
+        if not exchange and self._ddp_active():
+            key = None
         if key is None:
             loss = self.forward(imgs, labels)
-            self.backward(exchange=True)
-            self.step(lr)
+            self.backward(exchange=exchange)
             return loss
         st = self.__dict__.setdefault("_plans", {}).setdefault(key, dict(eager=0, tries=0, cand=None, plan=None))
         prepared = self._step_tensors(imgs, labels)
@@ -1788,5 +1803,74 @@ class TrainEngine(_ParamStore):
                 st["plan"], st["cand"] = cand, None          # two consecutive steps made the same calls with the same arguments
             else:
                 st["cand"] = cand
-        self.step(lr)
         return loss
+
+    # ---- gradient accumulation: one optimizer step over k micro-batches (the reference's 8 ranks x 12 clips run one after another on one GPU) ------------
+    # Micro-batch i's forward + backward leave g_i in flat_grads (the gradient of ITS mean loss under ITS OWN BatchNorm batch statistics: exactly what rank i of
+    # the reference computes, per-GPU BatchNorm, no SyncBN); mvf_grad_accumulate keeps acc = g_1, acc += g_i in arrival order (fp32, bit-identical from run to
+    # run); at the boundary the optimizer runs on acc with grad_scale = 1 / (k * world), so clip_grad_norm_ sees the mean gradient as DistOptimizerHook's does
+    # (codes/core/dist_utils.py:61-67).  BatchNorm running statistics and num_batches_tracked advance once per MICRO-step, as on every rank of the reference:
+    # after one optimizer step they have taken k momentum updates (what a rank-0 checkpoint of the reference, which holds rank 0's statistics only, would not
+    # show; the standard meaning of accumulation).  Dropout draws a fresh mask per micro-step.  An engine that never calls these methods allocates and launches
+    # nothing more than before.
+    flat_acc = None               # (accumulated_count, the micro-steps in the accumulator, is an instance attribute: public scalar CLASS attributes are plan-key switches)
+    _acc_loss_sum = None
+    _acc_loss_mean = None
+
+    def acc_grad_of(self, p):
+        """The accumulator's view for a parameter (beside grad_of); valid after the first accumulate_step."""
+        v = self._grad_view[id(p)]
+        first = v.storage_offset()
+        return self.flat_acc[first:first + v.numel()].view(v.shape)
+
+    @property
+    def accumulated_loss(self):
+        """Device tensor (1,): the mean of the micro-batch losses of the group being accumulated, or, when none is pending, of the group applied last."""
+        if self.accumulated_count:
+            return self._acc_loss_sum / float(self.accumulated_count)
+        return self._acc_loss_mean
+
+    def accumulate_step(self, imgs, labels):
+        """One micro-step: forward + backward without any gradient exchange, then flat_acc (=|+=) flat_grads on the launch stream.  Returns the micro-batch's loss."""
+        loss = self._forward_backward(imgs, labels, exchange=False)
+        if self.flat_acc is None:
+            # a new allocation, not a replacement, and the accumulate launch stays outside the launch plans: no recorded plan holds its address
+            self.flat_acc = torch.empty_like(self.flat_grads)
+            self._acc_loss_sum = torch.zeros(1, device=self.device, dtype=torch.float32)
+        first = self.accumulated_count == 0
+        # backward ended with join_side(): the launch stream is ordered behind the side stream's weight gradients
+        with _on_stream(torch.cuda.current_stream(), main=True):
+            check(lib.mvf_grad_accumulate(_p(self.flat_acc), _p(self.flat_grads), self.flat_grads.numel(), int(first), _st()), "grad accumulate")
+        if first:
+            torch.mul(loss, 1.0, out=self._acc_loss_sum)      # (an elementwise launch on this stream: copy_ would be a blit on another queue)
+        else:
+            self._acc_loss_sum += loss
+        self.accumulated_count += 1
+        return loss
+
+    def apply_accumulated(self, lr=None):
+        """The step boundary: all-reduce of the accumulator (one collective, only when a process group is active), then clip + SGD on it with
+        grad_scale = 1 / (accumulated_count * world).  A trailing group shorter than k is applied with its real count.  Returns norm_out."""
+        count = self.accumulated_count
+        if count == 0:
+            raise RuntimeError("apply_accumulated: nothing has been accumulated since the last optimizer step")
+        with _on_stream(torch.cuda.current_stream(), main=True):
+            world = 1
+            if self._ddp_active():
+                import torch.distributed as dist
+                dist.all_reduce(self.flat_acc)
+                world = dist.get_world_size()
+            if self._apply_sgd(self.flat_acc, 1.0 / (count * world), lr) is not None:
+                for m_ in (self.model.backbone, self.model.cls_head):
+                    if hasattr(m_, "invalidate_engine"):
+                        m_.invalidate_engine()
+        self._acc_loss_mean = self._acc_loss_sum / float(count)
+        self.accumulated_count = 0
+        return self.norm_out
+
+    def train_step_accumulated(self, batches, lr=None):
+        """One optimizer step over an iterable of (imgs, labels) micro-batches; returns the mean of their losses (device tensor)."""
+        for imgs, labels in batches:
+            self.accumulate_step(imgs, labels)
+        self.apply_accumulated(lr)
+        return self.accumulated_loss
