@@ -91,3 +91,28 @@ def test_plan_run_generic_call_marshals_integers_and_floats_in_order():
     ops[0].n_int = 41
     assert _lib.lib.mvf_plan_run(ops, 1, words, floats, C.byref(failed)) == -1 and failed.value == 0          # MVF_EINVAL
     assert b"bad call record" in _lib.lib.mvf_last_error()
+
+
+def test_head_and_optimizer_argument_failures_return_before_any_launch():
+    """The head's and the optimizer's entry points check their arguments before the first launch (csrc/train_ops.hip, csrc/net_ops.hip): the codes come back on
+    a machine without a GPU, from host addresses that are never read."""
+    import ctypes as C
+    from mvfnet_amd import _lib
+    lib = _lib.lib
+    host = (C.c_float * 64)()
+    a = C.cast(host, C.c_void_p)
+    EINVAL, ESHAPE, EWS = -1, -2, -3
+    ws_bytes = lib.mvf_sgd_workspace_bytes(1)
+    assert ws_bytes > 4
+    assert lib.mvf_sgd_nesterov_step(a, a, a, 0, 1.0, 40.0, 0.015, 0.9, 1e-4, 1, a, a, ws_bytes, None) == EINVAL
+    assert b"sgd_nesterov_step" in lib.mvf_last_error()
+    assert lib.mvf_sgd_nesterov_step(a, a, a, 1, 1.0, 40.0, 0.015, 0.9, 1e-4, 1, a, a, ws_bytes - 1, None) == EWS
+    assert b"workspace too small" in lib.mvf_last_error()
+    assert lib.mvf_sgd_nesterov_step(a, a, a, 1, 1.0, 40.0, 0.015, 0.9, 1e-4, 1, a, None, ws_bytes, None) == EWS
+    assert lib.mvf_sgd_step_segments(a, a, a, 1, 1.0, 40.0, 0.015, 0.9, 1e-4, 1, 1, a, 0, a, a, ws_bytes, None) == EINVAL
+    assert b"sgd_step_segments" in lib.mvf_last_error()
+    assert lib.mvf_sgd_step_segments(a, a, a, 1, 1.0, 40.0, 0.015, 0.9, 1e-4, 1, 1, a, 1, a, a, ws_bytes - 1, None) == EWS
+    assert lib.mvf_head_train_bwd(a, a, a, None, 1, 1, 1, 6, 1, a, a, a, a, 0, None) == ESHAPE
+    assert b"multiple of 4" in lib.mvf_last_error()
+    assert lib.mvf_head_pool_fc(a, 1, 1, 1, 6, a, a, 1, a, a, 0, None) == ESHAPE
+    assert b"multiple of 4" in lib.mvf_last_error()
