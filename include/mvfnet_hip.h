@@ -472,6 +472,29 @@ int mvf_ce_loss(const float* scores, const long long* labels, int clips, int cla
 int mvf_head_train_bwd(const float* dscores, const float* pooled, const float* fc_w, const float* drop_mask, int clips, int t,
                        int hw, int c, int classes, float* dfc_w, float* dfc_b, float* dpool_ws /* clips*c */, void* dfeat, int dtype,
                        void* stream);
+/* Batch blending (mmaction's MixupBlending / CutmixBlending) and soft labels.  One table per step, two DEVICE arrays:
+ *   rows int32 (clips, 5): partner, y0, x0, y1, x1 -- a half-open box in image pixels (before the pad); 0 <= y0 <= y1 <= H, 0 <= x0 <= x1 <= W,
+ *                          0 <= partner < clips
+ *   wts  fp32  (clips, 2): lam_px = weight of the clip's own pixel outside the box, lam_lab = weight of the clip's own label, both in [0, 1]
+ * Mixup: empty box, lam_px = lam_lab = lambda.  CutMix: lam_px = 1, a box, lam_lab = 1 - box_area / (H * W).
+ *
+ * mvf_stem_blend: xp / out = the stem operand (clips * t, hp, wp, 4) in `dtype` as mvf_stem_prep lays it out.  For clip i, each frame f and each element, with
+ * a = xp[i, f], b = xp[partner, f]: inside the box (shifted by pad) out = b, a copy; elsewhere out = a, a copy, when lam_px == 1 or partner == i, otherwise
+ * lam_px * a + (1 - lam_px) * b in fp32 rounded once to `dtype`.  The zero border and fourth channel stay zero.  OUT OF PLACE: out == xp or overlapping
+ * ranges are MVF_EINVAL (clip i reads clip partner).  xp / out 16-byte aligned.  The kernel clamps partner, the box and lam_px into range: a bad table
+ * cannot read outside the tensor (rejecting bad tables is the caller's job: mvfnet_amd.blending.check_blend_rows). */
+int mvf_stem_blend(const void* xp, int clips, int t, int hp, int wp, int pad, const int* rows, const float* wts, void* out, int dtype, void* stream);
+/* targets[i][k] = (1 - eps) * (lam_lab_i * [k == labels[i]] + (1 - lam_lab_i) * [k == labels[partner_i]]) + eps / classes, fp32 (clips, classes); eps in
+ * [0, 1) = label smoothing.  eps == 0: the two entries are exactly lam_lab and 1.0f - lam_lab (their fp32 sum where both labels coincide).
+ * rows == NULL: smoothing only (lam_lab = 1). */
+int mvf_soft_targets(const long long* labels, const int* rows, const float* wts, int clips, int classes, float eps, float* targets, void* stream);
+/* mvf_ce_loss against soft targets (clips, classes), any non-negative fp32 matrix (not assumed to sum to 1): loss_part[i] = sum_k t_ik * (lse_i - s_ik) --
+ * exactly 0 for one class --, loss = their mean, dscores = (softmax_ik * sum_k t_ik - t_ik) / clips or NULL. */
+int mvf_ce_loss_soft(const float* scores, const float* targets, int clips, int classes, float* dscores, float* loss_part, float* loss, void* stream);
+/* mvf_head_train_fwd with soft targets (clips, classes) in place of the integer labels: the same pool and fc launches, then the loss of mvf_ce_loss_soft. */
+int mvf_head_train_fwd_soft(const void* feat, int clips, int t, int hw, int c, const float* fc_w, const float* fc_b, int classes,
+                            const float* targets, const float* drop_mask /* (clips*t, c) pre-scaled keep mask or NULL */,
+                            float* pooled, float* scores, float* dscores, float* loss_part, float* loss, int dtype, void* stream);
 /* conv weight gradient dw_oihw (cout, cin_real, kh, kw_real) fp32; d describes the FORWARD conv (x dims, ho/wo = dz dims).
  * kw_packed*cin_packed == d->kw*d->cin; they differ from (kw_real, cin_real) only for the stem view (8x4 vs 7x3).
  * fp32 accumulation over the pixels in a fixed order (per-split partial tiles, then a split-lane reduce): deterministic, no atomics.  fp32

@@ -204,6 +204,14 @@ def _load():
     lib.mvf_wgrad_slab_reduce.argtypes = [fp, i32, i32, i32, fp, vp]
     lib.mvf_ce_loss.restype = i32
     lib.mvf_ce_loss.argtypes = [fp, ll, i32, i32, fp, fp, fp, vp]
+    lib.mvf_stem_blend.restype = i32
+    lib.mvf_stem_blend.argtypes = [vp, i32, i32, i32, i32, i32, vp, fp, vp, i32, vp]
+    lib.mvf_soft_targets.restype = i32
+    lib.mvf_soft_targets.argtypes = [ll, vp, fp, i32, i32, f32, fp, vp]
+    lib.mvf_ce_loss_soft.restype = i32
+    lib.mvf_ce_loss_soft.argtypes = [fp, fp, i32, i32, fp, fp, fp, vp]
+    lib.mvf_head_train_fwd_soft.restype = i32
+    lib.mvf_head_train_fwd_soft.argtypes = [vp, i32, i32, i32, i32, fp, fp, i32, fp, fp, fp, fp, fp, fp, fp, i32, vp]
     lib.mvf_head_train_bwd.restype = i32
     lib.mvf_head_train_bwd.argtypes = [fp, fp, fp, fp, i32, i32, i32, i32, i32, fp, fp, fp, vp, i32, vp]
     lib.mvf_conv2d_wgrad_workspace_bytes.restype = sz

@@ -1213,6 +1213,50 @@ __global__ void ce_loss_kernel(const float* scores, const long long* labels, int
     }
 }
 
+// the same against a row of soft targets t (any non-negative fp32 row, not assumed to sum to 1: blended and / or smoothed labels, mvf_soft_targets):
+// loss = sum_k t_k * (lse - s_k) -- exactly 0 for one class --, dscores = (softmax * sum_k t_k - t) / clips.  Fixed-order block reductions: deterministic.
+__global__ void ce_loss_soft_kernel(const float* scores, const float* targets, int clips, int classes, float* loss_part, float* dscores) {
+    __shared__ float red[256];
+    const int cl = blockIdx.x, tid = threadIdx.x;
+    const float* s = scores + (long)cl * classes;
+    const float* tg = targets + (long)cl * classes;
+    float mx = -INFINITY;
+    for (int k = tid; k < classes; k += blockDim.x) mx = fmaxf(mx, s[k]);
+    red[tid] = mx;
+    __syncthreads();
+    for (int o = blockDim.x >> 1; o > 0; o >>= 1) { if (tid < o) red[tid] = fmaxf(red[tid], red[tid + o]); __syncthreads(); }
+    mx = red[0];
+    __syncthreads();
+    float e = 0.f;
+    for (int k = tid; k < classes; k += blockDim.x) e += expf(s[k] - mx);
+    red[tid] = e;
+    __syncthreads();
+    for (int o = blockDim.x >> 1; o > 0; o >>= 1) { if (tid < o) red[tid] += red[tid + o]; __syncthreads(); }
+    const float den = red[0];
+    __syncthreads();
+    const float lse = logf(den) + mx;
+    float acc = 0.f, tsum = 0.f;
+    for (int k = tid; k < classes; k += blockDim.x) {
+        const float tk = tg[k];
+        acc += tk * (lse - s[k]);
+        tsum += tk;
+    }
+    red[tid] = acc;
+    __syncthreads();
+    for (int o = blockDim.x >> 1; o > 0; o >>= 1) { if (tid < o) red[tid] += red[tid + o]; __syncthreads(); }
+    if (tid == 0) loss_part[cl] = red[0];
+    if (!dscores) return;
+    __syncthreads();
+    red[tid] = tsum;
+    __syncthreads();
+    for (int o = blockDim.x >> 1; o > 0; o >>= 1) { if (tid < o) red[tid] += red[tid + o]; __syncthreads(); }
+    tsum = red[0];
+    for (int k = tid; k < classes; k += blockDim.x) {
+        const float p = expf(s[k] - mx) / den;
+        dscores[(long)cl * classes + k] = (p * tsum - tg[k]) / (float)clips;
+    }
+}
+
 __global__ void mean_reduce_kernel(const float* v, int n, float* out) {
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         double s = 0.0;
@@ -1914,6 +1958,42 @@ int mvf_ce_loss(const float* scores, const long long* labels, int clips, int cla
     MVF_REQUIRE(scores && labels && loss_part && loss && clips > 0 && classes > 0, MVF_EINVAL, "ce_loss: bad argument");
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(ce_loss_kernel, dim3(clips), dim3(256), 0, st, scores, labels, clips, classes, loss_part, dscores);
+    MVF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(mean_reduce_kernel, dim3(1), dim3(64), 0, st, loss_part, clips, loss);
+    MVF_LAUNCH_CHECK();
+    return MVF_OK;
+}
+
+// mvf_head_train_fwd against soft targets (clips, classes) instead of integer labels: the same frame_pool_kernel and head_fc_seg_kernel launches, then the
+// soft-target loss.  Every by-value argument is checked before the first launch.
+int mvf_head_train_fwd_soft(const void* feat, int clips, int t, int hw, int c, const float* fc_w, const float* fc_b, int classes,
+                            const float* targets, const float* drop_mask, float* pooled, float* scores, float* dscores, float* loss_part, float* loss,
+                            int dtype, void* stream) {
+    MVF_REQUIRE(clips > 0 && t > 0 && hw > 0 && c > 0 && classes > 0, MVF_EINVAL, "head_train_fwd_soft: bad argument (clips=%d t=%d hw=%d c=%d classes=%d)",
+                clips, t, hw, c, classes);
+    MVF_REQUIRE(dtype == MVF_F32 || dtype == MVF_BF16, MVF_EINVAL, "head_train_fwd_soft: dtype %d", dtype);
+    MVF_REQUIRE((size_t)c * sizeof(float) <= 160 * 1024, MVF_EUNSUPPORTED, "head_train_fwd_soft: c=%d does not fit the LDS feature buffer", c);
+    MVF_REQUIRE((long)clips * t <= 65535, MVF_ESHAPE, "head_train_fwd_soft: %d x %d frames exceed the grid", clips, t);
+    MVF_REQUIRE(feat && fc_w && targets && pooled && scores && dscores && loss_part && loss, MVF_EINVAL, "head_train_fwd_soft: NULL argument");
+    hipStream_t st = (hipStream_t)stream;
+    dim3 g((c + 255) / 256, clips * t);
+    if (dtype == MVF_F32) hipLaunchKernelGGL(frame_pool_kernel<float>, g, dim3(256), 0, st, (const float*)feat, hw, c, drop_mask, pooled);
+    else hipLaunchKernelGGL(frame_pool_kernel<bf16_t>, g, dim3(256), 0, st, (const bf16_t*)feat, hw, c, drop_mask, pooled);
+    MVF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(head_fc_seg_kernel, dim3(clips, kHeadSplit), dim3(256), (size_t)c * sizeof(float), st, pooled, fc_w, fc_b, clips, t, c, classes, scores);
+    MVF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ce_loss_soft_kernel, dim3(clips), dim3(256), 0, st, scores, targets, clips, classes, loss_part, dscores);
+    MVF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(mean_reduce_kernel, dim3(1), dim3(64), 0, st, loss_part, clips, loss);
+    MVF_LAUNCH_CHECK();
+    return MVF_OK;
+}
+
+int mvf_ce_loss_soft(const float* scores, const float* targets, int clips, int classes, float* dscores, float* loss_part, float* loss, void* stream) {
+    MVF_REQUIRE(clips > 0 && classes > 0, MVF_EINVAL, "ce_loss_soft: bad argument (clips=%d classes=%d)", clips, classes);
+    MVF_REQUIRE(scores && targets && loss_part && loss, MVF_EINVAL, "ce_loss_soft: NULL argument");
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(ce_loss_soft_kernel, dim3(clips), dim3(256), 0, st, scores, targets, clips, classes, loss_part, dscores);
     MVF_LAUNCH_CHECK();
     hipLaunchKernelGGL(mean_reduce_kernel, dim3(1), dim3(64), 0, st, loss_part, clips, loss);
     MVF_LAUNCH_CHECK();

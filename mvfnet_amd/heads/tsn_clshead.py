@@ -12,6 +12,8 @@ SURVEY.md 2.2 measured 1e-5), which is how the HIP head kernel computes them in 
 extract_feat=True (the reference's feature_extractor.py entry point; tsn_clshead.py:89-90, :110-112): eval-mode forward returns that mean
 itself, (clips, in_channels) fp32, for both branches; in training mode it is refused.
 """
+import numbers
+
 import torch
 import torch.nn as nn
 
@@ -22,8 +24,11 @@ from ..builder import HEADS
 class TSNClsHead(nn.Module):
     def __init__(self, spatial_type="avg", spatial_size=7, consensus_cfg=dict(type="avg", dim=1), with_avg_pool=False,
                  temporal_feature_size=1, spatial_feature_size=1, dropout_ratio=0.8, in_channels=1024, num_classes=101,
-                 init_std=0.001, fcn_testing=False, extract_feat=False):
+                 init_std=0.001, fcn_testing=False, extract_feat=False, label_smooth_eps=0.0):
         super().__init__()
+        if isinstance(label_smooth_eps, bool) or not isinstance(label_smooth_eps, numbers.Real) or not 0.0 <= label_smooth_eps < 1.0:
+            raise ValueError("TSNClsHead: label_smooth_eps must lie in [0, 1) (got %r)" % (label_smooth_eps,))
+        self.label_smooth_eps = float(label_smooth_eps)
         if spatial_type != "avg" or consensus_cfg.get("type") != "avg" or consensus_cfg.get("dim", 1) != 1:
             raise NotImplementedError("TSNClsHead: only spatial_type='avg' with the 'avg' consensus over dim 1 is built "
                                       "(the MVFNet configuration)")
@@ -83,12 +88,33 @@ class TSNClsHead(nn.Module):
     def loss(self, cls_score, labels):
         """reference heads/base.py:40-45: {'loss_cls': F.cross_entropy(cls_score, labels)} (mean over the clips), computed by the
         HIP cross-entropy kernel of the train head (mvf_ce_loss); no autograd through it -- Recognizer2D.forward_train is the
-        path that trains (scores, loss and their gradients in one fused head)."""
+        path that trains (scores, loss and their gradients in one fused head).
+        labels: integers (B,) / (B, 1), or a floating-point (B, num_classes) matrix of soft labels (mvf_ce_loss_soft).  In training mode integer labels are
+        smoothed with label_smooth_eps (mvf_soft_targets) as mmaction's head does."""
         import ctypes as C
         from .._lib import check, lib
         if not cls_score.is_cuda:
             raise RuntimeError("TSNClsHead.loss: mvfnet_amd runs on MI355X tensors only; no CPU fallback (tests use oracle/)")
         s = cls_score.detach().to(torch.float32).contiguous()
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        soft = labels.is_floating_point() and labels.dim() == 2 and tuple(labels.shape) == tuple(s.shape)
+        eps = self.label_smooth_eps if self.training else 0.0
+        if soft and eps > 0.0:
+            raise ValueError("TSNClsHead.loss: soft (B, num_classes) labels are taken as they are; label_smooth_eps needs integer labels")
+        if soft or eps > 0.0:
+            P = lambda t: C.c_void_p(t.data_ptr())
+            if soft:
+                tgt = labels.detach().to(device=s.device, dtype=torch.float32).contiguous()
+            else:
+                lab = labels.reshape(-1).to(device=s.device, dtype=torch.int64).contiguous()
+                if lab.numel() != s.shape[0]:
+                    raise ValueError("TSNClsHead.loss: %d labels for %d score rows" % (lab.numel(), s.shape[0]))
+                tgt = torch.empty_like(s)
+                check(lib.mvf_soft_targets(P(lab), None, None, s.shape[0], s.shape[1], C.c_float(eps), P(tgt), stream), "mvf_soft_targets")
+            part = torch.empty(s.shape[0], dtype=torch.float32, device=s.device)
+            out = torch.empty(1, dtype=torch.float32, device=s.device)
+            check(lib.mvf_ce_loss_soft(P(s), P(tgt), s.shape[0], s.shape[1], None, P(part), P(out), stream), "mvf_ce_loss_soft")
+            return dict(loss_cls=out.reshape(()))
         lab = labels.reshape(-1).to(device=s.device, dtype=torch.int64).contiguous()
         if lab.numel() != s.shape[0]:
             raise ValueError("TSNClsHead.loss: %d labels for %d score rows" % (lab.numel(), s.shape[0]))

@@ -56,6 +56,10 @@ class Recognizer2D(nn.Module):
         self.init_weights()
         self.fcn_testing, self.modality = fcn_testing, modality
         self.train_cfg, self.test_cfg = train_cfg, test_cfg
+        # train_cfg=dict(blending=dict(type='MixupBlending' | 'CutmixBlending', alpha=...)): batch blending on the device, in forward_train only
+        from ..blending import build_blending
+        blend_cfg = train_cfg.get("blending") if hasattr(train_cfg, "get") else getattr(train_cfg, "blending", None)
+        self.blending = build_blending(blend_cfg)
         self.module_cfg = dict(module_cfg) if module_cfg else module_cfg
         self.in_channels = 3
         if self.module_cfg:
@@ -121,12 +125,29 @@ class Recognizer2D(nn.Module):
         if getattr(self, "_train_engine", None) is None:
             from ..train_engine import TrainEngine
             self._train_engine = TrainEngine(self, **opt)
+            self._set_soft_options(self._train_engine, self.training)
         elif opt:                                  # an engine exists already: the options must not be dropped silently
             self._train_engine.set_options(**opt)
         return self._train_engine
 
+    def train(self, mode=True):
+        """The engine's blending / label smoothing follow the model's mode (engine.train_step users, e.g. the runner, never pass through forward_train)."""
+        super().train(mode)
+        if getattr(self, "_train_engine", None) is not None:
+            self._set_soft_options(self._train_engine, mode)
+        return self
+
+    def _set_soft_options(self, eng, training):
+        """The ONE place train_cfg['blending'] and the head's label_smooth_eps reach the engine: only while the model trains.  Called when the engine is
+        created, whenever the mode changes (train() / eval()) and by forward_train.  engine.blending / engine.label_smooth_eps are plain attributes:
+        whoever drives engine.train_step directly may also set them by hand, until the next of these calls."""
+        eng.blending = self.blending if training else None
+        eng.label_smooth_eps = float(getattr(self.cls_head, "label_smooth_eps", 0.0)) if training else 0.0
+
     def forward_train(self, imgs, labels, **kwargs):
         """imgs [B, T, 3, H, W], labels [B, 1] -> {'loss_cls': scalar tensor} (reference recognizer2d.py:132-149).
+        labels may also be a floating-point (B, num_classes) matrix of soft labels.  While self.training, train_cfg['blending'] (Mixup / CutMix) and the
+        head's label_smooth_eps are applied on the device (mvfnet_amd/blending.py).
         The returned loss supports .backward(): gradients land in the parameters' .grad (copies of the engine's flat gradient
         buffer; after engine.attach_grads() the .grad tensors ARE views of it), as the reference's DistOptimizerHook expects.
         A gather table (preprocess.gather_rows: a `src` column) is refused with a ValueError: training makes one image per frame.  An
@@ -151,6 +172,7 @@ class Recognizer2D(nn.Module):
         eng = self.train_engine()
         eng.trainable_offset()
         eng.input_pipeline, eng.input_window = getattr(self, "input_pipeline", None), kwargs.get("window")
+        self._set_soft_options(eng, self.training)
         eng.dropout = self.cls_head.dropout_ratio if (self.cls_head.dropout is not None and self.cls_head.training) else 0.0
         params = [p for p in self.parameters()]
         loss = _TrainStepFn.apply(eng, imgs, labels, *params)

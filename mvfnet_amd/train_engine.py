@@ -1466,6 +1466,10 @@ class TrainEngine(_ParamStore):
         self.input_pipeline, self.input_window = None, None
         self._pack_tables = None
         self.accumulated_count = 0      # micro-steps summed into flat_acc since the last apply_accumulated (accumulate_step)
+        # batch blending (blending.py: an object with draw(batch, h, w) -> (rows, wts); None = off) and label smoothing.  Both are part of the plan key
+        # (_plan_key); with None / 0.0 and integer labels the step issues exactly the launches it issued without them.
+        self.blending, self.label_smooth_eps = None, 0.0
+        self._blend_table = None
 
     def _pack_all(self, kind):
         """All forward (kind 0) or data-gradient (kind 1) weight packs in ONE launch (mvf_pack_conv_weights_batched); the job
@@ -1497,7 +1501,7 @@ class TrainEngine(_ParamStore):
     # ---- one step -----------------------------------------------------------------------------------------------
     def forward(self, imgs, labels, stages=None, _prepared=None):
         """imgs [B, T, 3, H, W] fp32 -- or decoded frames [B, T, Hs, Ws, 3] uint8 with `input_pipeline` set --, labels [B, 1] /
-        [B] int64 (GPU) -> loss tensor (1,), keeps activations."""
+        [B] int64 (GPU), or soft labels [B, num_classes] floating point -> loss tensor (1,), keeps activations."""
         if not imgs.is_cuda or imgs.dtype not in (torch.float32, torch.uint8):
             raise RuntimeError("TrainEngine.forward: float32 (or uint8 frames) GPU input required")
         self._main = torch.cuda.current_stream()
@@ -1508,7 +1512,22 @@ class TrainEngine(_ParamStore):
     def _step_tensors(self, imgs, labels):
         """The three tensors of a step that are made in Python: the flat int64 labels, the dropout mask over the pooled [frames, channels] features
         (nn.Dropout of the reference head, tsn_clshead.py: F.dropout of a ones tensor = the same draw, one launch) and the fresh loss tensor."""
-        lab = labels.reshape(-1).to(device=imgs.device, dtype=torch.int64).contiguous()
+        if self._soft_labels(imgs, labels):
+            if self.blending is not None or self.label_smooth_eps > 0.0:
+                raise ValueError("TrainEngine: soft (B, num_classes) labels are taken as they are; blending and label_smooth_eps need integer labels")
+            lab = labels.detach().to(device=imgs.device, dtype=torch.float32).contiguous()
+        else:
+            lab = labels.reshape(-1).to(device=imgs.device, dtype=torch.int64).contiguous()
+        self._blend_table = None
+        if self.blending is not None:
+            # The step's table, drawn and validated on the host, lives in a persistent device buffer filled HERE, outside the region a launch plan
+            # records: a replay skips torch calls made inside it and freezes every by-value argument, so lambda, partner and box never travel by value.
+            from .blending import check_blend_rows
+            b = imgs.shape[0]
+            h, w = self._input_hw(imgs)
+            rows, wts = self.blending.draw(b, h, w)
+            check_blend_rows(rows, wts, b, h, w)
+            self._blend_table = self._upload_blend_table(rows, wts, b)
         mask = None
         if self.dropout > 0.0:
             nt, cc = imgs.shape[0] * imgs.shape[1], self.fc_w.shape[1]
@@ -1521,6 +1540,49 @@ class TrainEngine(_ParamStore):
         # launch stream per step)
         loss = torch.empty(1, device=imgs.device, dtype=torch.float32)
         return lab, mask, loss
+
+    def _input_hw(self, imgs):
+        """(h, w) of the images the stem sees: the pipeline's crop for uint8 frames, the tensor's own for fp32 clips."""
+        if imgs.dtype == torch.uint8:
+            if self.input_pipeline is None:
+                raise RuntimeError("uint8 frames need engine.input_pipeline = preprocess.FramePipeline(...)")
+            h, w = self.input_pipeline.crop_hw
+        else:
+            h, w = imgs.shape[3:]
+        return int(h), int(w)
+
+    _BLEND_STAGES = 4       # pinned staging slots of the blending table: as many steps may be in flight before the host waits for the oldest copy
+
+    def _upload_blend_table(self, rows, wts, b):
+        """ONE non-blocking host-to-device copy of the step's table: [rows (b, 5) int32 | wts (b, 2) fp32] packed as 7 b 32-bit words, from a pinned staging
+        slot (a copy from pageable memory would make the host wait for everything queued on the stream, i.e. for the previous step, and lose the
+        launch-ahead the plans exist for).  A slot is reused only after the copy that read it has completed (its event).  Returns the two device views
+        blend_rows (b, 5) int32 and blend_wts (b, 2) fp32 of the persistent buffer."""
+        import numpy as np
+        table = self.buf("blend_table", (7 * b,), torch.int32)
+        ring = self.__dict__.setdefault("_blend_stages", {}).get(b)
+        if ring is None:
+            ring = self._blend_stages[b] = dict(next=0, used=set(), slots=[(torch.empty(7 * b, dtype=torch.int32).pin_memory(), torch.cuda.Event())
+                                                                          for _ in range(self._BLEND_STAGES)])
+        k = ring["next"]
+        ring["next"] = (k + 1) % self._BLEND_STAGES
+        host, ev = ring["slots"][k]
+        if k in ring["used"]:
+            ev.synchronize()
+        hn = host.numpy()
+        hn[:5 * b] = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+        hn[5 * b:] = np.ascontiguousarray(wts, dtype=np.float32).reshape(-1).view(np.int32)
+        table.copy_(host, non_blocking=True)
+        ev.record()
+        ring["used"].add(k)
+        return table[:5 * b].view(b, 5), table[5 * b:].view(torch.float32).view(b, 2)
+
+    def _soft_labels(self, imgs, labels):
+        """The caller hands the (B, num_classes) soft-label matrix itself (floating point) instead of integer labels."""
+        return labels.is_floating_point() and labels.dim() == 2 and tuple(labels.shape) == (imgs.shape[0], self.num_classes)
+
+    def _uses_soft_head(self, lab):
+        return self.blending is not None or self.label_smooth_eps > 0.0 or lab.is_floating_point()
 
     def set_options(self, lr=None, momentum=None, weight_decay=None, max_norm=None, dtype=None):
         """Update the optimizer hyper-parameters of an existing engine (Recognizer2D.train_engine(**opt) on a model that already
@@ -1535,15 +1597,13 @@ class TrainEngine(_ParamStore):
         b, t = imgs.shape[0], imgs.shape[1]
         lab, mask, loss = prepared if prepared is not None else self._step_tensors(imgs, labels)
         u8 = imgs.dtype == torch.uint8               # decoded (B, T, Hs, Ws, 3) frames: crop/flip/normalise fused into the stem prep
+        h, w = self._input_hw(imgs)
         if u8:
-            if self.input_pipeline is None:
-                raise RuntimeError("uint8 frames need engine.input_pipeline = preprocess.FramePipeline(...)")
             x = None
             nt = b * t
-            h, w = self.input_pipeline.crop_hw
         else:
             x = imgs.reshape((-1, 3) + tuple(imgs.shape[3:])).contiguous()
-            nt, _, h, w = x.shape
+            nt = x.shape[0]
         self._pack_all(0)                                  # every forward weight pack, one launch
         # the data-gradient packs are not needed before backward: off the critical path, on the side stream
         side = self.side_stream()
@@ -1558,6 +1618,12 @@ class TrainEngine(_ParamStore):
             self.input_pipeline.to_stem(imgs, self.input_window, 3, wp, self.tdtype, out=xp)
         else:
             check(lib.mvf_stem_prep(_p(x), nt, 3, h, w, 3, wp, _p(xp), self.dt, _st()), "stem_prep")
+        if self.blending is not None:
+            # out of place (clip i reads its partner clip); xp_blend is what the stem reads AND what backward's stem weight gradient sees (saved['xp'])
+            rows_d, wts_d = self._blend_table
+            xb = self.buf("xp_blend", (nt, hp, wp, 4))
+            check(lib.mvf_stem_blend(_p(xp), b, t, hp, wp, 3, _p(rows_d), _p(wts_d), _p(xb), self.dt, _st()), "stem_blend")
+            xp = xb
         ho, wo = (h + 6 - 7) // 2 + 1, (w + 6 - 7) // 2 + 1
         z0, _, _ = self.stem.forward(xp, nt, hp, wp, ho=ho, wo=wo, bn=self.stem_bn)
         h2, w2 = (ho - 1) // 2 + 1, (wo - 1) // 2 + 1
@@ -1583,8 +1649,20 @@ class TrainEngine(_ParamStore):
         scores = self.buf("scores", (b, self.num_classes), f32)
         dscores = self.buf("dscores", (b, self.num_classes), f32)
         loss_part = self.buf("loss_part", (b,), f32)
-        check(lib.mvf_head_train_fwd(_p(xcur), b, t, hc * wc, cc, _p(self.fc_w), _p(self.fc_b), self.num_classes, _p(lab), _p(mask), _p(pooled),
-                                     _p(scores), _p(dscores), _p(loss_part), _p(loss), self.dt, _st()), "head fwd")
+        if self._uses_soft_head(lab):
+            if lab.is_floating_point():
+                targets = lab                            # the caller's soft labels: their address is the plan's `labels` slot
+            else:
+                # a library call, not torch scatter ops: a replayed plan skips torch calls made inside the recorded region
+                rows_d, wts_d = self._blend_table if self.blending is not None else (None, None)
+                targets = self.buf("soft_targets", (b, self.num_classes), f32)
+                check(lib.mvf_soft_targets(_p(lab), _p(rows_d), _p(wts_d), b, self.num_classes, C.c_float(self.label_smooth_eps), _p(targets), _st()),
+                      "soft_targets")
+            check(lib.mvf_head_train_fwd_soft(_p(xcur), b, t, hc * wc, cc, _p(self.fc_w), _p(self.fc_b), self.num_classes, _p(targets), _p(mask), _p(pooled),
+                                              _p(scores), _p(dscores), _p(loss_part), _p(loss), self.dt, _st()), "head fwd (soft targets)")
+        else:
+            check(lib.mvf_head_train_fwd(_p(xcur), b, t, hc * wc, cc, _p(self.fc_w), _p(self.fc_b), self.num_classes, _p(lab), _p(mask), _p(pooled),
+                                         _p(scores), _p(dscores), _p(loss_part), _p(loss), self.dt, _st()), "head fwd")
         self.saved.update(pooled=pooled, dscores=dscores, mask=mask, hw=hc * wc, c=cc, feat_shape=xcur.shape, scores=scores)
         if self._nbt_touched:
             self._count_batches()
@@ -1736,7 +1814,9 @@ class TrainEngine(_ParamStore):
             sw = self._switch_names = sorted(k for c_ in type(self).__mro__ for k, v in vars(c_).items()
                                              if not k.startswith("_") and isinstance(v, (bool, int, float, str)) and k not in ("lr", "momentum", "weight_decay", "max_norm"))
         return (tuple(imgs.shape), tuple(labels.shape), labels.dtype, str(imgs.device), torch.cuda.current_stream().cuda_stream, self._ddp_active(),
-                self.dropout > 0.0, tuple(p.requires_grad for p in self.model.parameters()), tuple(getattr(self, k) for k in sw))
+                self.dropout > 0.0, tuple(p.requires_grad for p in self.model.parameters()), tuple(getattr(self, k) for k in sw),
+                # a plan recorded without blending / smoothing / soft labels is never replayed with them (other launches, and eps is a frozen float word)
+                self.blending is not None, float(self.label_smooth_eps), self._soft_labels(imgs, labels))
 
     def _record_step(self, imgs, labels, prepared):
         """One eager step with every library call and stream ordering recorded; returns (loss, Plan | None)."""
