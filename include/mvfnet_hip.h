@@ -580,6 +580,28 @@ int mvf_sgd_step_segments(float* params, const float* grads, float* momentum_buf
  * flat_*[off:] of the engine's buffers) and must not overlap; nothing outside [0, n) is read or written.  n == 0 succeeds without a launch; n < 0 or a NULL
  * pointer with n > 0 is MVF_EINVAL.  The optimizer then runs on acc with grad_scale = 1 / (micro-batches * world). */
 int mvf_grad_accumulate(float* acc, const float* g, long n, int first, void* stream);
+/* Exponential moving average of the parameters (the weights the fine-tuning recipes evaluate and ship), kept on a flat fp32 buffer laid out like params.
+ * One update, every element, every entry point below:  ema' = fmaf(m, p' - ema, ema)  in fp32, with p' the parameter value this optimizer step stores -- and
+ * ema' = p' itself at m = 1 (the mean of one iterate; the two roundings of the formula can miss p' by an ulp there).  ema == p' is an exact fixed point for
+ * every m (a -0 comes back as +0), and the rounding of 1 - m never enters.  The update rounds to nothing once m |p' - ema| < ulp(ema) / 2.
+ *
+ * mvf_sgd_nesterov_step_ema / mvf_sgd_step_segments_ema: the arguments of their plain twins with `float* ema, float ema_momentum` inserted directly in front
+ * of norm_out.  params, momentum_buf and norm_out come out bit-identical to the plain entry points (same kernels, same grids, the update compiled in), ema
+ * bit-identical to the plain step followed by mvf_ema_update.  In the segment form an excluded segment (lr_mult < 0) leaves ema untouched as well.  ema is n
+ * floats, 4-byte aligned, and overlaps none of params / grads / momentum_buf; a NULL, misaligned or overlapping ema, or an ema_momentum outside [0, 1] (or
+ * NaN), is MVF_EINVAL and nothing is launched. */
+int mvf_sgd_nesterov_step_ema(float* params, const float* grads, float* momentum_buf, long n, float grad_scale, float max_norm, float lr, float momentum,
+                              float weight_decay, int first_step, float* ema, float ema_momentum, float* norm_out, void* ws, size_t ws_bytes, void* stream);
+int mvf_sgd_step_segments_ema(float* params, const float* grads, float* momentum_buf, long n, float grad_scale, float max_norm, float lr, float momentum,
+                              float weight_decay, int first_step, int nesterov, const mvf_sgd_segment_t* segments, int nseg, float* ema, float ema_momentum,
+                              float* norm_out, void* ws, size_t ws_bytes, void* stream);
+/* The same update as a launch of its own (after an optimizer that is not this library's, and the twin the fused kernels are tested against), and the in-place
+ * exchange of two flat buffers (averaged <-> live parameters for evaluation: the model's parameters are views of the flat buffer, so pointers cannot be
+ * swapped; no third buffer is allocated).  Operands are flat fp32 device arrays that need only 4-byte alignment (they may be misaligned relative to each
+ * other) and must not overlap; nothing outside [0, n) is read or written; the grid depends on n and the alignment only, no atomics: bit-identical from run to
+ * run.  n == 0 succeeds without a launch; n < 0, a NULL pointer with n > 0, overlap, or a momentum outside [0, 1] (or NaN) is MVF_EINVAL. */
+int mvf_ema_update(float* ema, const float* params, long n, float momentum, void* stream);
+int mvf_ema_swap(float* a, float* b, long n, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * [r6] Launch-table replay.  One training step (the reference's batch_processor + DistOptimizerHook.after_train_iter, codes/core/train.py:45-60,

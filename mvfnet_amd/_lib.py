@@ -236,6 +236,14 @@ def _load():
     lib.mvf_sgd_step_segments.argtypes = [fp, fp, fp, i64, f32, f32, f32, f32, f32, i32, i32, vp, i32, fp, vp, sz, vp]
     lib.mvf_grad_accumulate.restype = i32
     lib.mvf_grad_accumulate.argtypes = [fp, fp, i64, i32, vp]
+    lib.mvf_sgd_nesterov_step_ema.restype = i32
+    lib.mvf_sgd_nesterov_step_ema.argtypes = [fp, fp, fp, i64, f32, f32, f32, f32, f32, i32, fp, f32, fp, vp, sz, vp]
+    lib.mvf_sgd_step_segments_ema.restype = i32
+    lib.mvf_sgd_step_segments_ema.argtypes = [fp, fp, fp, i64, f32, f32, f32, f32, f32, i32, i32, vp, i32, fp, f32, fp, vp, sz, vp]
+    lib.mvf_ema_update.restype = i32
+    lib.mvf_ema_update.argtypes = [fp, fp, i64, f32, vp]
+    lib.mvf_ema_swap.restype = i32
+    lib.mvf_ema_swap.argtypes = [fp, fp, i64, vp]
     lib.mvf_plan_run.restype = i32
     lib.mvf_plan_run.argtypes = [C.POINTER(PlanOp), i32, C.POINTER(C.c_ulonglong), C.POINTER(C.c_float), C.POINTER(C.c_int)]
     # Callers pass device pointers as plain Python ints (train_engine._p): without declared argtypes ctypes would truncate them to c_int silently.  Every

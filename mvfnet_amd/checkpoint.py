@@ -73,15 +73,39 @@ def weights_to_cpu(state_dict):
     return OrderedDict((k, v.detach().cpu().clone()) for k, v in state_dict.items())
 
 
-def save_checkpoint(model, filename, optimizer=None, meta=None):
+def save_checkpoint(model, filename, optimizer=None, meta=None, ema=None):
+    """`ema` (TrainEngine.ema_state_dict()) is written as a top-level 'ema' entry beside meta / state_dict / optimizer; state_dict stays the LIVE weights, so
+    the reference's loader and resume, which read only the keys they know (codes/utils/checkpoint.py:178-217), are unaffected."""
     meta = dict(meta or {})
     meta.update(time=time.asctime(), framework="mvfnet_amd")
     os.makedirs(os.path.dirname(os.path.abspath(filename)), exist_ok=True)
     ckpt = dict(meta=meta, state_dict=weights_to_cpu(_unwrap(model).state_dict()))
     if optimizer is not None:
         ckpt["optimizer"] = optimizer.state_dict() if hasattr(optimizer, "state_dict") else optimizer
+    if ema is not None:
+        ckpt["ema"] = ema
     torch.save(ckpt, filename)
     return filename
+
+
+def averaged_state_dict(ckpt):
+    """The state dict a user hands to inference: the checkpoint's averaged PARAMETERS (its 'ema' entry) with the checkpoint's buffers (BatchNorm running
+    statistics are not averaged).  `ckpt`: a loaded checkpoint dict.  Every key of the 'ema' entry must be a key of state_dict with the same shape."""
+    if not isinstance(ckpt, dict) or "state_dict" not in ckpt:
+        raise ValueError("averaged_state_dict: not a checkpoint dict (no 'state_dict')")
+    ema = ckpt.get("ema")
+    if not ema or "state_dict" not in ema:
+        raise KeyError("averaged_state_dict: the checkpoint has no 'ema' entry (it was written without averaged weights: set ema_config / Runner(ema=...))")
+    out = OrderedDict((k, v.detach().clone()) for k, v in ckpt["state_dict"].items())
+    strip = bool(out) and all(k.startswith("module.") for k in out)
+    for name, value in ema["state_dict"].items():
+        key = "module." + name if strip else name
+        if key not in out:
+            raise KeyError("averaged_state_dict: averaged parameter %s is not in the checkpoint's state_dict" % name)
+        if tuple(value.shape) != tuple(out[key].shape):
+            raise ValueError("averaged_state_dict: %s is %s in the 'ema' entry and %s in state_dict" % (name, tuple(value.shape), tuple(out[key].shape)))
+        out[key] = value.detach().clone().to(out[key].dtype)
+    return out
 
 
 # ---- optimizer state: torch.optim.SGD's state_dict layout (what the reference's checkpoints hold, checkpoint.py:262-263) ---------

@@ -1366,15 +1366,20 @@ __global__ void norm_finalize_kernel(const float* part, int nblk, float max_norm
         out[1] = coef < 1.f ? coef : 1.f;
     }
 }
+// EMA: the averaged copy of the parameters (ema.hip) takes its update from the value this lane has just computed: ema[i] = ema_step(ema[i], p', ema_m), one
+// more read and one more write of a flat buffer instead of a launch that re-reads the parameters.  The plain instantiation is the kernel as it was.
+template <bool EMA>
 __global__ void sgd_nesterov_kernel(float* p, const float* g, float* buf, long n, const float* coef_ptr, float gscale, float lr,
-                                    float momentum, float wd, int first_step) {
+                                    float momentum, float wd, int first_step, float* ema, float ema_m) {
     const float coef = (coef_ptr ? coef_ptr[1] : 1.f) * gscale;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
         const float pv = p[i];
         const float d = g[i] * coef + wd * pv;
         const float b = first_step ? d : momentum * buf[i] + d;
         buf[i] = b;
-        p[i] = pv - lr * (d + momentum * b);
+        const float pn = pv - lr * (d + momentum * b);
+        p[i] = pn;
+        if (EMA) ema[i] = ema_step(ema[i], pn, ema_m);
     }
 }
 // sum of squares over the elements of the segments that take part in training (lr_mult >= 0): the clip norm of
@@ -1400,22 +1405,86 @@ __global__ void sqsum_segments_kernel(const float* g, long n, const mvf_sgd_segm
 // the same update with per-SEGMENT learning-rate / weight-decay multipliers (build_optimizer's paramwise_options, reference
 // codes/core/train.py:117-156) and an optional plain-momentum form: seg[k] = {first element, lr multiplier, decay multiplier},
 // sorted by first element, seg[0].first == 0; a workgroup's 256-element run looks its segment up by binary search per element
+template <bool EMA>
 __global__ void sgd_segments_kernel(float* p, const float* g, float* buf, long n, const float* coef_ptr, float gscale, float lr,
-                                    float momentum, float wd, int first_step, int nesterov, const mvf_sgd_segment_t* seg, int nseg) {
+                                    float momentum, float wd, int first_step, int nesterov, const mvf_sgd_segment_t* seg, int nseg, float* ema, float ema_m) {
     const float coef = (coef_ptr ? coef_ptr[1] : 1.f) * gscale;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
         const int lo = seg_of(seg, nseg, i);
-        if (seg[lo].lr_mult < 0.f) continue;                 // excluded from training (requires_grad False): parameter and momentum untouched
+        if (seg[lo].lr_mult < 0.f) continue;                 // excluded from training (requires_grad False): parameter, momentum and average untouched
         const float lr_i = lr * seg[lo].lr_mult, wd_i = wd * seg[lo].decay_mult;
         const float pv = p[i];
         const float d = g[i] * coef + wd_i * pv;
         const float b = first_step ? d : momentum * buf[i] + d;
         buf[i] = b;
-        p[i] = pv - lr_i * (nesterov ? d + momentum * b : b);
+        const float pn = pv - lr_i * (nesterov ? d + momentum * b : b);
+        p[i] = pn;
+        if (EMA) ema[i] = ema_step(ema[i], pn, ema_m);
     }
 }
 
 inline int grid_for(long total, int cap = 256 * 16) { return (int)std::min<long>((total + 255) / 256, cap); }
+
+// the averaged copy handed to an _ema optimizer step: 4-byte aligned, n elements, disjoint from the three buffers the step reads and writes
+int check_ema_arg(const char* who, const float* ema, float ema_m, const float* params, const float* grads, const float* buf, long n) {
+    MVF_REQUIRE(ema, MVF_EINVAL, "%s: NULL ema", who);
+    MVF_REQUIRE(ema_m >= 0.f && ema_m <= 1.f, MVF_EINVAL, "%s: ema_momentum=%g is outside [0, 1]", who, (double)ema_m);      // (NaN fails both)
+    const uintptr_t pe = (uintptr_t)ema, len = (uintptr_t)n * 4;
+    MVF_REQUIRE(pe % 4 == 0, MVF_EINVAL, "%s: ema must be 4-byte aligned", who);
+    const uintptr_t other[3] = {(uintptr_t)params, (uintptr_t)grads, (uintptr_t)buf};
+    const char* names[3] = {"params", "grads", "momentum_buf"};
+    for (int k = 0; k < 3; ++k)
+        MVF_REQUIRE(pe + len <= other[k] || other[k] + len <= pe, MVF_EINVAL, "%s: ema and %s overlap", who, names[k]);
+    return MVF_OK;
+}
+
+// clip + SGD on flat fp32 buffers (mvf_sgd_nesterov_step / mvf_sgd_step_segments below); EMA: the _ema twins
+template <bool EMA>
+int sgd_nesterov_step_impl(const char* who, float* params, const float* grads, float* momentum_buf, long n, float grad_scale, float max_norm, float lr,
+                                  float momentum, float weight_decay, int first_step, float* ema, float ema_m, float* norm_out, void* ws, size_t ws_bytes,
+                                  void* stream) {
+    MVF_REQUIRE(params && grads && momentum_buf && norm_out && n > 0, MVF_EINVAL, "%s: bad argument", who);
+    if (EMA) {
+        const int rc = check_ema_arg(who, ema, ema_m, params, grads, momentum_buf, n);
+        if (rc != MVF_OK) return rc;
+    }
+    MVF_REQUIRE(ws && ws_bytes >= mvf_sgd_workspace_bytes(n), MVF_EWS, "%s: workspace too small", who);
+    hipStream_t st = (hipStream_t)stream;
+    float* part = (float*)ws;
+    const int nb = (int)std::min<long>((n + 255) / 256, 1024);
+    hipLaunchKernelGGL(sqsum_partial_kernel, dim3(nb), dim3(256), 0, st, grads, n, part);
+    MVF_LAUNCH_CHECK();
+    // the norm is of the scaled gradient (all-reduce sum / world happens before clipping, dist_utils.py:63-66)
+    hipLaunchKernelGGL(norm_finalize_kernel, dim3(1), dim3(64), 0, st, part, nb, max_norm, grad_scale, norm_out);
+    MVF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sgd_nesterov_kernel<EMA>, dim3(grid_for(n)), dim3(256), 0, st, params, grads, momentum_buf, n, norm_out, grad_scale, lr, momentum, weight_decay,
+                       first_step, ema, ema_m);
+    MVF_LAUNCH_CHECK();
+    return MVF_OK;
+}
+
+template <bool EMA>
+int sgd_step_segments_impl(const char* who, float* params, const float* grads, float* momentum_buf, long n, float grad_scale, float max_norm, float lr,
+                                  float momentum, float weight_decay, int first_step, int nesterov, const mvf_sgd_segment_t* segments, int nseg, float* ema,
+                                  float ema_m, float* norm_out, void* ws, size_t ws_bytes, void* stream) {
+    MVF_REQUIRE(params && grads && momentum_buf && norm_out && segments && nseg > 0 && n > 0, MVF_EINVAL, "%s: bad argument", who);
+    if (EMA) {
+        const int rc = check_ema_arg(who, ema, ema_m, params, grads, momentum_buf, n);
+        if (rc != MVF_OK) return rc;
+    }
+    MVF_REQUIRE(ws && ws_bytes >= mvf_sgd_workspace_bytes(n), MVF_EWS, "%s: workspace too small", who);
+    hipStream_t st = (hipStream_t)stream;
+    float* part = (float*)ws;
+    const int nb = (int)std::min<long>((n + 255) / 256, 1024);
+    hipLaunchKernelGGL(sqsum_segments_kernel, dim3(nb), dim3(256), 0, st, grads, n, segments, nseg, part);
+    MVF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(norm_finalize_kernel, dim3(1), dim3(64), 0, st, part, nb, max_norm, grad_scale, norm_out);
+    MVF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sgd_segments_kernel<EMA>, dim3(grid_for(n)), dim3(256), 0, st, params, grads, momentum_buf, n, norm_out, grad_scale, lr, momentum, weight_decay,
+                       first_step, nesterov, segments, nseg, ema, ema_m);
+    MVF_LAUNCH_CHECK();
+    return MVF_OK;
+}
 
 }  // namespace
 
@@ -2028,37 +2097,28 @@ size_t mvf_sgd_workspace_bytes(long n) { return 1024 * sizeof(float); }
 int mvf_sgd_nesterov_step(float* params, const float* grads, float* momentum_buf, long n, float grad_scale, float max_norm,
                           float lr, float momentum, float weight_decay, int first_step, float* norm_out, void* ws,
                           size_t ws_bytes, void* stream) {
-    MVF_REQUIRE(params && grads && momentum_buf && norm_out && n > 0, MVF_EINVAL, "sgd_nesterov_step: bad argument");
-    MVF_REQUIRE(ws && ws_bytes >= mvf_sgd_workspace_bytes(n), MVF_EWS, "sgd_nesterov_step: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    float* part = (float*)ws;
-    const int nb = (int)std::min<long>((n + 255) / 256, 1024);
-    hipLaunchKernelGGL(sqsum_partial_kernel, dim3(nb), dim3(256), 0, st, grads, n, part);
-    MVF_LAUNCH_CHECK();
-    // the norm is of the scaled gradient (all-reduce sum / world happens before clipping, dist_utils.py:63-66)
-    hipLaunchKernelGGL(norm_finalize_kernel, dim3(1), dim3(64), 0, st, part, nb, max_norm, grad_scale, norm_out);
-    MVF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sgd_nesterov_kernel, dim3(grid_for(n)), dim3(256), 0, st, params, grads, momentum_buf, n, norm_out, grad_scale, lr, momentum, weight_decay, first_step);
-    MVF_LAUNCH_CHECK();
-    return MVF_OK;
+    return sgd_nesterov_step_impl<false>("sgd_nesterov_step", params, grads, momentum_buf, n, grad_scale, max_norm, lr, momentum, weight_decay, first_step, nullptr, 0.f,
+                                         norm_out, ws, ws_bytes, stream);
+}
+
+int mvf_sgd_nesterov_step_ema(float* params, const float* grads, float* momentum_buf, long n, float grad_scale, float max_norm, float lr, float momentum,
+                              float weight_decay, int first_step, float* ema, float ema_momentum, float* norm_out, void* ws, size_t ws_bytes, void* stream) {
+    return sgd_nesterov_step_impl<true>("sgd_nesterov_step_ema", params, grads, momentum_buf, n, grad_scale, max_norm, lr, momentum, weight_decay, first_step, ema,
+                                        ema_momentum, norm_out, ws, ws_bytes, stream);
 }
 
 int mvf_sgd_step_segments(float* params, const float* grads, float* momentum_buf, long n, float grad_scale, float max_norm, float lr,
                           float momentum, float weight_decay, int first_step, int nesterov, const mvf_sgd_segment_t* segments, int nseg,
                           float* norm_out, void* ws, size_t ws_bytes, void* stream) {
-    MVF_REQUIRE(params && grads && momentum_buf && norm_out && segments && nseg > 0 && n > 0, MVF_EINVAL, "sgd_step_segments: bad argument");
-    MVF_REQUIRE(ws && ws_bytes >= mvf_sgd_workspace_bytes(n), MVF_EWS, "sgd_step_segments: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    float* part = (float*)ws;
-    const int nb = (int)std::min<long>((n + 255) / 256, 1024);
-    hipLaunchKernelGGL(sqsum_segments_kernel, dim3(nb), dim3(256), 0, st, grads, n, segments, nseg, part);
-    MVF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(norm_finalize_kernel, dim3(1), dim3(64), 0, st, part, nb, max_norm, grad_scale, norm_out);
-    MVF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sgd_segments_kernel, dim3(grid_for(n)), dim3(256), 0, st, params, grads, momentum_buf, n, norm_out, grad_scale, lr, momentum, weight_decay,
-                       first_step, nesterov, segments, nseg);
-    MVF_LAUNCH_CHECK();
-    return MVF_OK;
+    return sgd_step_segments_impl<false>("sgd_step_segments", params, grads, momentum_buf, n, grad_scale, max_norm, lr, momentum, weight_decay, first_step, nesterov,
+                                         segments, nseg, nullptr, 0.f, norm_out, ws, ws_bytes, stream);
+}
+
+int mvf_sgd_step_segments_ema(float* params, const float* grads, float* momentum_buf, long n, float grad_scale, float max_norm, float lr, float momentum,
+                              float weight_decay, int first_step, int nesterov, const mvf_sgd_segment_t* segments, int nseg, float* ema, float ema_momentum,
+                              float* norm_out, void* ws, size_t ws_bytes, void* stream) {
+    return sgd_step_segments_impl<true>("sgd_step_segments_ema", params, grads, momentum_buf, n, grad_scale, max_norm, lr, momentum, weight_decay, first_step, nesterov,
+                                        segments, nseg, ema, ema_momentum, norm_out, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -78,19 +78,24 @@ def get_weighted_score(score_list, coeff_list):
     return list(np.tensordot(np.array(coeff_list), scores, axes=(0, 0)))
 
 
+WEIGHTS = ("live", "ema", "both")
+
+
 class EvalTopKAccuracyHook(object):
     """After every `interval`-th training epoch: score the validation set with the model in eval mode (every rank its
     `rank::world` share, rows gathered on rank 0 -- `runner.multi_gpu_test`) and log top-k accuracy
     (eval_hooks.py:17-104; the reference exchanges pickled temp files through `work_dir`, here the rows travel as one
     all_gather of float tensors)."""
 
-    def __init__(self, loader, labels, interval=1, k=(1, 5)):
-        self.loader, self.labels, self.interval, self.k = loader, list(labels), interval, tuple(k)
+    def __init__(self, loader, labels, interval=1, k=(1, 5), weights="live"):
+        """weights = 'live' (the parameters being trained), 'ema' (the averaged parameters the engine keeps: Runner(ema=...) / cfg.ema_config; scored inside
+        engine.averaged_weights(), figures labelled 'ema top1 acc', ...) or 'both' (two passes over the validation set, both sets of figures)."""
+        if weights not in WEIGHTS:
+            raise ValueError("weights must be one of %s, got %r" % (", ".join(map(repr, WEIGHTS)), weights))
+        self.loader, self.labels, self.interval, self.k, self.weights = loader, list(labels), interval, tuple(k), weights
         self.history = []
 
-    def after_train_epoch(self, runner):
-        if (runner.epoch % self.interval) != 0:
-            return None
+    def _score(self, runner, prefix):
         from .runner import multi_gpu_test
         was_training = runner.model.training
         results = multi_gpu_test(runner.model, self.loader, size=len(self.labels))
@@ -98,7 +103,24 @@ class EvalTopKAccuracyHook(object):
         if results is None:                          # not rank 0
             return None
         acc = top_k_accuracy([np.asarray(r).squeeze() for r in results], self.labels, k=self.k)
-        out = {"top%d acc" % kk: float(a) for kk, a in zip(self.k, acc)}
+        return {"%stop%d acc" % (prefix, kk): float(a) for kk, a in zip(self.k, acc)}
+
+    def after_train_epoch(self, runner):
+        if (runner.epoch % self.interval) != 0:
+            return None
+        out = {}
+        if self.weights != "live":
+            eng = getattr(runner, "engine", None)
+            if eng is None or getattr(eng, "flat_ema", None) is None:
+                raise RuntimeError("evaluation hook with weights=%r: the runner keeps no averaged weights; set ema_config (Runner(ema=dict(momentum=...)))" % self.weights)
+        if self.weights != "ema":
+            out = self._score(runner, "")
+        if self.weights != "live":
+            with runner.engine.averaged_weights():
+                ema = self._score(runner, "ema ")
+            out = None if out is None or ema is None else dict(out, **ema)
+        if out is None:
+            return None
         out["epoch"] = runner.epoch
         self.history.append(out)
         return out
@@ -111,7 +133,7 @@ class DistEvalTopKAccuracyHook(EvalTopKAccuracyHook):
     here -- pass the object).  Every rank scores items `rank::world` one by one, as DistEvalHook.after_train_epoch does
     (collate([data], samples_per_gpu=1) = a batch dimension of one), the rows are gathered on rank 0 and top-k accuracy is logged."""
 
-    def __init__(self, dataset, interval=1, k=(1,), dist=True):
+    def __init__(self, dataset, interval=1, k=(1,), dist=True, weights="live"):
         if isinstance(dataset, dict):
             raise TypeError("DistEvalTopKAccuracyHook: a dataset CONFIG dict needs the reference's dataset classes (out of scope here); "
                             "pass the Dataset object")
@@ -119,7 +141,7 @@ class DistEvalTopKAccuracyHook(EvalTopKAccuracyHook):
             raise TypeError("dataset must be a Dataset object or a dict, not {}".format(type(dataset)))      # the reference's message
         self.dataset, self.dist = dataset, dist
         labels = [dataset.video_infos[i]["label"] for i in range(len(dataset))]
-        super().__init__(_RankShare(dataset, dist), labels, interval, k)
+        super().__init__(_RankShare(dataset, dist), labels, interval, k, weights)
 
 
 class _RankShare(object):

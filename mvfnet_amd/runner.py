@@ -24,6 +24,7 @@ import torch.distributed as dist
 
 from .checkpoint import load_checkpoint, save_checkpoint
 from .dist import get_dist_info, init_dist  # noqa: F401  (re-exported: train_recognizer.py imports init_dist from the core package)
+from .ema import check_ema
 
 
 def set_random_seed(seed):
@@ -295,11 +296,14 @@ class Runner(object):
 
     def __init__(self, model, work_dir=None, lr=0.015, momentum=0.9, weight_decay=1e-4, max_norm=40.0, lr_steps=(90, 130),
                  warmup_iters=25070, warmup_ratio=0.01, ckpt_interval=10, log_interval=20, logger=print, optimizer=None, dtype=None,
-                 warmup="linear", lr_gamma=0.1, accumulate=1):
-        """accumulate = k > 1: gradient accumulation -- k loader batches (micro-batches, each under its own BatchNorm statistics) per optimizer step, the
+                 warmup="linear", lr_gamma=0.1, accumulate=1, ema=None):
+        """ema = dict(momentum=2e-4, warmup_steps=0) (either key may be left out): the engine keeps an exponential moving average of the parameters, one update
+        per optimizer step inside the fused optimizer kernel (TrainEngine.enable_ema); checkpoints carry it as 'ema', hooks can score it (weights='ema').
+        accumulate = k > 1: gradient accumulation -- k loader batches (micro-batches, each under its own BatchNorm statistics) per optimizer step, the
         reference's 8 x 12-clip recipe on one GPU with videos_per_gpu=12, accumulate=8.  `iter`, the warm-up and the log interval then count OPTIMIZER steps."""
         self.model, self.work_dir = model, work_dir
         self.accumulate = check_accumulate(accumulate)
+        self.ema = check_ema(ema)                    # (refused before anything is built)
         if optimizer is not None:                    # build_optimizer's object: hyper-parameters and param-wise options live there
             self.engine = optimizer.engine
             g = optimizer.param_groups[0]
@@ -317,6 +321,8 @@ class Runner(object):
         self.ckpt_interval, self.log_interval, self.log = ckpt_interval, log_interval, logger
         self.epoch, self.iter = 0, 0
         self.hooks = []               # objects with after_train_epoch(runner), e.g. evaluation.EvalTopKAccuracyHook
+        if self.ema is not None:
+            self.engine.enable_ema(**self.ema)
 
     def register_hook(self, hook):
         self.hooks.append(hook)
@@ -380,7 +386,8 @@ class Runner(object):
         state_dict layout (reference checkpoint.py:235-265, mmcv CheckpointHook)."""
         path = os.path.join(self.work_dir, "epoch_%d.pth" % self.epoch)
         self.engine.lr = self.current_lr()
-        save_checkpoint(self.model, path, optimizer=self.engine.optimizer_state_dict(), meta=dict(epoch=self.epoch, iter=self.iter))
+        save_checkpoint(self.model, path, optimizer=self.engine.optimizer_state_dict(), meta=dict(epoch=self.epoch, iter=self.iter),
+                        ema=self.engine.ema_state_dict() if self.engine.flat_ema is not None else None)
         latest = os.path.join(self.work_dir, "latest.pth")
         if os.path.lexists(latest):
             os.remove(latest)
@@ -398,6 +405,14 @@ class Runner(object):
             lr, mom, wd = self.engine.lr, self.engine.momentum, self.engine.weight_decay
             self.engine.load_optimizer_state_dict(opt)
             self.engine.lr, self.engine.momentum, self.engine.weight_decay = lr, mom, wd      # the config's values win (lr follows the schedule)
+        if ckpt.get("ema"):
+            self.engine.load_ema_state_dict(ckpt["ema"])
+            if self.ema is not None:                 # the config's momentum / warm-up win; the averaged weights and the update count are the checkpoint's
+                self.engine.ema_momentum, self.engine.ema_warmup_steps = self.ema["momentum"], self.ema["warmup_steps"]
+        elif self.ema is not None:
+            self.engine.reset_ema()
+            if self.log:
+                self.log("resume: %s carries no averaged weights ('ema'); the average starts from the loaded weights" % filename)
         return ckpt
 
 
@@ -420,12 +435,14 @@ def train_network(model, dataset, cfg, distributed=False, validate=False, logger
     """reference train.py:63-76 + _dist_train / _non_dist_train :159-252: loaders, model on the GPU (parameters broadcast from
     rank 0 when distributed), optimizer from cfg.optimizer, grad clip from cfg.optimizer_config, lr schedule from cfg.lr_config,
     checkpoints from cfg.checkpoint_config, logging interval from cfg.log_config, optional fp16 section, resume_from /
-    load_from, then run cfg.total_epochs.  cfg.optimizer_config.accumulate = k (an integer >= 1, default 1) makes one optimizer step of k loader batches
+    load_from, then run cfg.total_epochs.  cfg.ema_config = dict(momentum=..., warmup_steps=...) keeps averaged weights (Runner(ema=...)).
+    cfg.optimizer_config.accumulate = k (an integer >= 1, default 1) makes one optimizer step of k loader batches
     (gradient accumulation, Runner(accumulate=k)).  `dataset`: a torch Dataset of dict(img_group, label) items, a ready loader, or an
     iterable of batches (or a list whose first entry is the training one).  `validate` registers the reference's
     DistEvalTopKAccuracyHook(cfg.data.val, interval=cfg.eval_interval, k=(1, 5)) for a Dataset OBJECT under cfg.data.val."""
     cfg = as_config(cfg)
     accumulate = check_accumulate(_cfg_get(cfg.get("optimizer_config") or {}, "accumulate", 1))      # (refused before anything is built)
+    ema = check_ema(cfg.get("ema_config"))
     log = (logger.info if logger is not None and hasattr(logger, "info") else (logger or print))
     is_list_of_sets = isinstance(dataset, (list, tuple)) and dataset and not isinstance(dataset[0], dict)     # (a list of dicts = ready batches)
     datasets = dataset if is_list_of_sets else [dataset]
@@ -451,7 +468,7 @@ def train_network(model, dataset, cfg, distributed=False, validate=False, logger
                     lr_steps=[steps] if isinstance(steps, int) else tuple(steps), warmup=_cfg_get(lrc, "warmup"),
                     warmup_iters=_cfg_get(lrc, "warmup_iters", 0), warmup_ratio=_cfg_get(lrc, "warmup_ratio", 0.1),
                     lr_gamma=_cfg_get(lrc, "gamma", 0.1), ckpt_interval=_cfg_get(ck, "interval", 0) or 0,
-                    log_interval=_cfg_get(lg, "interval", 0) or 0, logger=log, optimizer=optimizer, accumulate=accumulate)
+                    log_interval=_cfg_get(lg, "interval", 0) or 0, logger=log, optimizer=optimizer, accumulate=accumulate, ema=ema)
     if clip and _cfg_get(clip, "norm_type", 2) != 2:
         raise NotImplementedError("grad_clip norm_type %r: the fused clip is the L2 norm" % _cfg_get(clip, "norm_type"))
     if validate:

@@ -60,6 +60,7 @@ def _p(t):
     return t.data_ptr() if t is not None else None
 
 
+from .ema import check_ema as _check_ema, momentum_at as _ema_momentum_at
 from .policy import policy as _policy      # MVF_POLICY="name=value,...": the one environment variable of the switches below
 
 
@@ -1065,6 +1066,7 @@ class _ParamStore(object):
         self._ws = None
         self.norm_out = torch.zeros(2, device=dev)
         self.steps = 0
+        self.ema_momentum, self.ema_warmup_steps, self.ema_updates = None, 0, 0      # averaged weights (enable_ema); instance attributes: no plan-key switches
         self._ones = {}
         self._bufs = {}
         self._caps = {}
@@ -1319,17 +1321,110 @@ class _ParamStore(object):
         n = self.flat_params.numel() - off
         if n <= 0:
             return None
+        if self._ema_swapped:
+            raise RuntimeError("apply_sgd inside averaged_weights(): the parameters are the averaged ones; leave the block before training")
         ws = self.workspace(lib.mvf_sgd_workspace_bytes(n))
         args = (_p(self.flat_params[off:]), _p(grads[off:]), _p(self.flat_mom[off:]), n, C.c_float(grad_scale),
                 C.c_float(self.max_norm or 0.0), C.c_float(self.lr if lr is None else lr), C.c_float(self.momentum),
                 C.c_float(self.weight_decay), int(self.steps == 0))
-        if self.nesterov and not self.param_options and not self._scattered_frozen:
-            check(lib.mvf_sgd_nesterov_step(*(args + (_p(self.norm_out), _p(ws), ws.numel(), _st()))), "sgd step")
-        else:
+        tail = (_p(self.norm_out), _p(ws), ws.numel(), _st())
+        flat = self.nesterov and not self.param_options and not self._scattered_frozen
+        if not flat:
             tab, nseg = self._segments(off)
-            check(lib.mvf_sgd_step_segments(*(args + (int(self.nesterov), _p(tab), nseg, _p(self.norm_out), _p(ws), ws.numel(), _st()))), "sgd step")
+            args += (int(self.nesterov), _p(tab), nseg)
+        if self.flat_ema is None:
+            check((lib.mvf_sgd_nesterov_step if flat else lib.mvf_sgd_step_segments)(*(args + tail)), "sgd step")
+        else:
+            # the averaged copy moves in the kernel that stores the new parameters; the step's momentum travels by value (the optimizer runs outside the launch plans)
+            ema = (_p(self.flat_ema[off:]), C.c_float(_ema_momentum_at(self.ema_momentum, self.ema_warmup_steps, self.ema_updates)))
+            check((lib.mvf_sgd_nesterov_step_ema if flat else lib.mvf_sgd_step_segments_ema)(*(args + ema + tail)), "sgd step (ema)")
+            self.ema_updates += 1
         self.steps += 1
         return self.norm_out
+
+    # ---- averaged weights: an exponential moving average of the parameters, one update per OPTIMIZER step ------------------------------------------------
+    # e' = fmaf(m_t, p' - e, e) in fp32 (csrc/common.h ema_step), m_t = ema.momentum_at(momentum, warmup_steps, t).  flat_ema is laid out like flat_params; the
+    # elements in front of trainable_offset() and those of excluded segments are never touched and stay equal to their initial copy.  Under a process group
+    # nothing is exchanged: every rank holds identical parameters, hence identical averages.  An engine that never calls enable_ema allocates and launches
+    # exactly what it did without any of this (flat_ema is None, _apply_sgd calls the plain entry points).
+    flat_ema = None
+    _ema_swapped = False
+
+    def enable_ema(self, momentum=2e-4, warmup_steps=0):
+        """Start averaging: flat_ema = a copy of the current parameters, no update made yet.  momentum = the weight of the NEW parameters per optimizer step;
+        during the first warmup_steps updates it is max(momentum, 1 / (t + 1)), the plain running mean of the first iterates."""
+        if not self.rehomed:
+            raise RuntimeError("enable_ema: this store does not own its parameters (stand-alone Bottleneck.forward)")
+        cfg = _check_ema(dict(momentum=momentum, warmup_steps=warmup_steps))
+        self._ema_live("enable_ema")
+        self.ema_momentum, self.ema_warmup_steps = cfg["momentum"], cfg["warmup_steps"]
+        if self.flat_ema is None:
+            self.flat_ema = torch.empty_like(self.flat_params)      # a new allocation beside the others: no recorded plan holds its address
+        self.reset_ema()
+
+    def disable_ema(self):
+        self._ema_live("disable_ema")
+        self.flat_ema, self.ema_momentum, self.ema_warmup_steps, self.ema_updates = None, None, 0, 0
+
+    def reset_ema(self):
+        """The averaged copy becomes the current parameters again (one device copy); the update count, hence the warm-up, starts over."""
+        self._ema_on("reset_ema")
+        self._ema_live("reset_ema")
+        self.flat_ema.copy_(self.flat_params)
+        self.ema_updates = 0
+
+    def update_ema(self):
+        """One update as a launch of its own (mvf_ema_update), for an optimizer that is not the engine's (attach_grads + a torch optimizer): call it after that
+        optimizer's step.  The engine's own optimizer paths update the average inside their kernel and must not be followed by this."""
+        self._ema_on("update_ema")
+        self._ema_live("update_ema")
+        off = self.trainable_offset()
+        m = _ema_momentum_at(self.ema_momentum, self.ema_warmup_steps, self.ema_updates)
+        check(lib.mvf_ema_update(_p(self.flat_ema[off:]), _p(self.flat_params[off:]), self.flat_params.numel() - off, C.c_float(m), _st()), "ema update")
+        self.ema_updates += 1
+
+    def ema_of(self, p):
+        """The averaged copy's view for a parameter (beside grad_of / acc_grad_of)."""
+        self._ema_on("ema_of")
+        v = self._grad_view[id(p)]
+        first = v.storage_offset()
+        return self.flat_ema[first:first + v.numel()].view(v.shape)
+
+    def _ema_on(self, who):
+        if self.flat_ema is None:
+            raise RuntimeError("%s: no averaged weights are kept; call enable_ema() (Runner(ema=...), cfg.ema_config) first" % who)
+
+    def _ema_live(self, who):
+        if self._ema_swapped:
+            raise RuntimeError("%s inside averaged_weights(): leave the block first" % who)
+
+    def ema_state_dict(self):
+        """{'state_dict': {parameter name: cpu fp32 tensor}, 'updates': t, 'momentum': ..., 'warmup_steps': ...}: what a checkpoint carries as its 'ema' entry."""
+        from collections import OrderedDict
+        self._ema_on("ema_state_dict")
+        self._ema_live("ema_state_dict")
+        sd = OrderedDict((name, self.ema_of(p).detach().cpu().clone()) for name, p in self.model.named_parameters())
+        return dict(state_dict=sd, updates=int(self.ema_updates), momentum=float(self.ema_momentum), warmup_steps=int(self.ema_warmup_steps))
+
+    def load_ema_state_dict(self, state):
+        """Inverse of ema_state_dict: enables the average if need be.  Every parameter must be there under its name with its shape, and nothing else."""
+        self._ema_live("load_ema_state_dict")
+        sd = state["state_dict"]
+        params = dict(self.model.named_parameters())
+        missing, unexpected = sorted(set(params) - set(sd)), sorted(set(sd) - set(params))
+        if missing or unexpected:
+            raise ValueError("ema state: parameter names do not match the model (missing: %s; unexpected: %s)" % (", ".join(missing) or "-", ", ".join(unexpected) or "-"))
+        for name, p in params.items():
+            if tuple(sd[name].shape) != tuple(p.shape):
+                raise ValueError("ema state: %s is %s, the parameter %s" % (name, tuple(sd[name].shape), tuple(p.shape)))
+        cfg = _check_ema(dict(momentum=state["momentum"], warmup_steps=state["warmup_steps"]))
+        if self.flat_ema is None:
+            self.enable_ema(**cfg)
+        self.ema_momentum, self.ema_warmup_steps = cfg["momentum"], cfg["warmup_steps"]
+        with torch.no_grad():
+            for name, p in params.items():
+                self.ema_of(p).copy_(sd[name].to(device=self.device, dtype=torch.float32))
+        self.ema_updates = int(state["updates"])
 
     # ---- optimizer state in torch.optim.SGD's wire format (reference checkpoints: codes/utils/checkpoint.py:235-265) ---------
     def optimizer_state_dict(self):
@@ -1504,6 +1599,8 @@ class TrainEngine(_ParamStore):
         [B] int64 (GPU), or soft labels [B, num_classes] floating point -> loss tensor (1,), keeps activations."""
         if not imgs.is_cuda or imgs.dtype not in (torch.float32, torch.uint8):
             raise RuntimeError("TrainEngine.forward: float32 (or uint8 frames) GPU input required")
+        if self._ema_swapped:
+            self._ema_live("a training forward")
         self._main = torch.cuda.current_stream()
         self.forward_count += 1
         with _on_stream(self._main, main=True):
@@ -1851,6 +1948,8 @@ class TrainEngine(_ParamStore):
         """forward + backward of one step, replayed from a launch plan where one exists.  exchange=True is train_step.  exchange=False is a micro-step of
         accumulate_step: without a process group the flag changes no launch, so it shares train_step's plans (same key, same recordings); WITH one, a plan
         recorded by train_step carries the tail bucket's collective, which a micro-step must not issue -- those micro-steps run eagerly, never from a plan."""
+        if self._ema_swapped:
+            self._ema_live("a training step")
         key = self._plan_key(imgs, labels) if imgs.is_cuda else None
         if not exchange and self._ddp_active():
             key = None
@@ -1948,9 +2047,46 @@ class TrainEngine(_ParamStore):
         self.accumulated_count = 0
         return self.norm_out
 
+    def averaged_weights(self):
+        """with engine.averaged_weights(): the model's parameters ARE the averaged ones -- model.state_dict() and the eval-mode forward see them.  Entry and exit
+        exchange flat_params and flat_ema in place (mvf_ema_swap on the current stream, no third buffer) and drop the backbone's and the head's cached
+        inference engines, which hold packed copies.  Only PARAMETERS are averaged: BatchNorm running statistics (buffers) are the live ones, as mmengine's
+        ExponentialMovingAverage and torch.optim.swa_utils.AveragedModel do by default (update_buffers / use_buffers False).  Training calls inside the block
+        and nested entry raise.  After exit the parameters and the averaged copy hold the bits they held before entry."""
+        return _AveragedWeights(self)
+
+    def _swap_ema(self):
+        check(lib.mvf_ema_swap(_p(self.flat_params), _p(self.flat_ema), self.flat_params.numel(), _st()), "ema swap")
+        for m_ in (self.model.backbone, self.model.cls_head):
+            if hasattr(m_, "invalidate_engine"):
+                m_.invalidate_engine()
+
     def train_step_accumulated(self, batches, lr=None):
         """One optimizer step over an iterable of (imgs, labels) micro-batches; returns the mean of their losses (device tensor)."""
         for imgs, labels in batches:
             self.accumulate_step(imgs, labels)
         self.apply_accumulated(lr)
         return self.accumulated_loss
+
+
+class _AveragedWeights(object):
+    """TrainEngine.averaged_weights()"""
+
+    def __init__(self, eng):
+        self.eng = eng
+
+    def __enter__(self):
+        eng = self.eng
+        eng._ema_on("averaged_weights")
+        if eng._ema_swapped:
+            raise RuntimeError("averaged_weights() is already entered; the blocks do not nest")
+        if eng.accumulated_count:
+            raise RuntimeError("averaged_weights(): %d micro-steps are pending in the accumulator; call apply_accumulated() first" % eng.accumulated_count)
+        eng._swap_ema()
+        eng._ema_swapped = True
+        return eng
+
+    def __exit__(self, *a):
+        self.eng._swap_ema()
+        self.eng._ema_swapped = False
+        return False
