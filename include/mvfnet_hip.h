@@ -602,6 +602,26 @@ int mvf_sgd_step_segments_ema(float* params, const float* grads, float* momentum
  * run.  n == 0 succeeds without a launch; n < 0, a NULL pointer with n > 0, overlap, or a momentum outside [0, 1] (or NaN) is MVF_EINVAL. */
 int mvf_ema_update(float* ema, const float* params, long n, float momentum, void* stream);
 int mvf_ema_swap(float* a, float* b, long n, void* stream);
+/* Precise BatchNorm (mmaction2's PreciseBNHook, fvcore's update_bn_stats): before evaluation the running statistics of every BatchNorm in training mode are
+ * replaced by the plain average of the per-batch statistics over a few hundred forward-only batches with the weights held fixed.  The statistics stay in the
+ * modules' own buffers; a persistent DEVICE table of segments lays them out as one flat "shadow" range [0, n): segment k = {ptr, first} owns shadow elements
+ * [first_k, first_{k+1}) (the last one up to n), element first_k + j being ptr[j].  Each entry point is ONE launch over the whole table, one thread per
+ * element, no atomics: bit-identical from run to run.
+ *   accumulate:  acc[i] += (double)value_i                                   (after a forward whose statistics kernels ran with momentum 1: value = the batch's)
+ *   finalize:    (float)(acc[i] / (double)count) -> dst_flat_or_null[i], or with NULL through the table into the segments; equals numpy's
+ *                np.float32(sum_in_call_order(np.float64(x)) / np.float64(count)) bit for bit
+ *   exchange:    mode 0 flat[i] = value_i (gather), 1 value_i = flat[i] (scatter), 2 swap; 32-bit words moved unchanged (NaN payloads, -0.0)
+ * Checked before any launch, MVF_EINVAL otherwise: non-NULL seg / acc / flat (acc 8-byte, flat and every segment pointer 4-byte aligned), nseg > 0, n > 0,
+ * count > 0, mode in 0..2, first_0 == 0, first strictly ascending and below n, no segment overlapping the flat array of the call.  The table is read on the
+ * host for that check: directly when `seg` is host memory (only the checks can succeed then), through a private non-blocking stream when it is device memory
+ * -- that waits for a 16 * nseg byte copy, never for the caller's stream; the table's upload must be complete, and the calls cannot be captured into a HIP graph. */
+typedef struct mvf_stat_segment {
+    float* ptr;
+    long first;
+} mvf_stat_segment_t;
+int mvf_bn_stats_accumulate(const mvf_stat_segment_t* seg, int nseg, long n, double* acc, void* stream);
+int mvf_bn_stats_finalize(const mvf_stat_segment_t* seg, int nseg, long n, const double* acc, long count, float* dst_flat_or_null, void* stream);
+int mvf_bn_stats_exchange(const mvf_stat_segment_t* seg, int nseg, long n, float* flat, int mode, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * [r6] Launch-table replay.  One training step (the reference's batch_processor + DistOptimizerHook.after_train_iter, codes/core/train.py:45-60,

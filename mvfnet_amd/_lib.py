@@ -46,6 +46,11 @@ class SgdSegment(C.Structure):
     _fields_ = [("first", C.c_int64), ("lr_mult", C.c_float), ("decay_mult", C.c_float)]
 
 
+class StatSegment(C.Structure):
+    """mvf_stat_segment_t: one BatchNorm statistic buffer in the flat shadow layout of the precise-BN entry points (csrc/precise_bn.hip)."""
+    _fields_ = [("ptr", C.c_void_p), ("first", C.c_long)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -244,6 +249,12 @@ def _load():
     lib.mvf_ema_update.argtypes = [fp, fp, i64, f32, vp]
     lib.mvf_ema_swap.restype = i32
     lib.mvf_ema_swap.argtypes = [fp, fp, i64, vp]
+    lib.mvf_bn_stats_accumulate.restype = i32
+    lib.mvf_bn_stats_accumulate.argtypes = [vp, i32, i64, vp, vp]
+    lib.mvf_bn_stats_finalize.restype = i32
+    lib.mvf_bn_stats_finalize.argtypes = [vp, i32, i64, vp, i64, fp, vp]
+    lib.mvf_bn_stats_exchange.restype = i32
+    lib.mvf_bn_stats_exchange.argtypes = [vp, i32, i64, fp, i32, vp]
     lib.mvf_plan_run.restype = i32
     lib.mvf_plan_run.argtypes = [C.POINTER(PlanOp), i32, C.POINTER(C.c_ulonglong), C.POINTER(C.c_float), C.POINTER(C.c_int)]
     # Callers pass device pointers as plain Python ints (train_engine._p): without declared argtypes ctypes would truncate them to c_int silently.  Every

@@ -89,8 +89,10 @@ def save_checkpoint(model, filename, optimizer=None, meta=None, ema=None):
 
 
 def averaged_state_dict(ckpt):
-    """The state dict a user hands to inference: the checkpoint's averaged PARAMETERS (its 'ema' entry) with the checkpoint's buffers (BatchNorm running
-    statistics are not averaged).  `ckpt`: a loaded checkpoint dict.  Every key of the 'ema' entry must be a key of state_dict with the same shape."""
+    """The state dict a user hands to inference: the checkpoint's averaged PARAMETERS (its 'ema' entry) with the BatchNorm running statistics measured under
+    them where the entry carries some ('bn_stats': TrainEngine.precise_bn(weights='ema')), else -- and for every other buffer -- with the checkpoint's live
+    buffers (running statistics are not averaged).  `ckpt`: a loaded checkpoint dict.  Every key of the 'ema' entry must be a key of state_dict with the
+    same shape."""
     if not isinstance(ckpt, dict) or "state_dict" not in ckpt:
         raise ValueError("averaged_state_dict: not a checkpoint dict (no 'state_dict')")
     ema = ckpt.get("ema")
@@ -98,7 +100,7 @@ def averaged_state_dict(ckpt):
         raise KeyError("averaged_state_dict: the checkpoint has no 'ema' entry (it was written without averaged weights: set ema_config / Runner(ema=...))")
     out = OrderedDict((k, v.detach().clone()) for k, v in ckpt["state_dict"].items())
     strip = bool(out) and all(k.startswith("module.") for k in out)
-    for name, value in ema["state_dict"].items():
+    for name, value in list(ema["state_dict"].items()) + list((ema.get("bn_stats") or {}).items()):
         key = "module." + name if strip else name
         if key not in out:
             raise KeyError("averaged_state_dict: averaged parameter %s is not in the checkpoint's state_dict" % name)

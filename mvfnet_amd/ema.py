@@ -1,7 +1,8 @@
-"""Averaged weights (EMA): the host side that needs no device -- the configuration check and the per-step momentum.
+"""Averaged weights (EMA) and precise BatchNorm: the host side that needs no device -- the configuration checks and the per-step momentum.
 
 The average itself lives in the train engine (TrainEngine.enable_ema: a flat fp32 buffer beside flat_params, updated by the fused optimizer kernels,
-csrc/train_ops.hip / csrc/ema.hip); checkpoints carry it as a top-level 'ema' entry (checkpoint.averaged_state_dict)."""
+csrc/train_ops.hip / csrc/ema.hip); checkpoints carry it as a top-level 'ema' entry (checkpoint.averaged_state_dict).  Precise BatchNorm (TrainEngine.precise_bn, evaluation.PreciseBNHook)
+recomputes the running statistics before evaluation, also for the averaged weights."""
 import numpy as np
 
 EMA_KEYS = ("momentum", "warmup_steps")
@@ -32,3 +33,30 @@ def momentum_at(momentum, warmup_steps, t):
     """The weight of the new parameters in update number t (t = updates already made): max(momentum, 1 / (t + 1)) while t < warmup_steps -- a plain running
     mean of the first iterates -- then `momentum`."""
     return max(float(momentum), 1.0 / (t + 1)) if t < warmup_steps else float(momentum)
+
+
+PRECISE_BN_KEYS = ("num_iters", "interval", "weights")
+PRECISE_BN_DEFAULTS = dict(num_iters=200, interval=1, weights="live")
+PRECISE_BN_WEIGHTS = ("live", "ema", "both")
+
+
+def check_precise_bn(cfg):
+    """cfg.precise_bn / Runner(precise_bn=): None (off) or dict(num_iters=..., interval=..., weights='live' | 'ema' | 'both').  Returns None or a dict with the
+    three keys; an unknown key, a num_iters / interval that is not an integer >= 1 or another `weights` is refused."""
+    if cfg is None:
+        return None
+    if not hasattr(cfg, "keys"):
+        raise ValueError("precise_bn must be None or dict(num_iters=..., interval=..., weights=...), got %r" % (cfg,))
+    unknown = sorted(k for k in cfg.keys() if k not in PRECISE_BN_KEYS)
+    if unknown:
+        raise ValueError("precise_bn: unknown key %s (known: %s)" % (", ".join(map(repr, unknown)), ", ".join(PRECISE_BN_KEYS)))
+    out = dict(PRECISE_BN_DEFAULTS)
+    out.update({k: cfg[k] for k in cfg.keys()})
+    for k in ("num_iters", "interval"):
+        v = out[k]
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError("precise_bn: %s must be an integer >= 1, got %r" % (k, v))
+        out[k] = int(v)
+    if not isinstance(out["weights"], str) or out["weights"] not in PRECISE_BN_WEIGHTS:
+        raise ValueError("precise_bn: weights must be one of %s, got %r" % (", ".join(map(repr, PRECISE_BN_WEIGHTS)), out["weights"]))
+    return out

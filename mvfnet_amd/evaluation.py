@@ -1,4 +1,4 @@
-"""Evaluation metrics and the epoch-end evaluation hook of the runner shell.
+"""Evaluation metrics and the epoch-end hooks of the runner shell: top-k evaluation and precise BatchNorm before it.
 
 Mirrors the reference's `codes/core/evaluation/accuracy.py` (softmax :4-7, confusion_matrix :10-47, mean_class_accuracy :50-70,
 top_k_accuracy :83-100, get_weighted_score :103-124) and `eval_hooks.py` (DistEvalTopKAccuracyHook :86-104) in names, argument
@@ -124,6 +124,49 @@ class EvalTopKAccuracyHook(object):
         out["epoch"] = runner.epoch
         self.history.append(out)
         return out
+
+
+class PreciseBNHook(object):
+    """After every `interval`-th training epoch, BEFORE the evaluation hooks of that epoch (Runner.register_hook keeps hooks with `before_evaluation` in front):
+    recompute the BatchNorm running statistics as the plain average of per-batch statistics over at most `num_iters` batches of the TRAINING loader with the
+    weights held fixed (TrainEngine.precise_bn; mmaction2's PreciseBNHook, fvcore's update_bn_stats).  weights = 'live' (the modules' running statistics are
+    overwritten, training continues from them), 'ema' (the averaged model's own statistics, used inside engine.averaged_weights() and carried by checkpoints)
+    or 'both' (two passes over the loader's first batches).  loader = None: the loader the runner is training from."""
+
+    before_evaluation = True
+
+    def __init__(self, loader=None, num_iters=200, interval=1, weights="live"):
+        from .ema import check_precise_bn
+        cfg = check_precise_bn(dict(num_iters=num_iters, interval=interval, weights=weights))
+        self.loader, self.num_iters, self.interval, self.weights = loader, cfg["num_iters"], cfg["interval"], cfg["weights"]
+        self.history = []
+
+    @staticmethod
+    def _batches(loader):
+        for data in loader:
+            yield (data["img_group"], data["label"]) if hasattr(data, "keys") else tuple(data)
+
+    def after_train_epoch(self, runner):
+        if (runner.epoch % self.interval) != 0:
+            return None
+        eng = getattr(runner, "engine", None)
+        if self.weights != "live" and (eng is None or getattr(eng, "flat_ema", None) is None):
+            raise RuntimeError("precise BatchNorm with weights=%r: the runner keeps no averaged weights; set ema_config (Runner(ema=dict(momentum=...)))" % self.weights)
+        loader = self.loader if self.loader is not None else getattr(runner, "train_loader", None)
+        if loader is None:
+            raise RuntimeError("precise BatchNorm: no loader was given and the runner has not trained from one yet")
+        model = getattr(runner, "model", None)
+        was_training = model.training if model is not None else True
+        if model is not None:
+            model.train()                            # (the backbone's train() keeps norm_eval / frozen stages in eval mode: those are not calibrated)
+        used = {}
+        for w in ("live", "ema"):
+            if self.weights in (w, "both"):
+                used[w] = eng.precise_bn(self._batches(loader), num_iters=self.num_iters, weights=w)
+        if model is not None:
+            model.train(was_training)
+        self.history.append(dict(epoch=runner.epoch, batches=used))
+        return None                                  # nothing to log as a figure
 
 
 class DistEvalTopKAccuracyHook(EvalTopKAccuracyHook):

@@ -24,7 +24,7 @@ import torch.distributed as dist
 
 from .checkpoint import load_checkpoint, save_checkpoint
 from .dist import get_dist_info, init_dist  # noqa: F401  (re-exported: train_recognizer.py imports init_dist from the core package)
-from .ema import check_ema
+from .ema import check_ema, check_precise_bn
 
 
 def set_random_seed(seed):
@@ -296,14 +296,20 @@ class Runner(object):
 
     def __init__(self, model, work_dir=None, lr=0.015, momentum=0.9, weight_decay=1e-4, max_norm=40.0, lr_steps=(90, 130),
                  warmup_iters=25070, warmup_ratio=0.01, ckpt_interval=10, log_interval=20, logger=print, optimizer=None, dtype=None,
-                 warmup="linear", lr_gamma=0.1, accumulate=1, ema=None):
+                 warmup="linear", lr_gamma=0.1, accumulate=1, ema=None, precise_bn=None):
         """ema = dict(momentum=2e-4, warmup_steps=0) (either key may be left out): the engine keeps an exponential moving average of the parameters, one update
         per optimizer step inside the fused optimizer kernel (TrainEngine.enable_ema); checkpoints carry it as 'ema', hooks can score it (weights='ema').
+        precise_bn = dict(num_iters=200, interval=1, weights='live' | 'ema' | 'both') (any key may be left out): an evaluation.PreciseBNHook over the loader this
+        runner trains from recomputes the BatchNorm running statistics at epoch end, before the evaluation hooks ('ema' / 'both' need `ema`).
         accumulate = k > 1: gradient accumulation -- k loader batches (micro-batches, each under its own BatchNorm statistics) per optimizer step, the
         reference's 8 x 12-clip recipe on one GPU with videos_per_gpu=12, accumulate=8.  `iter`, the warm-up and the log interval then count OPTIMIZER steps."""
         self.model, self.work_dir = model, work_dir
         self.accumulate = check_accumulate(accumulate)
         self.ema = check_ema(ema)                    # (refused before anything is built)
+        self.precise_bn = check_precise_bn(precise_bn)
+        if self.precise_bn is not None and self.precise_bn["weights"] != "live" and self.ema is None:
+            raise ValueError("precise_bn: weights=%r needs averaged weights; set ema (ema_config) as well" % self.precise_bn["weights"])
+        self.train_loader = None
         if optimizer is not None:                    # build_optimizer's object: hyper-parameters and param-wise options live there
             self.engine = optimizer.engine
             g = optimizer.param_groups[0]
@@ -323,9 +329,17 @@ class Runner(object):
         self.hooks = []               # objects with after_train_epoch(runner), e.g. evaluation.EvalTopKAccuracyHook
         if self.ema is not None:
             self.engine.enable_ema(**self.ema)
+        if self.precise_bn is not None:
+            from .evaluation import PreciseBNHook
+            self.register_hook(PreciseBNHook(None, **self.precise_bn))
 
     def register_hook(self, hook):
-        self.hooks.append(hook)
+        """Hooks run in registration order, except that one with `before_evaluation` set (evaluation.PreciseBNHook) runs before every hook without it."""
+        if getattr(hook, "before_evaluation", False):
+            k = next((i for i, h in enumerate(self.hooks) if not getattr(h, "before_evaluation", False)), len(self.hooks))
+            self.hooks.insert(k, hook)
+        else:
+            self.hooks.append(hook)
         return hook
 
     def current_lr(self):
@@ -354,6 +368,7 @@ class Runner(object):
 
     def train_epoch(self, loader):
         self.model.train()
+        self.train_loader = loader                   # (what a PreciseBNHook without a loader of its own draws its batches from)
         rank, _ = get_dist_info()
         if self.accumulate > 1:
             self._train_epoch_accumulated(loader, rank)
@@ -436,6 +451,7 @@ def train_network(model, dataset, cfg, distributed=False, validate=False, logger
     rank 0 when distributed), optimizer from cfg.optimizer, grad clip from cfg.optimizer_config, lr schedule from cfg.lr_config,
     checkpoints from cfg.checkpoint_config, logging interval from cfg.log_config, optional fp16 section, resume_from /
     load_from, then run cfg.total_epochs.  cfg.ema_config = dict(momentum=..., warmup_steps=...) keeps averaged weights (Runner(ema=...)).
+    cfg.precise_bn = dict(num_iters=..., interval=..., weights=...) recomputes the BatchNorm running statistics at epoch end (Runner(precise_bn=...)).
     cfg.optimizer_config.accumulate = k (an integer >= 1, default 1) makes one optimizer step of k loader batches
     (gradient accumulation, Runner(accumulate=k)).  `dataset`: a torch Dataset of dict(img_group, label) items, a ready loader, or an
     iterable of batches (or a list whose first entry is the training one).  `validate` registers the reference's
@@ -443,6 +459,9 @@ def train_network(model, dataset, cfg, distributed=False, validate=False, logger
     cfg = as_config(cfg)
     accumulate = check_accumulate(_cfg_get(cfg.get("optimizer_config") or {}, "accumulate", 1))      # (refused before anything is built)
     ema = check_ema(cfg.get("ema_config"))
+    precise_bn = check_precise_bn(cfg.get("precise_bn"))
+    if precise_bn is not None and precise_bn["weights"] != "live" and ema is None:
+        raise ValueError("precise_bn: weights=%r needs averaged weights; set ema_config as well" % precise_bn["weights"])
     log = (logger.info if logger is not None and hasattr(logger, "info") else (logger or print))
     is_list_of_sets = isinstance(dataset, (list, tuple)) and dataset and not isinstance(dataset[0], dict)     # (a list of dicts = ready batches)
     datasets = dataset if is_list_of_sets else [dataset]
@@ -468,7 +487,7 @@ def train_network(model, dataset, cfg, distributed=False, validate=False, logger
                     lr_steps=[steps] if isinstance(steps, int) else tuple(steps), warmup=_cfg_get(lrc, "warmup"),
                     warmup_iters=_cfg_get(lrc, "warmup_iters", 0), warmup_ratio=_cfg_get(lrc, "warmup_ratio", 0.1),
                     lr_gamma=_cfg_get(lrc, "gamma", 0.1), ckpt_interval=_cfg_get(ck, "interval", 0) or 0,
-                    log_interval=_cfg_get(lg, "interval", 0) or 0, logger=log, optimizer=optimizer, accumulate=accumulate, ema=ema)
+                    log_interval=_cfg_get(lg, "interval", 0) or 0, logger=log, optimizer=optimizer, accumulate=accumulate, ema=ema, precise_bn=precise_bn)
     if clip and _cfg_get(clip, "norm_type", 2) != 2:
         raise NotImplementedError("grad_clip norm_type %r: the fused clip is the L2 norm" % _cfg_get(clip, "norm_type"))
     if validate:

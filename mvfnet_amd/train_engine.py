@@ -1018,6 +1018,38 @@ class _TBlock(object):
         return dx
 
 
+class _StatTable(object):
+    """Device table of mvf_stat_segment_t over the running_mean / running_var buffers of a list of _BN (csrc/precise_bn.hip): the buffers stay where they are,
+    the table lays them out as one flat range of n floats (mean then variance per BatchNorm, in the order given).  keys / slices: the state_dict name, flat
+    offset, length and shape of every segment.  acc (fp64) and shadow (fp32) are the two flat work arrays of TrainEngine.precise_bn."""
+
+    def __init__(self, eng, bns):
+        names = {id(m_): n_ for n_, m_ in eng.model.named_modules()}
+        segs, self.keys, self.slices, first = [], [], [], 0
+        for bn in bns:
+            for attr in ("running_mean", "running_var"):
+                t = getattr(bn.mod, attr)
+                segs.append(_lib.StatSegment(t.data_ptr(), first))
+                self.keys.append("%s.%s" % (names[id(bn.mod)], attr))
+                self.slices.append((first, t.numel(), tuple(t.shape)))
+                first += t.numel()
+        self.bns, self.nseg, self.n = list(bns), len(segs), first
+        arr = (_lib.StatSegment * len(segs))(*segs)
+        self.dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(eng.device)      # (from pageable memory: complete when .to() returns)
+        self.acc = torch.zeros(first, dtype=torch.float64, device=eng.device)
+        self.shadow = torch.empty(first, dtype=torch.float32, device=eng.device)
+
+    def accumulate(self):
+        check(lib.mvf_bn_stats_accumulate(_p(self.dev), self.nseg, self.n, _p(self.acc), _st()), "bn stats accumulate")
+
+    def finalize(self, count, dst=None):
+        check(lib.mvf_bn_stats_finalize(_p(self.dev), self.nseg, self.n, _p(self.acc), count, _p(dst), _st()), "bn stats finalize")
+
+    def exchange(self, flat, mode):
+        """mode 0: flat <- the modules' buffers, 1: the modules' buffers <- flat, 2: swap."""
+        check(lib.mvf_bn_stats_exchange(_p(self.dev), self.nseg, self.n, _p(flat), mode, _st()), "bn stats exchange")
+
+
 class _ParamStore(object):
     """Flat fp32 parameter / gradient / momentum buffers for a module; its nn.Parameters become views."""
 
@@ -1349,6 +1381,8 @@ class _ParamStore(object):
     # exactly what it did without any of this (flat_ema is None, _apply_sgd calls the plain entry points).
     flat_ema = None
     _ema_swapped = False
+    flat_ema_stats = None      # the averaged model's own BatchNorm statistics (TrainEngine.precise_bn(weights='ema')): flat fp32, laid out by _ema_stats_table
+    _ema_stats_table = None
 
     def enable_ema(self, momentum=2e-4, warmup_steps=0):
         """Start averaging: flat_ema = a copy of the current parameters, no update made yet.  momentum = the weight of the NEW parameters per optimizer step;
@@ -1365,6 +1399,7 @@ class _ParamStore(object):
     def disable_ema(self):
         self._ema_live("disable_ema")
         self.flat_ema, self.ema_momentum, self.ema_warmup_steps, self.ema_updates = None, None, 0, 0
+        self.flat_ema_stats = self._ema_stats_table = None
 
     def reset_ema(self):
         """The averaged copy becomes the current parameters again (one device copy); the update count, hence the warm-up, starts over."""
@@ -1372,6 +1407,7 @@ class _ParamStore(object):
         self._ema_live("reset_ema")
         self.flat_ema.copy_(self.flat_params)
         self.ema_updates = 0
+        self.flat_ema_stats = self._ema_stats_table = None      # (statistics calibrated for another average: precise_bn(weights='ema') measures them again)
 
     def update_ema(self):
         """One update as a launch of its own (mvf_ema_update), for an optimizer that is not the engine's (attach_grads + a torch optimizer): call it after that
@@ -1399,12 +1435,20 @@ class _ParamStore(object):
             raise RuntimeError("%s inside averaged_weights(): leave the block first" % who)
 
     def ema_state_dict(self):
-        """{'state_dict': {parameter name: cpu fp32 tensor}, 'updates': t, 'momentum': ..., 'warmup_steps': ...}: what a checkpoint carries as its 'ema' entry."""
+        """{'state_dict': {parameter name: cpu fp32 tensor}, 'updates': t, 'momentum': ..., 'warmup_steps': ...[, 'bn_stats': {buffer name: cpu fp32 tensor}]}:
+        what a checkpoint carries as its 'ema' entry."""
         from collections import OrderedDict
         self._ema_on("ema_state_dict")
         self._ema_live("ema_state_dict")
         sd = OrderedDict((name, self.ema_of(p).detach().cpu().clone()) for name, p in self.model.named_parameters())
-        return dict(state_dict=sd, updates=int(self.ema_updates), momentum=float(self.ema_momentum), warmup_steps=int(self.ema_warmup_steps))
+        out = dict(state_dict=sd, updates=int(self.ema_updates), momentum=float(self.ema_momentum), warmup_steps=int(self.ema_warmup_steps))
+        if self.flat_ema_stats is not None:
+            # the averaged model's own running statistics (precise_bn(weights='ema')) under their state_dict names; an engine that never calibrated them writes
+            # the entry it always wrote
+            host = self.flat_ema_stats.detach().cpu()
+            out["bn_stats"] = OrderedDict((key, host[first:first + k].view(shape).clone())
+                                          for key, (first, k, shape) in zip(self._ema_stats_table.keys, self._ema_stats_table.slices))
+        return out
 
     def load_ema_state_dict(self, state):
         """Inverse of ema_state_dict: enables the average if need be.  Every parameter must be there under its name with its shape, and nothing else."""
@@ -1425,6 +1469,29 @@ class _ParamStore(object):
             for name, p in params.items():
                 self.ema_of(p).copy_(sd[name].to(device=self.device, dtype=torch.float32))
         self.ema_updates = int(state["updates"])
+        self._load_ema_stats(state.get("bn_stats"))
+
+    def _load_ema_stats(self, stats):
+        """The 'bn_stats' part of an 'ema' entry: {'<module>.running_mean' / '<module>.running_var': tensor} of BatchNorms this engine runs, both buffers of each,
+        with their shapes.  None / empty (a checkpoint written without calibration): the averaged weights go with the live statistics again."""
+        self.flat_ema_stats = self._ema_stats_table = None
+        if not stats:
+            return
+        bns = getattr(self, "_all_bns", lambda: [])()
+        names = {id(m_): n_ for n_, m_ in self.model.named_modules()}
+        known = {"%s.%s" % (names[id(b.mod)], a): getattr(b.mod, a) for b in bns for a in ("running_mean", "running_var")}
+        unexpected = sorted(set(stats) - set(known))
+        if unexpected:
+            raise ValueError("ema state: bn_stats names no BatchNorm statistic of this model: %s" % ", ".join(unexpected))
+        picked = [b for b in bns if "%s.running_mean" % names[id(b.mod)] in stats or "%s.running_var" % names[id(b.mod)] in stats]
+        tab = self._stat_table(picked)
+        for key, (first, k, shape) in zip(tab.keys, tab.slices):
+            if key not in stats:
+                raise ValueError("ema state: bn_stats lacks %s" % key)
+            if tuple(stats[key].shape) != shape:
+                raise ValueError("ema state: bn_stats %s is %s, the buffer %s" % (key, tuple(stats[key].shape), shape))
+        host = torch.cat([stats[key].detach().to(dtype=torch.float32, device="cpu").reshape(-1) for key in tab.keys])
+        self.flat_ema_stats, self._ema_stats_table = host.to(self.device), tab
 
     # ---- optimizer state in torch.optim.SGD's wire format (reference checkpoints: codes/utils/checkpoint.py:235-265) ---------
     def optimizer_state_dict(self):
@@ -2048,18 +2115,134 @@ class TrainEngine(_ParamStore):
         return self.norm_out
 
     def averaged_weights(self):
-        """with engine.averaged_weights(): the model's parameters ARE the averaged ones -- model.state_dict() and the eval-mode forward see them.  Entry and exit
-        exchange flat_params and flat_ema in place (mvf_ema_swap on the current stream, no third buffer) and drop the backbone's and the head's cached
-        inference engines, which hold packed copies.  Only PARAMETERS are averaged: BatchNorm running statistics (buffers) are the live ones, as mmengine's
-        ExponentialMovingAverage and torch.optim.swa_utils.AveragedModel do by default (update_buffers / use_buffers False).  Training calls inside the block
-        and nested entry raise.  After exit the parameters and the averaged copy hold the bits they held before entry."""
+        """with engine.averaged_weights(): the model IS the averaged one -- model.state_dict() and the eval-mode forward see the averaged parameters.  Entry and
+        exit exchange flat_params and flat_ema in place (mvf_ema_swap on the current stream, no third buffer) and drop the backbone's and the head's cached
+        inference engines, which hold packed copies.
+        BatchNorm running statistics (buffers): once precise_bn(weights='ema') has measured the averaged model's own statistics (flat_ema_stats), entry and exit
+        also exchange those with the modules' buffers (mvf_bn_stats_exchange mode 2, one launch), so inside the block the averaged parameters go with statistics
+        measured under them; BatchNorms that were not calibrated (norm_eval / frozen stages) keep theirs.  An engine that never calibrated for 'ema' pairs the
+        averaged parameters with the LIVE statistics and issues the launches it always did, as mmengine's ExponentialMovingAverage and
+        torch.optim.swa_utils.AveragedModel do by default (update_buffers / use_buffers False).
+        Training calls inside the block and nested entry raise.  After exit the parameters, the averaged copy, the statistics and flat_ema_stats hold the bits
+        they held before entry."""
         return _AveragedWeights(self)
 
-    def _swap_ema(self):
+    def _swap_ema(self, stats=True):
+        """Exchange the live and the averaged model in place: the parameters, and (stats=True) the calibrated running statistics where flat_ema_stats exists."""
+        if stats and self.flat_ema_stats is not None:
+            self._ema_stats_table.exchange(self.flat_ema_stats, 2)
         check(lib.mvf_ema_swap(_p(self.flat_params), _p(self.flat_ema), self.flat_params.numel(), _st()), "ema swap")
+        self._invalidate_inference()
+
+    def _invalidate_inference(self):
         for m_ in (self.model.backbone, self.model.cls_head):
             if hasattr(m_, "invalidate_engine"):
                 m_.invalidate_engine()
+
+    # ---- precise BatchNorm: running statistics recomputed as the plain average of per-batch statistics, weights held fixed --------------------------------
+    # (mmaction2's PreciseBNHook, fvcore's update_bn_stats.)  The live running statistics are a momentum-0.1 average of the last few micro-batches -- with
+    # 12-clip micro-batches under blending the noisiest numbers of the model at evaluation time -- and the averaged weights (flat_ema) have none of their own.
+    # Calibration = k forward-only training-mode batches; every statistics kernel computes (1 - m) r + m x, so with the by-value momentum argument of every
+    # calibrated _BN at 1.0 the running buffers hold exactly the batch mean / unbiased batch variance after a forward, and ONE launch over a segment table
+    # (csrc/precise_bn.hip) adds all ~140 buffers into an fp64 shadow array; one more launch at the end writes (float)(sum / k).  No backward, no optimizer, no
+    # average update, no blending table, no dropout draw (the torch generator is left where it was); the forwards run eagerly: launch plans are neither
+    # recorded nor touched, and their frozen momentum words stay valid because _BN.momentum is back at its value afterwards.  Under a process group every rank
+    # calibrates its own statistics, as every rank keeps its own today.
+    def _all_bns(self):
+        """Every _BN the engine runs, in forward order."""
+        bns = [self.stem_bn]
+        for blk in self.blocks:
+            if blk.mvf is not None and blk.mvf.bn is not None:
+                bns.append(blk.mvf.bn)
+            bns += [b for b in (blk.b1, blk.bd, blk.b2, blk.b3) if b is not None]
+        return bns
+
+    def _stat_table(self, bns):
+        """The segment table over `bns`' running statistics, built once per set of buffers (= once per training / eval pattern)."""
+        key = tuple(getattr(b.mod, a).data_ptr() for b in bns for a in ("running_mean", "running_var"))
+        tabs = self.__dict__.setdefault("_stat_tables", {})
+        if key not in tabs:
+            tabs[key] = _StatTable(self, bns)
+        return tabs[key]
+
+    def precise_bn(self, batches, num_iters=200, weights="live"):
+        """Replace the running statistics of every BatchNorm in training mode by the plain average of their per-batch statistics over at most num_iters
+        batches of `batches` (an iterable of (imgs, labels), as train_step_accumulated takes; what it yields beyond num_iters is not consumed; if it ends
+        early, what came is used; no batch at all raises).  Frozen / norm_eval BatchNorms are not calibrated and keep their statistics bit for bit.
+        Parameters, optimizer state, num_batches_tracked and the averaged weights are left as they were.  Returns the number of batches used.
+
+        weights='live': the result overwrites the modules' running statistics and training continues from them.
+        weights='ema' (needs enable_ema): the averaged parameters are swapped in, the result goes to flat_ema_stats (which averaged_weights() then exchanges
+        with the modules' statistics on entry and exit; checkpoints carry it as ema['bn_stats']), and the live parameters and statistics end bit-equal to what
+        they were.
+
+        Refused: micro-steps pending in the accumulator; a non-finite calibrated statistic on entry (0 * inf would poison the first batch); a call inside
+        averaged_weights().  If a batch raises, the statistics are restored from the copy taken on entry and the error is passed on."""
+        import itertools
+        if weights not in ("live", "ema"):
+            raise ValueError("precise_bn: weights must be 'live' or 'ema', got %r" % (weights,))
+        if isinstance(num_iters, bool) or not isinstance(num_iters, int) or num_iters < 1:
+            raise ValueError("precise_bn: num_iters must be an integer >= 1, got %r" % (num_iters,))
+        self._ema_live("precise_bn")
+        ema = weights == "ema"
+        if ema:
+            self._ema_on("precise_bn(weights='ema')")
+        if self.accumulated_count:
+            raise RuntimeError("precise_bn: %d micro-steps are pending in the accumulator; call apply_accumulated() first" % self.accumulated_count)
+        bns = [b for b in self._all_bns() if not b.frozen]
+        if not bns:
+            return 0                             # every BatchNorm is frozen: nothing to calibrate
+        tab = self._stat_table(bns)
+        on = lambda: _on_stream(torch.cuda.current_stream(), main=True)      # noqa: E731
+        with on():
+            tab.exchange(tab.shadow, 0)          # the pre-call statistics: checked here, put back on failure (and after an 'ema' calibration)
+        if not bool(torch.isfinite(tab.shadow).all()):
+            bad = [key for key, (first, k, _) in zip(tab.keys, tab.slices) if not bool(torch.isfinite(tab.shadow[first:first + k]).all())]
+            raise RuntimeError("precise_bn: non-finite running statistics on entry (%s); nothing was changed" % ", ".join(bad[:4]))
+        nbt = self._nbt_flat.clone()
+        state = [(b, b.momentum) for b in bns], self.blending, self.dropout
+        tab.acc.zero_()
+        used, done, swapped = 0, False, False
+        try:
+            if ema:
+                with on():
+                    self._swap_ema(stats=False)
+                swapped = True
+            for b in bns:
+                b.momentum = 1.0
+            self.blending, self.dropout = None, 0.0
+            for imgs, labels in itertools.islice(batches, num_iters):
+                self.forward(imgs, labels)
+                with on():
+                    tab.accumulate()
+                used += 1
+            if used == 0:
+                raise ValueError("precise_bn: the iterable yielded no batch")
+            with on():
+                if ema:
+                    if self.flat_ema_stats is None or self._ema_stats_table is not tab:
+                        self.flat_ema_stats, self._ema_stats_table = torch.empty_like(tab.shadow), tab
+                    tab.finalize(used, self.flat_ema_stats)
+                else:
+                    tab.finalize(used)
+            done = True
+        finally:
+            for b, m in state[0]:
+                b.momentum = m
+            self.blending, self.dropout = state[1], state[2]
+            side = getattr(self, "_side", None)
+            if side is not None:
+                torch.cuda.current_stream().wait_stream(side)      # the forwards' data-gradient weight packs read the parameters there
+            with on():
+                if ema or not done:
+                    tab.exchange(tab.shadow, 1)
+                if swapped:
+                    self._swap_ema(stats=False)
+            self._nbt_flat.copy_(nbt)
+            self._nbt_touched = False
+            self.saved = None
+            self._invalidate_inference()
+        return used
 
     def train_step_accumulated(self, batches, lr=None):
         """One optimizer step over an iterable of (imgs, labels) micro-batches; returns the mean of their losses (device tensor)."""
