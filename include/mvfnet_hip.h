@@ -622,6 +622,41 @@ typedef struct mvf_stat_segment {
 int mvf_bn_stats_accumulate(const mvf_stat_segment_t* seg, int nseg, long n, double* acc, void* stream);
 int mvf_bn_stats_finalize(const mvf_stat_segment_t* seg, int nseg, long n, const double* acc, long count, float* dst_flat_or_null, void* stream);
 int mvf_bn_stats_exchange(const mvf_stat_segment_t* seg, int nseg, long n, float* flat, int mode, void* stream);
+/* Non-finite step guard: an optimizer step whose clip norm is not finite becomes a no-op ON THE DEVICE, with no host synchronisation, and the BatchNorm
+ * statistics the step's forward passes have already updated are put back (torch's GradScaler.step skips on found_inf, clip_grad_norm_ has
+ * error_if_nonfinite; here the decision never leaves the device).
+ *
+ * guard: four ints in device memory, 4-byte aligned, owned by the caller, zero at the start of a run:
+ *   guard[0]  this step's flag, 1 = skipped        guard[1]  skipped steps in total
+ *   guard[2]  the current run of consecutive skips  guard[3]  steps seen
+ *
+ * mvf_sgd_step_guarded: ONE entry point for the four forms of the step above -- segments == NULL (nseg ignored) is the flat Nesterov form
+ * (mvf_sgd_nesterov_step; `nesterov` is ignored), ema == NULL (ema_momentum ignored) keeps no average.  The flag is decided where the norm is finished, by
+ * the one lane that writes norm_out: flag = the scaled norm grad_scale * sqrt(sum g^2) is not finite.  That is a NaN or an infinity anywhere in a gradient
+ * that enters the norm, AND a finite gradient whose sum of squares overflows fp32 (|g| ~ 1.8e19 and beyond): such a step is SKIPPED too, where the plain
+ * entry points would clip it to nothing (coef = max_norm / inf = 0) or, with clipping off, apply it.  The same lane updates the counters (a good step
+ * resets guard[2]); norm_out is written as always, so a logged nan / inf is the honest value.  Every workgroup of the update kernel reads guard[0] and returns
+ * before any store when it is set: params, momentum_buf and ema keep their bits.  With the flag clear, params, momentum_buf, ema and norm_out are
+ * bit-identical to the plain entry point of the same form (the same kernel bodies and grids, instantiated with the check).  Excluded segments
+ * (lr_mult < 0) stay outside the norm and therefore outside the decision; so does whatever the caller cuts off in front of `params`.
+ * Checked as the _ema entry points are, and: a NULL or misaligned guard, or a guard that overlaps params / grads / momentum_buf / ema / norm_out / ws /
+ * the segment table, is MVF_EINVAL and nothing is launched.
+ *
+ * mvf_bn_stats_snapshot / mvf_bn_stats_restore: ONE launch each over a segment table of running statistics (as above) and an int64 array (the
+ * num_batches_tracked counters).  snapshot: flat[i] = value_i for i in [0, n), counters_copy[j] = counters[j] for j in [0, ncount).  restore: the inverse
+ * (value_i = flat[i], counters[j] = counters_copy[j]) when guard[0] != 0, and NOT ONE STORE otherwise.  Words travel as uint32 / int64 (NaN payloads, -0.0),
+ * one thread per element, no atomics.  ncount == 0 (then the two counter pointers may be NULL) moves the statistics alone.
+ * These two run every training step, so UNLIKE the three entry points above they do NOT read the table back to the host: they check their by-value arguments
+ * (nseg > 0, n > 0, nseg <= n, ncount >= 0), non-NULL pointers and their alignment (seg 8, flat and guard 4, counters 8 bytes), and that guard overlaps
+ * neither flat nor the counter arrays nor the table -- MVF_EINVAL otherwise, nothing launched.  The table's CONTENT (first_0 == 0, ascending offsets below n,
+ * valid pointers, no overlap with flat) must have been validated once by the caller when it built the table: any mvf_bn_stats_exchange call on it does. */
+int mvf_sgd_step_guarded(float* params, const float* grads, float* momentum_buf, long n, float grad_scale, float max_norm, float lr, float momentum,
+                         float weight_decay, int first_step, int nesterov, const mvf_sgd_segment_t* segments, int nseg, float* ema, float ema_momentum,
+                         int* guard, float* norm_out, void* ws, size_t ws_bytes, void* stream);
+int mvf_bn_stats_snapshot(const mvf_stat_segment_t* seg, int nseg, long n, float* flat, const long long* counters, long ncount, long long* counters_copy,
+                          void* stream);
+int mvf_bn_stats_restore(const mvf_stat_segment_t* seg, int nseg, long n, const float* flat, long long* counters, long ncount,
+                         const long long* counters_copy, const int* guard, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * [r6] Launch-table replay.  One training step (the reference's batch_processor + DistOptimizerHook.after_train_iter, codes/core/train.py:45-60,

@@ -255,6 +255,12 @@ def _load():
     lib.mvf_bn_stats_finalize.argtypes = [vp, i32, i64, vp, i64, fp, vp]
     lib.mvf_bn_stats_exchange.restype = i32
     lib.mvf_bn_stats_exchange.argtypes = [vp, i32, i64, fp, i32, vp]
+    lib.mvf_sgd_step_guarded.restype = i32
+    lib.mvf_sgd_step_guarded.argtypes = [fp, fp, fp, i64, f32, f32, f32, f32, f32, i32, i32, vp, i32, fp, f32, vp, fp, vp, sz, vp]
+    lib.mvf_bn_stats_snapshot.restype = i32
+    lib.mvf_bn_stats_snapshot.argtypes = [vp, i32, i64, fp, vp, i64, vp, vp]
+    lib.mvf_bn_stats_restore.restype = i32
+    lib.mvf_bn_stats_restore.argtypes = [vp, i32, i64, fp, vp, i64, vp, vp, vp]
     lib.mvf_plan_run.restype = i32
     lib.mvf_plan_run.argtypes = [C.POINTER(PlanOp), i32, C.POINTER(C.c_ulonglong), C.POINTER(C.c_float), C.POINTER(C.c_int)]
     # Callers pass device pointers as plain Python ints (train_engine._p): without declared argtypes ctypes would truncate them to c_int silently.  Every

@@ -17,6 +17,12 @@
 // is read back through a private non-blocking stream (16 bytes per segment, ~2 KB), which waits for that copy alone and never for the work queued on the
 // caller's stream.  The table's upload must have completed before the call (a torch .to(device) from pageable memory has); the entry points are not capturable
 // into a HIP graph -- the engine calls them outside its launch plans.
+//
+// Non-finite step guard (mvf_bn_stats_snapshot, mvf_bn_stats_restore): the same table, every training step.  snapshot gathers the statistics into a flat
+// array and copies the int64 num_batches_tracked array before the step's first forward; restore scatters both back when the optimizer's guard flag says the
+// step was skipped, and stores nothing otherwise (every lane reads the flag first).  One launch each: lanes [0, n) move the 32-bit words, lanes
+// [n, n + ncount) the counters.  These two do NOT read the table back -- a blocking copy per step is what the launch-ahead of the training loop cannot
+// afford -- they check by-value arguments and alignment only; the table's content is validated once by the caller (any mvf_bn_stats_exchange call on it).
 #include <climits>
 #include <cstring>
 #include <mutex>
@@ -65,6 +71,20 @@ __global__ __launch_bounds__(kThreads) void stats_exchange_kernel(const mvf_stat
         const uint32_t a = *e, b = flat[i];
         *e = b;
         flat[i] = a;
+    }
+}
+
+// RESTORE = false: flat / cnt_copy <- the segments / cnt; true: the other way round, and only when *guard != 0
+template <bool RESTORE>
+__global__ __launch_bounds__(kThreads) void stats_guard_kernel(const mvf_stat_segment_t* __restrict__ seg, int nseg, long n, uint32_t* flat, long long* cnt, long ncount,
+                                                                long long* cnt_copy, const int* __restrict__ guard) {
+    if (RESTORE) { if (guard[0] == 0) return; }
+    const long i = (long)blockIdx.x * kThreads + threadIdx.x;
+    if (i < n) {
+        uint32_t* e = element_of(seg, nseg, i);
+        if (RESTORE) *e = flat[i]; else flat[i] = *e;
+    } else if (i - n < ncount) {
+        if (RESTORE) cnt[i - n] = cnt_copy[i - n]; else cnt_copy[i - n] = cnt[i - n];
     }
 }
 
@@ -150,6 +170,34 @@ int check_table(const char* who, const mvf_stat_segment_t* seg, int nseg, long n
 
 inline int grid_of(long n) { return (int)((n + kThreads - 1) / kThreads); }
 
+// what snapshot / restore can check without reading the table: by-value arguments, NULL, alignment, and (restore) the guard against the other operands
+int check_guard_call(const char* who, const mvf_stat_segment_t* seg, int nseg, long n, const void* flat, const void* cnt, long ncount, const void* cnt_copy,
+                     const int* guard, bool with_guard) {
+    MVF_REQUIRE(seg && (uintptr_t)seg % 8 == 0, MVF_EINVAL, "%s: the segment table is NULL or not 8-byte aligned", who);
+    MVF_REQUIRE(nseg > 0, MVF_EINVAL, "%s: nseg=%d must be positive", who, nseg);
+    MVF_REQUIRE(n > 0, MVF_EINVAL, "%s: n=%ld must be positive", who, n);
+    MVF_REQUIRE((long)nseg <= n, MVF_EINVAL, "%s: nseg=%d segments cannot share n=%ld elements", who, nseg, n);
+    MVF_REQUIRE(ncount >= 0, MVF_EINVAL, "%s: ncount=%ld is negative", who, ncount);
+    MVF_REQUIRE(n <= LONG_MAX - ncount && (n + ncount + kThreads - 1) / kThreads <= (long)INT_MAX, MVF_EINVAL, "%s: n=%ld + ncount=%ld is beyond one launch", who, n,
+                ncount);
+    MVF_REQUIRE(flat && (uintptr_t)flat % 4 == 0, MVF_EINVAL, "%s: flat is NULL or not 4-byte aligned", who);
+    if (ncount > 0) {
+        MVF_REQUIRE(cnt && cnt_copy && (uintptr_t)cnt % 8 == 0 && (uintptr_t)cnt_copy % 8 == 0, MVF_EINVAL, "%s: the counter arrays are NULL or not 8-byte aligned", who);
+        const uintptr_t a = (uintptr_t)cnt, b = (uintptr_t)cnt_copy, len = (uintptr_t)ncount * 8;
+        MVF_REQUIRE(a + len <= b || b + len <= a, MVF_EINVAL, "%s: the counters and their copy overlap", who);
+    }
+    if (with_guard) {
+        MVF_REQUIRE(guard && (uintptr_t)guard % 4 == 0, MVF_EINVAL, "%s: guard is NULL or not 4-byte aligned", who);
+        const uintptr_t pg = (uintptr_t)guard;
+        const uintptr_t other[4] = {(uintptr_t)flat, (uintptr_t)cnt, (uintptr_t)cnt_copy, (uintptr_t)seg};
+        const uintptr_t bytes[4] = {(uintptr_t)n * 4, (uintptr_t)ncount * 8, (uintptr_t)ncount * 8, (uintptr_t)nseg * sizeof(mvf_stat_segment_t)};
+        const char* names[4] = {"flat", "the counters", "the counters' copy", "the segment table"};
+        for (int k = 0; k < 4; ++k)
+            MVF_REQUIRE(!other[k] || pg + 16 <= other[k] || other[k] + bytes[k] <= pg, MVF_EINVAL, "%s: guard and %s overlap", who, names[k]);
+    }
+    return MVF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -184,6 +232,26 @@ int mvf_bn_stats_exchange(const mvf_stat_segment_t* seg, int nseg, long n, float
     if (mode == 0) hipLaunchKernelGGL(stats_exchange_kernel<0>, dim3(grid_of(n)), dim3(kThreads), 0, st, seg, nseg, n, f);
     else if (mode == 1) hipLaunchKernelGGL(stats_exchange_kernel<1>, dim3(grid_of(n)), dim3(kThreads), 0, st, seg, nseg, n, f);
     else hipLaunchKernelGGL(stats_exchange_kernel<2>, dim3(grid_of(n)), dim3(kThreads), 0, st, seg, nseg, n, f);
+    MVF_LAUNCH_CHECK();
+    return MVF_OK;
+}
+
+int mvf_bn_stats_snapshot(const mvf_stat_segment_t* seg, int nseg, long n, float* flat, const long long* counters, long ncount, long long* counters_copy,
+                          void* stream) {
+    const int rc = check_guard_call("bn_stats_snapshot", seg, nseg, n, flat, counters, ncount, counters_copy, nullptr, false);
+    if (rc != MVF_OK) return rc;
+    hipLaunchKernelGGL(stats_guard_kernel<false>, dim3(grid_of(n + ncount)), dim3(kThreads), 0, (hipStream_t)stream, seg, nseg, n, reinterpret_cast<uint32_t*>(flat),
+                       const_cast<long long*>(counters), ncount, counters_copy, (const int*)nullptr);
+    MVF_LAUNCH_CHECK();
+    return MVF_OK;
+}
+
+int mvf_bn_stats_restore(const mvf_stat_segment_t* seg, int nseg, long n, const float* flat, long long* counters, long ncount,
+                         const long long* counters_copy, const int* guard, void* stream) {
+    const int rc = check_guard_call("bn_stats_restore", seg, nseg, n, flat, counters, ncount, counters_copy, guard, true);
+    if (rc != MVF_OK) return rc;
+    hipLaunchKernelGGL(stats_guard_kernel<true>, dim3(grid_of(n + ncount)), dim3(kThreads), 0, (hipStream_t)stream, seg, nseg, n,
+                       reinterpret_cast<uint32_t*>(const_cast<float*>(flat)), counters, ncount, const_cast<long long*>(counters_copy), guard);
     MVF_LAUNCH_CHECK();
     return MVF_OK;
 }

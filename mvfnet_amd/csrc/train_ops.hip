@@ -1349,7 +1349,11 @@ __global__ void sqsum_partial_kernel(const float* g, long n, float* part) {
     for (int o = blockDim.x >> 1; o > 0; o >>= 1) { if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
     if (threadIdx.x == 0) part[blockIdx.x] = red[0];
 }
-__global__ void norm_finalize_kernel(const float* part, int nblk, float max_norm, float gscale, float* out /*[0]=norm,[1]=coef*/) {
+// GUARD (mvf_sgd_step_guarded): the lane that finishes the norm also decides whether the step is skipped -- the scaled norm is not finite: a NaN / inf in a
+// gradient that entered the sum, or a sum of squares beyond fp32 -- and keeps the counters guard[0..4) = {this step's flag, skipped in total, consecutive
+// skips, steps seen}.  Exponent bits, not isfinite(): the test must survive any floating-point flag the library is ever built with.
+template <bool GUARD = false>
+__global__ void norm_finalize_kernel(const float* part, int nblk, float max_norm, float gscale, float* out /*[0]=norm,[1]=coef*/, int* guard = nullptr) {
     // 64 lanes sum strided slices of the partials (fixed order), lane 0 combines them in lane order: one wave, a handful of
     // memory round trips instead of nblk serial ones (47 -> ~6 us on the optimizer's critical path)
     __shared__ double red[64];
@@ -1364,13 +1368,22 @@ __global__ void norm_finalize_kernel(const float* part, int nblk, float max_norm
         out[0] = nrm;
         float coef = max_norm > 0.f ? max_norm / (nrm + 1e-6f) : 1.f;     // torch clip_grad_norm_
         out[1] = coef < 1.f ? coef : 1.f;
+        if (GUARD) {
+            const int bad = (__float_as_uint(nrm) & 0x7f800000u) == 0x7f800000u;
+            guard[0] = bad;
+            guard[1] += bad;
+            guard[2] = bad ? guard[2] + 1 : 0;
+            guard[3] += 1;
+        }
     }
 }
 // EMA: the averaged copy of the parameters (ema.hip) takes its update from the value this lane has just computed: ema[i] = ema_step(ema[i], p', ema_m), one
 // more read and one more write of a flat buffer instead of a launch that re-reads the parameters.  The plain instantiation is the kernel as it was.
-template <bool EMA>
+// GUARD: every workgroup reads the step's flag (one scalar load) and leaves before any store when the step is skipped.
+template <bool EMA, bool GUARD = false>
 __global__ void sgd_nesterov_kernel(float* p, const float* g, float* buf, long n, const float* coef_ptr, float gscale, float lr,
-                                    float momentum, float wd, int first_step, float* ema, float ema_m) {
+                                    float momentum, float wd, int first_step, float* ema, float ema_m, const int* guard = nullptr) {
+    if (GUARD) { if (guard[0] != 0) return; }
     const float coef = (coef_ptr ? coef_ptr[1] : 1.f) * gscale;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
         const float pv = p[i];
@@ -1405,9 +1418,11 @@ __global__ void sqsum_segments_kernel(const float* g, long n, const mvf_sgd_segm
 // the same update with per-SEGMENT learning-rate / weight-decay multipliers (build_optimizer's paramwise_options, reference
 // codes/core/train.py:117-156) and an optional plain-momentum form: seg[k] = {first element, lr multiplier, decay multiplier},
 // sorted by first element, seg[0].first == 0; a workgroup's 256-element run looks its segment up by binary search per element
-template <bool EMA>
+template <bool EMA, bool GUARD = false>
 __global__ void sgd_segments_kernel(float* p, const float* g, float* buf, long n, const float* coef_ptr, float gscale, float lr,
-                                    float momentum, float wd, int first_step, int nesterov, const mvf_sgd_segment_t* seg, int nseg, float* ema, float ema_m) {
+                                    float momentum, float wd, int first_step, int nesterov, const mvf_sgd_segment_t* seg, int nseg, float* ema, float ema_m,
+                                    const int* guard = nullptr) {
+    if (GUARD) { if (guard[0] != 0) return; }
     const float coef = (coef_ptr ? coef_ptr[1] : 1.f) * gscale;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
         const int lo = seg_of(seg, nseg, i);
@@ -1438,14 +1453,32 @@ int check_ema_arg(const char* who, const float* ema, float ema_m, const float* p
     return MVF_OK;
 }
 
-// clip + SGD on flat fp32 buffers (mvf_sgd_nesterov_step / mvf_sgd_step_segments below); EMA: the _ema twins
-template <bool EMA>
+// the counters handed to mvf_sgd_step_guarded: four ints, 4-byte aligned, disjoint from everything the step reads or writes
+int check_guard_arg(const char* who, const int* guard, const float* params, const float* grads, const float* buf, const float* ema, long n, const float* norm_out,
+                    const void* ws, size_t ws_bytes, const mvf_sgd_segment_t* seg, int nseg) {
+    MVF_REQUIRE(guard, MVF_EINVAL, "%s: NULL guard", who);
+    const uintptr_t pg = (uintptr_t)guard, len = (uintptr_t)n * 4;
+    MVF_REQUIRE(pg % 4 == 0, MVF_EINVAL, "%s: guard must be 4-byte aligned", who);
+    const uintptr_t other[7] = {(uintptr_t)params, (uintptr_t)grads, (uintptr_t)buf, (uintptr_t)ema, (uintptr_t)norm_out, (uintptr_t)ws, (uintptr_t)seg};
+    const uintptr_t bytes[7] = {len, len, len, len, 2 * sizeof(float), (uintptr_t)ws_bytes, seg ? (uintptr_t)nseg * sizeof(mvf_sgd_segment_t) : 0};
+    const char* names[7] = {"params", "grads", "momentum_buf", "ema", "norm_out", "the workspace", "the segment table"};
+    for (int k = 0; k < 7; ++k)
+        MVF_REQUIRE(!other[k] || pg + 16 <= other[k] || other[k] + bytes[k] <= pg, MVF_EINVAL, "%s: guard and %s overlap", who, names[k]);
+    return MVF_OK;
+}
+
+// clip + SGD on flat fp32 buffers (mvf_sgd_nesterov_step / mvf_sgd_step_segments below); EMA: the _ema twins; GUARD: mvf_sgd_step_guarded
+template <bool EMA, bool GUARD = false>
 int sgd_nesterov_step_impl(const char* who, float* params, const float* grads, float* momentum_buf, long n, float grad_scale, float max_norm, float lr,
                                   float momentum, float weight_decay, int first_step, float* ema, float ema_m, float* norm_out, void* ws, size_t ws_bytes,
-                                  void* stream) {
+                                  void* stream, int* guard = nullptr) {
     MVF_REQUIRE(params && grads && momentum_buf && norm_out && n > 0, MVF_EINVAL, "%s: bad argument", who);
     if (EMA) {
         const int rc = check_ema_arg(who, ema, ema_m, params, grads, momentum_buf, n);
+        if (rc != MVF_OK) return rc;
+    }
+    if (GUARD) {
+        const int rc = check_guard_arg(who, guard, params, grads, momentum_buf, EMA ? ema : nullptr, n, norm_out, ws, ws_bytes, nullptr, 0);
         if (rc != MVF_OK) return rc;
     }
     MVF_REQUIRE(ws && ws_bytes >= mvf_sgd_workspace_bytes(n), MVF_EWS, "%s: workspace too small", who);
@@ -1455,21 +1488,25 @@ int sgd_nesterov_step_impl(const char* who, float* params, const float* grads, f
     hipLaunchKernelGGL(sqsum_partial_kernel, dim3(nb), dim3(256), 0, st, grads, n, part);
     MVF_LAUNCH_CHECK();
     // the norm is of the scaled gradient (all-reduce sum / world happens before clipping, dist_utils.py:63-66)
-    hipLaunchKernelGGL(norm_finalize_kernel, dim3(1), dim3(64), 0, st, part, nb, max_norm, grad_scale, norm_out);
+    hipLaunchKernelGGL(norm_finalize_kernel<GUARD>, dim3(1), dim3(64), 0, st, part, nb, max_norm, grad_scale, norm_out, guard);
     MVF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sgd_nesterov_kernel<EMA>, dim3(grid_for(n)), dim3(256), 0, st, params, grads, momentum_buf, n, norm_out, grad_scale, lr, momentum, weight_decay,
-                       first_step, ema, ema_m);
+    hipLaunchKernelGGL((sgd_nesterov_kernel<EMA, GUARD>), dim3(grid_for(n)), dim3(256), 0, st, params, grads, momentum_buf, n, norm_out, grad_scale, lr, momentum,
+                       weight_decay, first_step, ema, ema_m, (const int*)guard);
     MVF_LAUNCH_CHECK();
     return MVF_OK;
 }
 
-template <bool EMA>
+template <bool EMA, bool GUARD = false>
 int sgd_step_segments_impl(const char* who, float* params, const float* grads, float* momentum_buf, long n, float grad_scale, float max_norm, float lr,
                                   float momentum, float weight_decay, int first_step, int nesterov, const mvf_sgd_segment_t* segments, int nseg, float* ema,
-                                  float ema_m, float* norm_out, void* ws, size_t ws_bytes, void* stream) {
+                                  float ema_m, float* norm_out, void* ws, size_t ws_bytes, void* stream, int* guard = nullptr) {
     MVF_REQUIRE(params && grads && momentum_buf && norm_out && segments && nseg > 0 && n > 0, MVF_EINVAL, "%s: bad argument", who);
     if (EMA) {
         const int rc = check_ema_arg(who, ema, ema_m, params, grads, momentum_buf, n);
+        if (rc != MVF_OK) return rc;
+    }
+    if (GUARD) {
+        const int rc = check_guard_arg(who, guard, params, grads, momentum_buf, EMA ? ema : nullptr, n, norm_out, ws, ws_bytes, segments, nseg);
         if (rc != MVF_OK) return rc;
     }
     MVF_REQUIRE(ws && ws_bytes >= mvf_sgd_workspace_bytes(n), MVF_EWS, "%s: workspace too small", who);
@@ -1478,10 +1515,10 @@ int sgd_step_segments_impl(const char* who, float* params, const float* grads, f
     const int nb = (int)std::min<long>((n + 255) / 256, 1024);
     hipLaunchKernelGGL(sqsum_segments_kernel, dim3(nb), dim3(256), 0, st, grads, n, segments, nseg, part);
     MVF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(norm_finalize_kernel, dim3(1), dim3(64), 0, st, part, nb, max_norm, grad_scale, norm_out);
+    hipLaunchKernelGGL(norm_finalize_kernel<GUARD>, dim3(1), dim3(64), 0, st, part, nb, max_norm, grad_scale, norm_out, guard);
     MVF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sgd_segments_kernel<EMA>, dim3(grid_for(n)), dim3(256), 0, st, params, grads, momentum_buf, n, norm_out, grad_scale, lr, momentum, weight_decay,
-                       first_step, nesterov, segments, nseg, ema, ema_m);
+    hipLaunchKernelGGL((sgd_segments_kernel<EMA, GUARD>), dim3(grid_for(n)), dim3(256), 0, st, params, grads, momentum_buf, n, norm_out, grad_scale, lr, momentum,
+                       weight_decay, first_step, nesterov, segments, nseg, ema, ema_m, (const int*)guard);
     MVF_LAUNCH_CHECK();
     return MVF_OK;
 }
@@ -2119,6 +2156,25 @@ int mvf_sgd_step_segments_ema(float* params, const float* grads, float* momentum
                               float* norm_out, void* ws, size_t ws_bytes, void* stream) {
     return sgd_step_segments_impl<true>("sgd_step_segments_ema", params, grads, momentum_buf, n, grad_scale, max_norm, lr, momentum, weight_decay, first_step, nesterov,
                                         segments, nseg, ema, ema_momentum, norm_out, ws, ws_bytes, stream);
+}
+
+// The four forms above behind the non-finite guard (mvfnet_hip.h): segments == NULL selects the flat Nesterov form, ema == NULL keeps no average.
+int mvf_sgd_step_guarded(float* params, const float* grads, float* momentum_buf, long n, float grad_scale, float max_norm, float lr, float momentum,
+                         float weight_decay, int first_step, int nesterov, const mvf_sgd_segment_t* segments, int nseg, float* ema, float ema_momentum,
+                         int* guard, float* norm_out, void* ws, size_t ws_bytes, void* stream) {
+    const char* who = "sgd_step_guarded";
+    if (!segments) {
+        if (ema)
+            return sgd_nesterov_step_impl<true, true>(who, params, grads, momentum_buf, n, grad_scale, max_norm, lr, momentum, weight_decay, first_step, ema,
+                                                      ema_momentum, norm_out, ws, ws_bytes, stream, guard);
+        return sgd_nesterov_step_impl<false, true>(who, params, grads, momentum_buf, n, grad_scale, max_norm, lr, momentum, weight_decay, first_step, nullptr, 0.f,
+                                                   norm_out, ws, ws_bytes, stream, guard);
+    }
+    if (ema)
+        return sgd_step_segments_impl<true, true>(who, params, grads, momentum_buf, n, grad_scale, max_norm, lr, momentum, weight_decay, first_step, nesterov,
+                                                  segments, nseg, ema, ema_momentum, norm_out, ws, ws_bytes, stream, guard);
+    return sgd_step_segments_impl<false, true>(who, params, grads, momentum_buf, n, grad_scale, max_norm, lr, momentum, weight_decay, first_step, nesterov, segments,
+                                               nseg, nullptr, 0.f, norm_out, ws, ws_bytes, stream, guard);
 }
 
 }  // extern "C"

@@ -25,6 +25,7 @@ import torch.distributed as dist
 from .checkpoint import load_checkpoint, save_checkpoint
 from .dist import get_dist_info, init_dist  # noqa: F401  (re-exported: train_recognizer.py imports init_dist from the core package)
 from .ema import check_ema, check_precise_bn
+from .guard import check_nonfinite_guard
 
 
 def set_random_seed(seed):
@@ -296,8 +297,14 @@ class Runner(object):
 
     def __init__(self, model, work_dir=None, lr=0.015, momentum=0.9, weight_decay=1e-4, max_norm=40.0, lr_steps=(90, 130),
                  warmup_iters=25070, warmup_ratio=0.01, ckpt_interval=10, log_interval=20, logger=print, optimizer=None, dtype=None,
-                 warmup="linear", lr_gamma=0.1, accumulate=1, ema=None, precise_bn=None):
-        """ema = dict(momentum=2e-4, warmup_steps=0) (either key may be left out): the engine keeps an exponential moving average of the parameters, one update
+                 warmup="linear", lr_gamma=0.1, accumulate=1, ema=None, precise_bn=None, nonfinite_guard=None):
+        """nonfinite_guard = dict(max_consecutive=100) (an empty dict gives the default): an optimizer step whose clip norm is not finite -- a NaN / inf in a
+        gradient, or a sum of squares beyond fp32 -- is skipped on the device and the BatchNorm statistics go back to before it (TrainEngine.enable_step_guard);
+        the counters are read where the loop synchronises anyway (the log interval, and always at epoch end): the log line gains `skipped N`, and
+        max_consecutive skipped steps in a row raise FloatingPointError -- nothing has been poisoned by then, the live state and the last checkpoint are both
+        usable.  `iter`, the learning-rate schedule and the EMA warm-up count ATTEMPTED steps, as a scheduler does under torch's GradScaler.  Checkpoints carry
+        the total as meta['skipped_steps'].
+        ema = dict(momentum=2e-4, warmup_steps=0) (either key may be left out): the engine keeps an exponential moving average of the parameters, one update
         per optimizer step inside the fused optimizer kernel (TrainEngine.enable_ema); checkpoints carry it as 'ema', hooks can score it (weights='ema').
         precise_bn = dict(num_iters=200, interval=1, weights='live' | 'ema' | 'both') (any key may be left out): an evaluation.PreciseBNHook over the loader this
         runner trains from recomputes the BatchNorm running statistics at epoch end, before the evaluation hooks ('ema' / 'both' need `ema`).
@@ -307,6 +314,7 @@ class Runner(object):
         self.accumulate = check_accumulate(accumulate)
         self.ema = check_ema(ema)                    # (refused before anything is built)
         self.precise_bn = check_precise_bn(precise_bn)
+        self.nonfinite_guard = check_nonfinite_guard(nonfinite_guard)
         if self.precise_bn is not None and self.precise_bn["weights"] != "live" and self.ema is None:
             raise ValueError("precise_bn: weights=%r needs averaged weights; set ema (ema_config) as well" % self.precise_bn["weights"])
         self.train_loader = None
@@ -329,6 +337,8 @@ class Runner(object):
         self.hooks = []               # objects with after_train_epoch(runner), e.g. evaluation.EvalTopKAccuracyHook
         if self.ema is not None:
             self.engine.enable_ema(**self.ema)
+        if self.nonfinite_guard is not None:
+            self.engine.enable_step_guard()
         if self.precise_bn is not None:
             from .evaluation import PreciseBNHook
             self.register_hook(PreciseBNHook(None, **self.precise_bn))
@@ -345,13 +355,28 @@ class Runner(object):
     def current_lr(self):
         return step_lr(self.base_lr, self.epoch, self.iter, self.lr_steps, self.lr_gamma, self.warmup, self.warmup_iters, self.warmup_ratio)
 
+    def _check_guard(self):
+        """Read the step guard's counters (a synchronising 16-byte read: called only where the loop synchronises anyway).  Returns ' skipped N' for the log
+        line; raises once max_consecutive optimizer steps in a row have been skipped."""
+        if self.nonfinite_guard is None:
+            return ""
+        st = self.engine.guard_state()
+        if st["consecutive"] >= self.nonfinite_guard["max_consecutive"]:
+            raise FloatingPointError(
+                "non-finite gradient norm in %d consecutive optimizer steps (max_consecutive=%d), seen between iter %d and iter %d of epoch %d; every one was "
+                "skipped on the device: parameters, optimizer state, averaged weights and BatchNorm statistics are those of the last good step"
+                % (st["consecutive"], self.nonfinite_guard["max_consecutive"], self.iter - st["consecutive"] + 1, self.iter, self.epoch + 1))
+        return " skipped %d" % st["skipped"]
+
     def _apply_accumulated(self, rank):
         lr = self.current_lr()
         self.engine.apply_accumulated(lr=lr)
         self.iter += 1
-        if rank == 0 and self.log_interval and self.iter % self.log_interval == 0:
-            self.log("Epoch [%d] iter %d lr %.5f loss_cls %.4f grad_norm %.3f" % (
-                self.epoch + 1, self.iter, lr, float(self.engine.accumulated_loss), float(self.engine.norm_out[0])))
+        if self.log_interval and self.iter % self.log_interval == 0:
+            note = self._check_guard()               # on every rank: all of them take the same decisions, so all of them stop together
+            if rank == 0:
+                self.log("Epoch [%d] iter %d lr %.5f loss_cls %.4f grad_norm %.3f%s" % (
+                    self.epoch + 1, self.iter, lr, float(self.engine.accumulated_loss), float(self.engine.norm_out[0]), note))
 
     def _train_epoch_accumulated(self, loader, rank):
         """One micro-step per loader batch; the optimizer runs after every k-th batch and after the epoch's last one (a shorter trailing group is applied
@@ -377,9 +402,12 @@ class Runner(object):
             lr = self.current_lr()
             loss = self.engine.train_step(data["img_group"], data["label"], lr=lr)
             self.iter += 1
-            if rank == 0 and self.log_interval and self.iter % self.log_interval == 0:
-                self.log("Epoch [%d] iter %d lr %.5f loss_cls %.4f grad_norm %.3f" % (
-                    self.epoch + 1, self.iter, lr, float(loss), float(self.engine.norm_out[0])))
+            if self.log_interval and self.iter % self.log_interval == 0:
+                note = self._check_guard()           # on every rank: all of them take the same decisions, so all of them stop together
+                if rank == 0:
+                    self.log("Epoch [%d] iter %d lr %.5f loss_cls %.4f grad_norm %.3f%s" % (
+                        self.epoch + 1, self.iter, lr, float(loss), float(self.engine.norm_out[0]), note))
+        self._check_guard()                          # always at epoch end, before a checkpoint is written
         self.epoch += 1
         if rank == 0 and self.work_dir and self.ckpt_interval and self.epoch % self.ckpt_interval == 0:
             self.save_checkpoint()
@@ -401,7 +429,10 @@ class Runner(object):
         state_dict layout (reference checkpoint.py:235-265, mmcv CheckpointHook)."""
         path = os.path.join(self.work_dir, "epoch_%d.pth" % self.epoch)
         self.engine.lr = self.current_lr()
-        save_checkpoint(self.model, path, optimizer=self.engine.optimizer_state_dict(), meta=dict(epoch=self.epoch, iter=self.iter),
+        meta = dict(epoch=self.epoch, iter=self.iter)
+        if self.nonfinite_guard is not None:
+            meta["skipped_steps"] = self.engine.guard_state()["skipped"]
+        save_checkpoint(self.model, path, optimizer=self.engine.optimizer_state_dict(), meta=meta,
                         ema=self.engine.ema_state_dict() if self.engine.flat_ema is not None else None)
         latest = os.path.join(self.work_dir, "latest.pth")
         if os.path.lexists(latest):
@@ -415,6 +446,8 @@ class Runner(object):
         ckpt = load_checkpoint(self.model, filename, strict=True)
         meta = ckpt.get("meta", {})
         self.epoch, self.iter = meta.get("epoch", 0), meta.get("iter", 0)
+        if self.nonfinite_guard is not None and "skipped_steps" in meta:      # (checkpoints without it load as before)
+            self.engine.set_skipped_steps(meta["skipped_steps"])
         opt = ckpt.get("optimizer")
         if opt:
             lr, mom, wd = self.engine.lr, self.engine.momentum, self.engine.weight_decay
@@ -452,6 +485,7 @@ def train_network(model, dataset, cfg, distributed=False, validate=False, logger
     checkpoints from cfg.checkpoint_config, logging interval from cfg.log_config, optional fp16 section, resume_from /
     load_from, then run cfg.total_epochs.  cfg.ema_config = dict(momentum=..., warmup_steps=...) keeps averaged weights (Runner(ema=...)).
     cfg.precise_bn = dict(num_iters=..., interval=..., weights=...) recomputes the BatchNorm running statistics at epoch end (Runner(precise_bn=...)).
+    cfg.nonfinite_guard = dict(max_consecutive=100) skips optimizer steps with a non-finite gradient norm on the device (Runner(nonfinite_guard=...)).
     cfg.optimizer_config.accumulate = k (an integer >= 1, default 1) makes one optimizer step of k loader batches
     (gradient accumulation, Runner(accumulate=k)).  `dataset`: a torch Dataset of dict(img_group, label) items, a ready loader, or an
     iterable of batches (or a list whose first entry is the training one).  `validate` registers the reference's
@@ -460,6 +494,7 @@ def train_network(model, dataset, cfg, distributed=False, validate=False, logger
     accumulate = check_accumulate(_cfg_get(cfg.get("optimizer_config") or {}, "accumulate", 1))      # (refused before anything is built)
     ema = check_ema(cfg.get("ema_config"))
     precise_bn = check_precise_bn(cfg.get("precise_bn"))
+    nonfinite_guard = check_nonfinite_guard(cfg.get("nonfinite_guard"))
     if precise_bn is not None and precise_bn["weights"] != "live" and ema is None:
         raise ValueError("precise_bn: weights=%r needs averaged weights; set ema_config as well" % precise_bn["weights"])
     log = (logger.info if logger is not None and hasattr(logger, "info") else (logger or print))
@@ -487,7 +522,8 @@ def train_network(model, dataset, cfg, distributed=False, validate=False, logger
                     lr_steps=[steps] if isinstance(steps, int) else tuple(steps), warmup=_cfg_get(lrc, "warmup"),
                     warmup_iters=_cfg_get(lrc, "warmup_iters", 0), warmup_ratio=_cfg_get(lrc, "warmup_ratio", 0.1),
                     lr_gamma=_cfg_get(lrc, "gamma", 0.1), ckpt_interval=_cfg_get(ck, "interval", 0) or 0,
-                    log_interval=_cfg_get(lg, "interval", 0) or 0, logger=log, optimizer=optimizer, accumulate=accumulate, ema=ema, precise_bn=precise_bn)
+                    log_interval=_cfg_get(lg, "interval", 0) or 0, logger=log, optimizer=optimizer, accumulate=accumulate, ema=ema, precise_bn=precise_bn,
+                    nonfinite_guard=nonfinite_guard)
     if clip and _cfg_get(clip, "norm_type", 2) != 2:
         raise NotImplementedError("grad_clip norm_type %r: the fused clip is the L2 norm" % _cfg_get(clip, "norm_type"))
     if validate:

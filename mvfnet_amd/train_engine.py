@@ -1364,7 +1364,9 @@ class _ParamStore(object):
         if not flat:
             tab, nseg = self._segments(off)
             args += (int(self.nesterov), _p(tab), nseg)
-        if self.flat_ema is None:
+        if self._guard is not None:
+            self._apply_sgd_guarded(args, tail, flat, off)
+        elif self.flat_ema is None:
             check((lib.mvf_sgd_nesterov_step if flat else lib.mvf_sgd_step_segments)(*(args + tail)), "sgd step")
         else:
             # the averaged copy moves in the kernel that stores the new parameters; the step's momentum travels by value (the optimizer runs outside the launch plans)
@@ -1373,6 +1375,25 @@ class _ParamStore(object):
             self.ema_updates += 1
         self.steps += 1
         return self.norm_out
+
+    _guard = None      # non-finite step guard (TrainEngine.enable_step_guard): None = off, the launches above are all there is
+
+    def _apply_sgd_guarded(self, args, tail, flat, off):
+        """The optimizer behind the non-finite guard: mvf_sgd_step_guarded (all four forms), then the conditional restore of the BatchNorm statistics."""
+        g = self._guard
+        if flat:
+            args += (0, None, 0)
+        if self.flat_ema is None:
+            ema = (None, C.c_float(0.0))
+        else:
+            ema = (_p(self.flat_ema[off:]), C.c_float(_ema_momentum_at(self.ema_momentum, self.ema_warmup_steps, self.ema_updates)))
+            self.ema_updates += 1
+        check(lib.mvf_sgd_step_guarded(*(args + ema + (_p(g["buf"]),) + tail)), "sgd step (guarded)")
+        snap, g["snap"] = g["snap"], None
+        if snap is not None:
+            tab, flat_stats = snap
+            check(lib.mvf_bn_stats_restore(_p(tab.dev), tab.nseg, tab.n, _p(flat_stats), _p(self._nbt_flat), self._nbt_flat.numel(), _p(g["nbt"]), _p(g["buf"]),
+                                           _st()), "bn stats restore")
 
     # ---- averaged weights: an exponential moving average of the parameters, one update per OPTIMIZER step ------------------------------------------------
     # e' = fmaf(m_t, p' - e, e) in fp32 (csrc/common.h ema_step), m_t = ema.momentum_at(momentum, warmup_steps, t).  flat_ema is laid out like flat_params; the
@@ -1669,6 +1690,8 @@ class TrainEngine(_ParamStore):
         if self._ema_swapped:
             self._ema_live("a training forward")
         self._main = torch.cuda.current_stream()
+        if self._guard is not None:
+            self._guard_snapshot()               # (the autograd path; train_step / accumulate_step have taken it already)
         self.forward_count += 1
         with _on_stream(self._main, main=True):
             return self._forward(imgs, labels, stages, _prepared)
@@ -2017,6 +2040,8 @@ class TrainEngine(_ParamStore):
         recorded by train_step carries the tail bucket's collective, which a micro-step must not issue -- those micro-steps run eagerly, never from a plan."""
         if self._ema_swapped:
             self._ema_live("a training step")
+        if self._guard is not None:
+            self._guard_snapshot()               # before the plan-or-eager branch: never inside a recorded region
         key = self._plan_key(imgs, labels) if imgs.is_cuda else None
         if not exchange and self._ddp_active():
             key = None
@@ -2050,6 +2075,69 @@ class TrainEngine(_ParamStore):
             else:
                 st["cand"] = cand
         return loss
+
+    # ---- non-finite step guard: a step whose clip norm is not finite is skipped on the device, the BatchNorm statistics go back ----------------------------
+    # One NaN pixel, a loss spike or a bf16 overflow otherwise ends a run for good: coef = max_norm / (nan + 1e-6) reaches every parameter, every momentum
+    # element and the averaged weights, and the forward has folded NaN batch statistics into every running mean and variance before the optimizer even starts.
+    # With the guard on, the lane that finishes the clip norm (norm_finalize_kernel) sets a flag in device memory when the scaled norm is not finite -- a NaN
+    # or inf anywhere in a gradient that enters the norm, or a sum of squares beyond fp32: SKIPPED as well --, the update kernel returns before any store, and
+    # one launch puts the running statistics and num_batches_tracked of every BatchNorm in training mode back to the snapshot taken before the step's first
+    # forward (under accumulation: before the group's first micro-step, so one poisoned micro-batch drops the whole group).  After a skipped step the model,
+    # the optimizer state and the average are what they were before it: the run continues as if the batch had never been drawn.  Nothing is read back: the
+    # host cannot know, so its counters (steps, ema_updates, the runner's iter, hence learning-rate and EMA warm-up schedules) count ATTEMPTED steps, as a
+    # scheduler does under torch's GradScaler; a skipped step still draws its dropout mask and blending table.  A skipped very first step is harmless: the
+    # momentum buffer is still zero and momentum * 0 + d is first_step's d (signs of zero may differ).  Under a process group the norm is taken after the
+    # all-reduce, so every rank takes the same decision and rolls back its own statistics: no collective is added.  guard_state() is the one call that
+    # synchronises.  Not covered: an external torch optimizer (attach_grads) and update_ema() behind one.  An engine that never enables the guard allocates
+    # and launches exactly what it did without it.
+    def enable_step_guard(self):
+        """Start guarding: counters at zero.  The guard buffer, the snapshot arrays and the int64 copy are allocations of their own (no recorded plan holds
+        their addresses, and they are not part of any plan key)."""
+        if self._guard is None:
+            self._guard = dict(buf=torch.zeros(4, dtype=torch.int32, device=self.device), nbt=torch.empty_like(self._nbt_flat), snap=None, tables={}, hold=False)
+
+    def disable_step_guard(self):
+        self._guard = None
+
+    def guard_state(self):
+        """dict(skipped_last, skipped, consecutive, steps): whether the last optimizer step was skipped, skipped steps in total, the current run of
+        consecutive skips, optimizer steps seen.  A 16-byte read that waits for the device: the only synchronising call of the guard."""
+        if self._guard is None:
+            raise RuntimeError("guard_state: the non-finite step guard is off; call enable_step_guard() (Runner(nonfinite_guard=...), cfg.nonfinite_guard) first")
+        last, skipped, run, steps = self._guard["buf"].tolist()
+        return dict(skipped_last=bool(last), skipped=int(skipped), consecutive=int(run), steps=int(steps))
+
+    def set_skipped_steps(self, total):
+        """The total a resumed run continues counting from (a checkpoint's meta['skipped_steps'])."""
+        if self._guard is None:
+            raise RuntimeError("set_skipped_steps: the non-finite step guard is off")
+        self._guard["buf"][1:2].fill_(int(total))
+
+    def _guard_snapshot(self):
+        """Once per optimizer step, before the first forward that follows one: the running statistics of every BatchNorm in training mode (what precise_bn
+        would calibrate, MVF's BatchNorm3d included) and all num_batches_tracked counters, one launch on the launch stream."""
+        g = self._guard
+        if g["snap"] is not None or g["hold"]:
+            return
+        pattern = tuple(m_.training for m_ in self._nbt_mods)
+        ent = g["tables"].get(pattern)
+        if ent is None:
+            bns = [b for b in self._all_bns() if not b.frozen]
+            if bns:
+                tab = self._stat_table(bns)
+                flat = torch.empty(tab.n, dtype=torch.float32, device=self.device)
+                with _on_stream(torch.cuda.current_stream()):
+                    tab.exchange(flat, 0)        # the ONE host-side validation of the table's content: snapshot / restore never read it back
+                ent = (tab, flat)
+            else:
+                ent = ()                         # every BatchNorm frozen: no statistic moves, nothing to put back
+            g["tables"][pattern] = ent
+        if not ent:
+            return
+        tab, flat = ent
+        check(lib.mvf_bn_stats_snapshot(_p(tab.dev), tab.nseg, tab.n, _p(flat), _p(self._nbt_flat), self._nbt_flat.numel(), _p(g["nbt"]),
+                                        C.c_void_p(torch.cuda.current_stream().cuda_stream)), "bn stats snapshot")
+        g["snap"] = ent
 
     # ---- gradient accumulation: one optimizer step over k micro-batches (the reference's 8 ranks x 12 clips run one after another on one GPU) ------------
     # Micro-batch i's forward + backward leave g_i in flat_grads (the gradient of ITS mean loss under ITS OWN BatchNorm batch statistics: exactly what rank i of
@@ -2203,6 +2291,8 @@ class TrainEngine(_ParamStore):
         state = [(b, b.momentum) for b in bns], self.blending, self.dropout
         tab.acc.zero_()
         used, done, swapped = 0, False, False
+        if self._guard is not None:
+            self._guard["hold"] = True           # calibration forwards neither take nor consume the step guard's snapshot
         try:
             if ema:
                 with on():
@@ -2242,6 +2332,8 @@ class TrainEngine(_ParamStore):
             self._nbt_touched = False
             self.saved = None
             self._invalidate_inference()
+            if self._guard is not None:
+                self._guard["hold"] = False
         return used
 
     def train_step_accumulated(self, batches, lr=None):
