@@ -177,15 +177,16 @@ struct SkArgs {            // stream-K tail (see launch_conv): G workgroups shar
 // gives 3.1e-7).  gfx950's bf16 matrix rate is 16 x its fp32 matrix rate (2.5 PF/s vs 157 TF/s), so six bf16 instructions per k-step cost
 // 6 / 16 of the fp32 instruction they replace: 2.67 x the matrix throughput at fp32 accuracy.
 template <typename ET, int WM, int WN, int TM, int TN, bool LOWK = false, bool PF2 = false, bool GEN = false, int EPI = 0, bool PW = false, int GLDS = 0,
-          bool MVFL = false, bool ILV = false, bool HALFK = false, bool X3 = false>
+          bool MVFL = false, bool HALFK = false, bool X3 = false>
 __device__ __forceinline__ void conv_tile(const ConvArgs& a, char* smem, const int tile, const int c_begin, const int c_end,
                                           const int mode, const SkArgs& sk, const int g_first, const int g_self) {
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
-    static_assert(BM == kBM || (BM == 2 * kBM && (GLDS >= 2 || X3)), "BM is 128 (256 for the 8-wave LDS-DMA tiles and the 8-wave X3 tile)");
-    static_assert(WM * WN == 4 || (WM * WN == 8 && (GLDS >= 2 || X3)), "4 waves (8 for the LDS-DMA experiments and the X3 tile)");
+    static_assert(GLDS == 0 || GLDS == 1 || GLDS == 2 || GLDS == 4, "register-staged, one or two LDS-DMA buffers, or the four-phase loop");
+    static_assert(BM == kBM || (BM == 2 * kBM && BN == 2 * kBM && (GLDS == 2 || GLDS == 4)), "BM is 128 (256 for the 256 x 256 LDS-DMA tile)");
+    static_assert((WM * WN == 8) == (BM == 2 * kBM), "4 waves (8 for the 256 x 256 tile: the two-buffer LDS-DMA loop and the four-phase loop)");
     // P4 = the four-phase ping-pong main loop (see the loop itself): 2 x 4 waves of 128 x 64 outputs on a 256 x 256 tile
     constexpr bool P4 = GLDS == 4;
-    static_assert(!P4 || (WM == 2 && WN == 4 && TM == 4 && TN == 2 && sizeof(ET) == 2 && !MVFL && !ILV && !HALFK), "the four-phase loop is written for the bf16 256 x 256 tile");
+    static_assert(!P4 || (WM == 2 && WN == 4 && TM == 4 && TN == 2 && sizeof(ET) == 2 && !MVFL && !HALFK), "the four-phase loop is written for the bf16 256 x 256 tile");
     constexpr int NT = WM * WN * 64;        // threads per workgroup
     constexpr int RP = NT / 8;              // rows per loader pass (8 lanes x 16 B per row)
     constexpr int ESZ = TT<ET>::ESZ, UE = TT<ET>::UE, CE = TT<ET>::CE;
@@ -197,13 +198,12 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, char* smem, const i
     __syncthreads();                                   // LDS hand-over from a previous segment of this workgroup
     static_assert(!GLDS || (!GEN && !PF2 && !LOWK), "the LDS-DMA loop is its own variant");
     static_assert(!MVFL || (((LOWK && PW) || GLDS == 1 || GLDS == 2) && !GEN), "the fused MVF loader: single-buffer register-staged pointwise kernel or the 4-wave LDS-DMA kernels");
-    static_assert(!ILV || (GLDS == 2 && !MVFL), "interleaved DMA issue: the two-buffer LDS-DMA loop");
     constexpr int NBUF = P4 ? 2 : (GLDS ? GLDS : (LOWK ? 1 : 2));
-    static_assert(!X3 || (sizeof(ET) == 4 && !GLDS && !MVFL && !PF2), "X3: fp32 storage, register-staged kernels (single- or double-buffered)");
+    static_assert(!X3 || (sizeof(ET) == 4 && LOWK && !GLDS && !MVFL && !PF2), "X3: fp32 storage, the single-buffer register-staged kernel");
     // X3: a chunk row is 32 channels = 64 bytes per bf16 plane, three planes per tile; unpadded rows, 16-byte units XOR-swizzled by the row
     // (unit u of row r at u ^ ((r >> 2) & 3): the 16 rows a ds_read_b128 service group reads fall on 16 distinct 16-byte bank slots)
     constexpr int PITCH = X3 ? 64 : (GLDS ? 128 : kPitch);         // LDS-DMA rows are unpadded (lane-linear destination)
-    constexpr int kSmem = X3 ? (LOWK ? kLowkLdsX3<BM, BN>() : 2 * (BM + BN) * 192) : (GLDS ? kGldsLds<BM, BN, GLDS ? NBUF : 1>() : (LOWK ? kLowkLds<BM, BN>() : 2 * (BM + BN) * kPitch));
+    constexpr int kSmem = X3 ? kLowkLdsX3<BM, BN>() : (GLDS ? kGldsLds<BM, BN, GLDS ? NBUF : 1>() : (LOWK ? kLowkLds<BM, BN>() : 2 * (BM + BN) * kPitch));
     constexpr int NPL = X3 ? 3 : 1;                    // operand planes per tile
     char* As = smem;                                   // [NBUF][NPL][BM][PITCH]
     char* Bs = smem + NBUF * NPL * BM * PITCH;         // [NBUF][NPL][BN][PITCH]
@@ -503,38 +503,6 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, char* smem, const i
         }
         advance();
     };
-    // ILV: the next chunk's DMA pieces are issued BETWEEN the MFMAs of the current chunk's first k-step instead of in a block
-    // before them: a wave's VMEM issue (60-185 cycles per LDS-DMA piece in a loaded phase) then hides under the 32-cycle matrix
-    // instructions already in the pipe -- with one workgroup per CU (the 256 x 256 tile) the two waves of a SIMD run in lockstep,
-    // so a DMA block ahead of the MFMAs leaves the matrix pipe idle for its whole length.  prep_chunk() does the offset
-    // arithmetic of load_chunk() for the chunk at (cc, kh, kw) and advances; issue_piece(n) issues piece n of it.
-    unsigned pv[A_ROWS_PT + B_ROWS_PT];
-    unsigned p_lds_a = 0, p_lds_b = 0;
-    bool p_from2 = false;
-    auto prep_chunk = [&](int buf) {
-        const int ci = cc * CE + q * UE;
-        const unsigned cbad = ci < a.Cin ? 0u : kOOB;
-        p_from2 = (a.split_c > 0) && (cc * CE < a.split_c);
-        const int ps = p_from2 ? a.x2ps : a.xps;
-        const unsigned toff = (unsigned)((kh * a.W + kw) * ps + cc * CE - (p_from2 ? 0 : a.x_c0)) * ESZ;
-#pragma unroll
-        for (int i = 0; i < A_ROWS_PT; ++i) {
-            const bool ok = ((hmask[i] >> kh) & (wmask[i] >> kw) & 1u) != 0u;
-            pv[i] = ok ? (((p_from2 ? a_off2[i] : a_off[i]) + toff) | cbad) : kOOB;
-        }
-        const unsigned koff = (unsigned)(((a.w_kh0 + kh * a.w_ts) * a.w_kwfull + (a.w_kw0 + kw * a.w_ts)) * a.Cin + cc * CE) * ESZ;
-#pragma unroll
-        for (int i = 0; i < B_ROWS_PT; ++i) pv[A_ROWS_PT + i] = (b_off[i] + koff) | cbad;
-        p_lds_a = lds_a0 + (unsigned)(buf * BM * PITCH);
-        p_lds_b = lds_b0 + (unsigned)(buf * BN * PITCH);
-        advance();
-    };
-    auto issue_piece = [&](int n) {
-        if constexpr (GLDS > 0) {
-            if (n < A_ROWS_PT) glds16(p_from2 ? gs_x2 : gs_x, p_lds_a + (unsigned)(RP * n * PITCH), pv[n]);
-            else glds16(gs_w, p_lds_b + (unsigned)(RP * (n - A_ROWS_PT) * PITCH), pv[n]);
-        }
-    };
     // X3: hi / mid / lo bf16 terms of four fp32 values (exact: x - bf16(x) is representable, twice), packed 4 x bf16 = 8 bytes per plane
     auto split3 = [&](const uint4& v, uint2 (&pl)[3]) {
         float r[4] = {__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w)};
@@ -609,8 +577,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, char* smem, const i
     // FPIPE: the operand fragments of k-step ks+2 are fetched from LDS behind the MFMAs of k-step ks (two fragment register
     // sets), so the ds_read round trip is exposed once per chunk instead of once per k-step
     constexpr bool FPIPE = GLDS != 0;
-    auto compute = [&](int buf, bool ilv_more = false) {
-        (void)ilv_more;
+    auto compute = [&](int buf) {
         if constexpr (X3) {
             // two k-steps of 16 channels; lane (row = lane & 31, half = lane >> 5) reads unit 2 * ks + half of its row in each plane
             const int fr = lane & 31, fx = (fr >> 2) & 3;          // (fragment rows are multiples of 32 apart: the XOR only depends on lane & 31)
@@ -656,8 +623,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, char* smem, const i
 #pragma unroll
             for (int j = 0; j < TN; ++j) fb[j] = *reinterpret_cast<const uint4*>(Bb + j * 32 * PITCH + ko);
         };
-        auto mma = [&](const uint4 (&fa)[TM], const uint4 (&fb)[TN], int piece0 = -1) {
-            (void)piece0;
+        auto mma = [&](const uint4 (&fa)[TM], const uint4 (&fb)[TN]) {
             if constexpr (ESZ == 4) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
@@ -678,13 +644,6 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, char* smem, const i
                         __builtin_memcpy(&av, &fa[i], 16);
                         __builtin_memcpy(&bv, &fb[j], 16);
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bv, av, acc[i][j], 0, 0, 0);
-                        if constexpr (ILV) {                   // one DMA piece of the next chunk behind each matrix instruction
-                            if (piece0 >= 0 && piece0 + i * TN + j < A_ROWS_PT + B_ROWS_PT) {
-                                __builtin_amdgcn_sched_barrier(0);
-                                issue_piece(piece0 + i * TN + j);
-                                __builtin_amdgcn_sched_barrier(0);
-                            }
-                        }
                     }
             }
         };
@@ -701,11 +660,11 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, char* smem, const i
                 return;
             }
             __builtin_amdgcn_sched_barrier(0);
-            mma(fa0, fb0, ilv_more ? 0 : -1);
+            mma(fa0, fb0);
             __builtin_amdgcn_sched_barrier(0);
             fetch(2, fa0, fb0);
             __builtin_amdgcn_sched_barrier(0);
-            mma(fa1, fb1, ilv_more ? TM * TN : -1);
+            mma(fa1, fb1);
             __builtin_amdgcn_sched_barrier(0);
             fetch(3, fa1, fb1);
             __builtin_amdgcn_sched_barrier(0);
@@ -737,25 +696,6 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, char* smem, const i
 #endif
             __syncthreads();
         }
-    } else if constexpr (GLDS == 3) {
-        // three buffers, two chunks in flight: chunk kc+2 is issued as soon as every wave is past chunk kc-1 (whose buffer it
-        // takes), and the wait at the top leaves the DMAs of chunk kc+1 outstanding (a counted vmcnt: the statements are asm,
-        // so the count is this loop's own bookkeeping -- A_ROWS_PT + B_ROWS_PT DMAs per chunk per thread)
-        constexpr int kPerChunk = A_ROWS_PT + B_ROWS_PT;
-        static_assert(kPerChunk == 6, "the counted wait below is written for 6 DMAs per chunk");
-        if (nseg > 0) load_chunk(s0, 0);
-        if (nseg > 1) load_chunk(s0, 1);
-        int bcur = 0, bnext = 2;
-        for (int kc = 0; kc < nseg; ++kc) {
-            if (kc + 1 < nseg) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();                           // (hipcc does not know of the DMAs: this is a bare barrier + lgkmcnt)
-            if (kc + 2 < nseg) load_chunk(s0, bnext);
-            compute(bcur);
-            bcur = bcur == 2 ? 0 : bcur + 1;
-            bnext = bnext == 2 ? 0 : bnext + 1;
-        }
-        __syncthreads();
     } else if constexpr (GLDS == 4) {
         // ---- four-phase ping-pong loop (tools/probes/gemm8p_probe.hip VAR 3: the matrix pipe issues 99 % of the loop's cycles) ----------------
         // The 8 waves are two groups (wave rows wm = 0 / 1: one wave of each on every SIMD) running ONE BARRIER APART: while a group issues the
@@ -899,8 +839,8 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, char* smem, const i
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the zero-fill DMAs of the tail must not land in the epilogue's C tile
         __syncthreads();
 #undef MVF_PIN2
-    } else if constexpr (GLDS >= 2) {
-        // GLDS buffers: chunk kc+GLDS-1 is in flight while chunk kc is multiplied; one barrier per chunk
+    } else if constexpr (GLDS == 2) {
+        // two buffers: chunk kc+1 is in flight while chunk kc is multiplied; one barrier per chunk
         if (nseg > 0) load_chunk(s0, 0);
         for (int kc = 0; kc < nseg; ++kc) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -909,14 +849,8 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, char* smem, const i
             if (kc + 1 < nseg && !(a.prio & 4)) load_chunk(s0, (kc + 1) & 1);      // ablation: bit 2 = no loads, bit 1 = no MFMAs
             if (!(a.prio & 2)) compute(kc & 1);
 #else
-            if constexpr (ILV) {
-                const bool more = kc + 1 < nseg;
-                if (more) prep_chunk((kc + 1) & 1);
-                compute(kc & 1, more);
-            } else {
-                if (kc + 1 < nseg) load_chunk(s0, (kc + 1) & 1);
-                compute(kc & 1);
-            }
+            if (kc + 1 < nseg) load_chunk(s0, (kc + 1) & 1);
+            compute(kc & 1);
 #endif
         }
         __syncthreads();
@@ -1472,7 +1406,7 @@ template <int WM, int WN, int TM, int TN, int EPI = 0, bool PW = false>
 __global__ __launch_bounds__(kThreads, 3) void conv_igemm_x3_kernel(ConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     SkArgs sk = {};
-    conv_tile<float, WM, WN, TM, TN, true, false, false, EPI, PW, 0, false, false, false, true>(a, smem, xcd_swizzle(blockIdx.x, gridDim.x), 0, a.nchunks, SEG_FULL, sk, 0, 0);
+    conv_tile<float, WM, WN, TM, TN, true, false, false, EPI, PW, 0, false, false, true>(a, smem, xcd_swizzle(blockIdx.x, gridDim.x), 0, a.nchunks, SEG_FULL, sk, 0, 0);
 }
 
 // LDS-DMA staged variant for the long-K (matrix-core bound) launches
@@ -1483,58 +1417,74 @@ template <typename ET, int WM, int WN, int TM, int TN, int EPI, int NB, bool MVF
 __global__ __launch_bounds__(kThreads, (NB == 1 && !MVFL) ? 4 : 1) void conv_igemm_glds_kernel(ConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     SkArgs sk = {};
-    conv_tile<ET, WM, WN, TM, TN, false, false, false, EPI, PW, NB, MVFL, false, HALFK>(a, smem, xcd_swizzle(blockIdx.x, gridDim.x), 0, a.nchunks, SEG_FULL, sk, 0, 0);
+    conv_tile<ET, WM, WN, TM, TN, false, false, false, EPI, PW, NB, MVFL, HALFK>(a, smem, xcd_swizzle(blockIdx.x, gridDim.x), 0, a.nchunks, SEG_FULL, sk, 0, 0);
 }
 
-// The long-K tile: 256 x 128 outputs per workgroup of 8 waves (4 x 2, 64 x 64 each), three 48 KB LDS-DMA buffers = one
-// workgroup per CU with two chunks (96 KB) in flight.  A 128 x 128 tile moves 32 KB per 2.1 MFLOP (64 FLOP/B); at the ~1.5 us
-// loaded latency the 64-96 KB a CU can keep in flight caps it near 700 TF/s whatever the staging (measured: register-staged
-// 3 workgroups/CU 650, LDS-DMA 2 x 2 buffers 700-750) -- this tile needs 2/3 of the bytes per flop and keeps 1.5x in flight.
-template <typename ET, int EPI>
-__global__ __launch_bounds__(512) void conv_igemm_big_kernel(ConvArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    SkArgs sk = {};
-    conv_tile<ET, 4, 2, 2, 2, false, false, false, EPI, false, 3>(a, smem, xcd_swizzle(blockIdx.x, gridDim.x), 0, a.nchunks, SEG_FULL, sk, 0, 0);
+// The epilogue specialisations (conv_tile EPI) and the pointwise loader (PW) are A/B-switched by policy conv_epi: bit 0 epilogues, bit 1 loader
+inline int conv_epi_spec() {
+    static const int v = mvf_policy_int("conv_epi", 3);
+    return v;
 }
 
-// experiment: the 128 x 128 two-buffer DMA tile computed by 8 waves (4 x 2, 32 x 64 each) -> 4 waves per SIMD at 2 workgroups/CU
-template <typename ET, int EPI>
-__global__ __launch_bounds__(512) void conv_igemm_glds8_kernel(ConvArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    SkArgs sk = {};
-    conv_tile<ET, 4, 2, 1, 2, false, false, false, EPI, false, 2>(a, smem, xcd_swizzle(blockIdx.x, gridDim.x), 0, a.nchunks, SEG_FULL, sk, 0, 0);
+// pointwise launches (1x1 taps, no padding, no split operand) take the loader specialisation PW: no tap masks, no second-operand
+// offsets and, at stride 1, no division in the per-tile set-up
+inline bool is_pointwise(const ConvArgs& a) {
+    return (conv_epi_spec() & 2) && a.KH == 1 && a.KW == 1 && a.pad == 0 && a.pad_w == 0 && a.split_c == 0 && a.dil <= 1;
+}
+
+inline bool infer_like(const ConvArgs& a, int epi_spec) { return (epi_spec & 1) && a.o_s <= 0 && a.bias && a.relu && !a.stats_part; }
+// contiguous or a scattered parity class ([r5] + an optional bias)
+inline bool bnsum_epi(const ConvArgs& a, int epi_spec) { return (epi_spec & 1) && a.bn_z && !a.relu && !a.res; }
+
+// The epilogue (conv_tile EPI) a launch asks for: the one place that ranks them.  A kernel family that does not instantiate the
+// answer runs the generic epilogue 0 instead (with_epi), which computes the same from the run-time arguments.
+int conv_epi_of(const ConvArgs& a, int epi_spec) {
+    const bool train_like = (epi_spec & 1) && a.o_s <= 0 && !a.bias && !a.relu;
+    if (a.ap_scale) return 8;
+    if (a.bw_mode == 9 || a.bw_mode == 10) return a.bw_mode;
+    if (train_like && a.stats_part && !a.res && !a.bn_z) return 1;
+    if (bnsum_epi(a, epi_spec)) return 6;
+    if (train_like && !a.stats_part && !a.res) return 2;
+    if (train_like && !a.stats_part && a.res) return 3;
+    if (train_like && a.stats_part && a.res && a.out_gate && !a.bn_z) return 12;
+    if (infer_like(a, epi_spec)) return a.res ? 5 : 4;
+    return 0;
+}
+
+// f(std::integral_constant<int, E>) for the E of the list that equals epi, f(0) when the list does not have it
+template <int... E, class F>
+int with_epi(int epi, F&& f) {
+    int rc = MVF_OK;
+    const bool hit = ((epi == E ? (rc = f(std::integral_constant<int, E>{}), true) : false) || ...);
+    return hit ? rc : f(std::integral_constant<int, 0>{});
 }
 
 // 256 x 256 outputs per workgroup of 8 waves (4 x 2, 64 x 128 each), two 64 KB LDS-DMA buffers, one workgroup per CU: per SIMD 16 DMA
-// instructions feed 2048 cycles of MFMA work per chunk -- twice the ratio of the 128 x 128 and 256 x 128 tiles, which plateau on the DMA
+// instructions feed 2048 cycles of MFMA work per chunk -- twice the ratio of the 128 x 128 tile, which plateaus on the DMA
 // issue path.  Only for launches whose tile count suits 256 single-workgroup slots (policy conv_big2).
-template <typename ET, int EPI, bool ILV>
+template <typename ET, int EPI>
 __global__ __launch_bounds__(512) void conv_igemm_big2_kernel(ConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     SkArgs sk = {};
-    conv_tile<ET, 4, 2, 2, 4, false, false, false, EPI, false, 2, false, ILV>(a, smem, xcd_swizzle(blockIdx.x, gridDim.x), 0, a.nchunks, SEG_FULL, sk, 0, 0);
+    conv_tile<ET, 4, 2, 2, 4, false, false, false, EPI, false, 2>(a, smem, xcd_swizzle(blockIdx.x, gridDim.x), 0, a.nchunks, SEG_FULL, sk, 0, 0);
 }
 
-template <typename ET, int EPI>
-int launch_big2(hipStream_t st, const ConvArgs& a0) {
+template <typename ET>
+int launch_big2(int epi, hipStream_t st, const ConvArgs& a0) {
     ConvArgs a = a0;
     a.tiles_m = (a.M + 255) / 256;
     a.tiles_n = (a.Cout + 255) / 256;
-    constexpr int lds = kGldsLds<256, 256, 2>();
-    // experiment switch policy conv_ilv=1: the next chunk's DMA pieces issued one behind each MFMA of the first k-step instead of in a block
-    // ahead of them.  Measured neutral on the K = 2304 launches and 6-8 % SLOWER on the K = 1024 ones (0.234 -> 0.25 ms): off.
-    static const int ilv = mvf_policy_int("conv_ilv", 0);
-    auto k0 = conv_igemm_big2_kernel<ET, EPI, false>;
-    auto k1 = conv_igemm_big2_kernel<ET, EPI, true>;
-    static bool attr = false;
-    if (!attr) {
-        MVF_HIP_OK(hipFuncSetAttribute((const void*)k0, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        MVF_HIP_OK(hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        attr = true;
-    }
-    if (ilv) hipLaunchKernelGGL(k1, dim3(a.tiles_m * a.tiles_n), dim3(512), lds, st, a);
-    else hipLaunchKernelGGL(k0, dim3(a.tiles_m * a.tiles_n), dim3(512), lds, st, a);
-    return MVF_OK;
+    return with_epi<1, 2, 3, 4, 5, 6>(epi, [&](auto e) -> int {
+        constexpr int lds = kGldsLds<256, 256, 2>();
+        auto k = conv_igemm_big2_kernel<ET, decltype(e)::value>;
+        static bool attr = false;
+        if (!attr) {
+            MVF_HIP_OK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+            attr = true;
+        }
+        hipLaunchKernelGGL(k, dim3(a.tiles_m * a.tiles_n), dim3(512), lds, st, a);
+        return MVF_OK;
+    });
 }
 
 // The 256 x 256 tile on the four-phase ping-pong loop (conv_tile GLDS = 4): 8 waves as 2 x 4 (128 x 64 outputs each), two 64 KB LDS-DMA
@@ -1546,110 +1496,63 @@ __global__ __launch_bounds__(512) void conv_igemm_p4_kernel(ConvArgs a) {
     conv_tile<ET, 2, 4, 4, 2, false, false, false, EPI, PW, 4>(a, smem, xcd_swizzle(blockIdx.x, gridDim.x), 0, a.nchunks, SEG_FULL, sk, 0, 0);
 }
 
-template <typename ET, int EPI>
-int launch_p4(hipStream_t st, const ConvArgs& a0) {
+template <typename ET>
+int launch_p4(int epi, hipStream_t st, const ConvArgs& a0) {
     if constexpr (sizeof(ET) != 2) {
         return MVF_EUNSUPPORTED;
     } else {
         ConvArgs a = a0;
         a.tiles_m = (a.M + 255) / 256;
         a.tiles_n = (a.Cout + 255) / 256;
-        constexpr int lds = kGldsLds<256, 256, 2>();
-        auto k0 = conv_igemm_p4_kernel<ET, EPI, false>;
-        auto k1 = conv_igemm_p4_kernel<ET, EPI, true>;
-        static bool attr = false;
-        if (!attr) {
-            MVF_HIP_OK(hipFuncSetAttribute((const void*)k0, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            MVF_HIP_OK(hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            attr = true;
-        }
-        const bool pw = a.KH == 1 && a.KW == 1 && a.pad == 0 && a.pad_w == 0 && a.split_c == 0 && a.dil <= 1;
-        if (pw) hipLaunchKernelGGL(k1, dim3(a.tiles_m * a.tiles_n), dim3(512), lds, st, a);
-        else hipLaunchKernelGGL(k0, dim3(a.tiles_m * a.tiles_n), dim3(512), lds, st, a);
-        return MVF_OK;
-    }
-}
-
-template <typename ET, int EPI>
-int launch_big(hipStream_t st, const ConvArgs& a0) {
-    ConvArgs a = a0;
-    a.tiles_m = (a.M + 255) / 256;
-    a.tiles_n = (a.Cout + 127) / 128;
-    auto k = conv_igemm_big_kernel<ET, EPI>;
-    constexpr int lds = kGldsLds<256, 128, 3>();
-    static bool attr = false;
-    if (!attr) {
-        MVF_HIP_OK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        attr = true;
-    }
-    hipLaunchKernelGGL(k, dim3(a.tiles_m * a.tiles_n), dim3(512), lds, st, a);
-    return MVF_OK;
-}
-
-template <typename ET, int WM, int WN, int TM, int TN, int EPI>
-int launch_glds(int nb, int tiles, hipStream_t st, const ConvArgs& a) {
-    constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
-    if constexpr (BM == 128 && BN == 128) {
-        if (nb == 3) {
-            auto k = conv_igemm_glds8_kernel<ET, EPI>;
-            constexpr int lds = kGldsLds<128, 128, 2>();
-            static bool attr8 = false;
-            if (!attr8) {
-                MVF_HIP_OK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-                attr8 = true;
+        return with_epi<1, 2, 3, 4, 5, 6>(epi, [&](auto e) -> int {
+            constexpr int EPI = decltype(e)::value, lds = kGldsLds<256, 256, 2>();
+            auto k0 = conv_igemm_p4_kernel<ET, EPI, false>;
+            auto k1 = conv_igemm_p4_kernel<ET, EPI, true>;
+            static bool attr = false;
+            if (!attr) {
+                MVF_HIP_OK(hipFuncSetAttribute((const void*)k0, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+                MVF_HIP_OK(hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+                attr = true;
             }
-            hipLaunchKernelGGL(k, dim3(tiles), dim3(512), lds, st, a);
+            hipLaunchKernelGGL(is_pointwise(a) ? k1 : k0, dim3(a.tiles_m * a.tiles_n), dim3(512), lds, st, a);
             return MVF_OK;
-        }
+        });
     }
-    // pointwise launches (1x1 taps, no padding, no split operand) take the loader specialisation PW: no tap masks, no second-operand
-    // offsets and, at stride 1, no division in the per-tile set-up (policy conv_epi bit 1, as for the register-staged kernel)
-    static const int epi_spec = mvf_policy_int("conv_epi", 3);
-    const bool pw = (epi_spec & 2) && a.KH == 1 && a.KW == 1 && a.pad == 0 && a.pad_w == 0 && a.split_c == 0 && a.dil <= 1;
-    if (nb == 1) {
-        constexpr int lds = kGldsLds<BM, BN, 1>();
-        if constexpr (BN == 64 && sizeof(ET) == 2 && (EPI == 1 || EPI == 4)) {       // the stem (training: + statistics; inference: bias + ReLU)
-            if (!pw && (size_t)a.Cin * sizeof(ET) <= 64 && a.split_c == 0) {
-                hipLaunchKernelGGL((conv_igemm_glds_kernel<ET, WM, WN, TM, TN, EPI, 1, false, false, true>), dim3(tiles), dim3(kThreads), lds, st, a);
-                return MVF_OK;
-            }
-        }
-        if (pw) hipLaunchKernelGGL((conv_igemm_glds_kernel<ET, WM, WN, TM, TN, EPI, 1, false, true>), dim3(tiles), dim3(kThreads), lds, st, a);
-        else hipLaunchKernelGGL((conv_igemm_glds_kernel<ET, WM, WN, TM, TN, EPI, 1>), dim3(tiles), dim3(kThreads), lds, st, a);
-    } else {
-        constexpr int lds = kGldsLds<BM, BN, 2>();
-        static bool attr = false;
-        if (!attr) {
-            MVF_HIP_OK(hipFuncSetAttribute((const void*)(conv_igemm_glds_kernel<ET, WM, WN, TM, TN, EPI, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            MVF_HIP_OK(hipFuncSetAttribute((const void*)(conv_igemm_glds_kernel<ET, WM, WN, TM, TN, EPI, 2, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            attr = true;
-        }
-        if (pw) hipLaunchKernelGGL((conv_igemm_glds_kernel<ET, WM, WN, TM, TN, EPI, 2, false, true>), dim3(tiles), dim3(kThreads), lds, st, a);
-        else hipLaunchKernelGGL((conv_igemm_glds_kernel<ET, WM, WN, TM, TN, EPI, 2>), dim3(tiles), dim3(kThreads), lds, st, a);
-    }
-    return MVF_OK;
 }
 
-// X3 on a 256 x 128 tile computed by 8 waves (4 x 2, 64 x 64 each): the per-chunk fixed costs of the single-buffer loop (two barriers, the
-// LDS round trips, the store phase) are paid once per 2 x the matrix work, and a workgroup keeps two waves on every SIMD
-template <int EPI = 0, bool PW = false>
-__global__ __launch_bounds__(512) void conv_igemm_x3w_kernel(ConvArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    SkArgs sk = {};
-    conv_tile<float, 4, 2, 2, 2, true, false, false, EPI, PW, 0, false, false, false, true>(a, smem, xcd_swizzle(blockIdx.x, gridDim.x), 0, a.nchunks, SEG_FULL, sk, 0, 0);
+// the 4-wave LDS-DMA kernels with nb = 1 or 2 buffers (anything but 1 means 2)
+template <typename ET, int WM, int WN, int TM, int TN>
+int launch_glds(int nb, int epi, int tiles, hipStream_t st, const ConvArgs& a) {
+    constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
+    const bool pw = is_pointwise(a);
+    return with_epi<1, 2, 3, 4, 5, 6, 8, 9, 10, 12>(epi, [&](auto e) -> int {
+        constexpr int EPI = decltype(e)::value;
+        if (nb == 1) {
+            constexpr int lds = kGldsLds<BM, BN, 1>();
+            if constexpr (BN == 64 && sizeof(ET) == 2 && (EPI == 1 || EPI == 4)) {       // the stem (training: + statistics; inference: bias + ReLU)
+                if (!pw && (size_t)a.Cin * sizeof(ET) <= 64 && a.split_c == 0) {
+                    hipLaunchKernelGGL((conv_igemm_glds_kernel<ET, WM, WN, TM, TN, EPI, 1, false, false, true>), dim3(tiles), dim3(kThreads), lds, st, a);
+                    return MVF_OK;
+                }
+            }
+            if (pw) hipLaunchKernelGGL((conv_igemm_glds_kernel<ET, WM, WN, TM, TN, EPI, 1, false, true>), dim3(tiles), dim3(kThreads), lds, st, a);
+            else hipLaunchKernelGGL((conv_igemm_glds_kernel<ET, WM, WN, TM, TN, EPI, 1>), dim3(tiles), dim3(kThreads), lds, st, a);
+        } else {
+            constexpr int lds = kGldsLds<BM, BN, 2>();
+            static bool attr = false;
+            if (!attr) {
+                MVF_HIP_OK(hipFuncSetAttribute((const void*)(conv_igemm_glds_kernel<ET, WM, WN, TM, TN, EPI, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+                MVF_HIP_OK(hipFuncSetAttribute((const void*)(conv_igemm_glds_kernel<ET, WM, WN, TM, TN, EPI, 2, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+                attr = true;
+            }
+            if (pw) hipLaunchKernelGGL((conv_igemm_glds_kernel<ET, WM, WN, TM, TN, EPI, 2, false, true>), dim3(tiles), dim3(kThreads), lds, st, a);
+            else hipLaunchKernelGGL((conv_igemm_glds_kernel<ET, WM, WN, TM, TN, EPI, 2>), dim3(tiles), dim3(kThreads), lds, st, a);
+        }
+        return MVF_OK;
+    });
 }
-int g_x3_wide = 0;               // policy x3_wide=n: the 8-wave 256 x 128 X3 tile for launches with >= n tiles of that size (0 = off)
 
 int g_f32_x3 = 1;                // fp32 storage: products on the bf16 matrix cores as 3-term bf16 splits (policy f32_x3=0: the fp32 MFMA)
-int g_x3_db_min = 1 << 30;       // X3: double-buffered planes (one workgroup per CU, one barrier per chunk) from this many K chunks on (policy x3_db)
-
-// X3 with two LDS buffers: chunk k + 1 is split and written to the other buffer behind the MFMAs of chunk k, one barrier per chunk
-template <int WM, int WN, int TM, int TN, int EPI = 0, bool PW = false>
-__global__ __launch_bounds__(kThreads) void conv_igemm_x3db_kernel(ConvArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    SkArgs sk = {};
-    conv_tile<float, WM, WN, TM, TN, false, false, false, EPI, PW, 0, false, false, false, true>(a, smem, xcd_swizzle(blockIdx.x, gridDim.x), 0, a.nchunks, SEG_FULL, sk, 0, 0);
-}
 
 // policy f32_x3: 0 never, 1 always; diagnostics: 2 only launches with a forward epilogue (statistics / bias / BatchNorm apply), 3 only the others
 // (data gradients, plain forwards), 4 only 3x3 taps, 5 only pointwise, 6 only the stem's 7 x 1 view, 7 everything but the stem
@@ -1667,58 +1570,26 @@ inline bool x3_on(const ConvArgs& a) {
     }
 }
 
-template <typename ET, int WM, int WN, int TM, int TN, int EPI>
-void launch_lowk(bool pw, int tiles, size_t lds, hipStream_t st, const ConvArgs& a) {
-    if constexpr (sizeof(ET) == 4) {
-        if (x3_on(a)) {
-            constexpr size_t lds3 = (size_t)kLowkLdsX3<WM * TM * 32, WN * TN * 32>();
-            if constexpr (WN * TN * 32 == 128 && EPI >= 1 && EPI <= 6) {
-                const int t_wide = ((a.M + 255) / 256) * a.tiles_n;
-                if (g_x3_wide > 0 && t_wide >= g_x3_wide) {
-                    ConvArgs b = a;
-                    b.tiles_m = (a.M + 255) / 256;
-                    constexpr size_t ldsw = (size_t)kLowkLdsX3<256, 128>();
-                    auto k0 = conv_igemm_x3w_kernel<EPI, false>;
-                    auto k1 = conv_igemm_x3w_kernel<EPI, true>;
-                    static bool attrw = false;
-                    if (!attrw) {
-                        (void)hipFuncSetAttribute((const void*)k0, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw);
-                        (void)hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw);
-                        attrw = true;
-                    }
-                    if (pw) hipLaunchKernelGGL(k1, dim3(t_wide), dim3(512), ldsw, st, b);
-                    else hipLaunchKernelGGL(k0, dim3(t_wide), dim3(512), ldsw, st, b);
-                    return;
-                }
+// the single-buffer register-staged kernels: fp32 on the bf16 matrix cores (x3_on) or the storage type's own MFMA
+template <typename ET, int WM, int WN, int TM, int TN>
+int launch_lowk(int epi, int tiles, hipStream_t st, const ConvArgs& a) {
+    constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
+    const bool pw = is_pointwise(a);
+    return with_epi<1, 2, 3, 4, 5, 6, 8, 9, 10, 12>(epi, [&](auto e) -> int {
+        constexpr int EPI = decltype(e)::value;
+        if constexpr (sizeof(ET) == 4) {
+            if (x3_on(a)) {
+                constexpr size_t lds3 = (size_t)kLowkLdsX3<BM, BN>();
+                if (pw) hipLaunchKernelGGL((conv_igemm_x3_kernel<WM, WN, TM, TN, EPI, true>), dim3(tiles), dim3(kThreads), lds3, st, a);
+                else hipLaunchKernelGGL((conv_igemm_x3_kernel<WM, WN, TM, TN, EPI, false>), dim3(tiles), dim3(kThreads), lds3, st, a);
+                return MVF_OK;
             }
-            if constexpr (EPI >= 1 && EPI <= 6) {
-                if (a.nchunks >= g_x3_db_min) {
-                    constexpr size_t ldsdb = (size_t)2 * (WM * TM * 32 + WN * TN * 32) * 192;
-                    auto k0 = conv_igemm_x3db_kernel<WM, WN, TM, TN, EPI, false>;
-                    auto k1 = conv_igemm_x3db_kernel<WM, WN, TM, TN, EPI, true>;
-                    static bool attr = false;
-                    if (!attr) {
-                        (void)hipFuncSetAttribute((const void*)k0, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsdb);
-                        (void)hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsdb);
-                        attr = true;
-                    }
-                    if (pw) hipLaunchKernelGGL(k1, dim3(tiles), dim3(kThreads), ldsdb, st, a);
-                    else hipLaunchKernelGGL(k0, dim3(tiles), dim3(kThreads), ldsdb, st, a);
-                    return;
-                }
-            }
-            if (pw) hipLaunchKernelGGL((conv_igemm_x3_kernel<WM, WN, TM, TN, EPI, true>), dim3(tiles), dim3(kThreads), lds3, st, a);
-            else hipLaunchKernelGGL((conv_igemm_x3_kernel<WM, WN, TM, TN, EPI, false>), dim3(tiles), dim3(kThreads), lds3, st, a);
-            return;
         }
-    }
-    if (pw) {
-        auto k = conv_igemm_lowk_kernel<ET, WM, WN, TM, TN, EPI, true>;
-        hipLaunchKernelGGL(k, dim3(tiles), dim3(kThreads), lds, st, a);
-    } else {
-        auto k = conv_igemm_lowk_kernel<ET, WM, WN, TM, TN, EPI, false>;
-        hipLaunchKernelGGL(k, dim3(tiles), dim3(kThreads), lds, st, a);
-    }
+        constexpr size_t lds = (size_t)kLowkLds<BM, BN>();
+        if (pw) hipLaunchKernelGGL((conv_igemm_lowk_kernel<ET, WM, WN, TM, TN, EPI, true>), dim3(tiles), dim3(kThreads), lds, st, a);
+        else hipLaunchKernelGGL((conv_igemm_lowk_kernel<ET, WM, WN, TM, TN, EPI, false>), dim3(tiles), dim3(kThreads), lds, st, a);
+        return MVF_OK;
+    });
 }
 
 // Stream-K tail: the last, partial wave of tiles is NOT run one tile per workgroup (which leaves e.g. 47 % of the CUs idle
@@ -1796,7 +1667,6 @@ int g_pf2_mode = 1;              // two-chunk register prefetch: 0 off, 1 bf16 o
 int g_glds1_f32_infer = 1;       // fp32: only the inference epilogues (bias + ReLU [+ residual]) take it by default (policy conv_glds1_f32=0/1)
 int g_glds1_max = -1;            // single-buffer LDS-DMA kernel (4 workgroups per CU) up to this many K chunks: -1 = default policy
                                  // (bf16: 8), 0 = off (policy conv_glds1)
-int g_big_min = 0;               // 256 x 128 LDS-DMA tile from this many K chunks on (policy conv_big; 0 = off)
 int g_big2_min = 16;             // 256 x 256 LDS-DMA tile (bf16) from this many K chunks on, when the tile count suits it (policy conv_big2; 0 = off).
                                  // Measured on the R50 bf16 train step: layer3's K = 1024 pointwise launches -16...-19 %, its 3x3 convs -5...-7 %
                                  // (conv family 9.59 -> 9.42 ms per step); from 8 chunks on the K = 512 launches lose (9.49)
@@ -1811,12 +1681,9 @@ int sk_slots() {
         g_glds1_f32_infer = mvf_policy_int("conv_glds1_f32", g_glds1_f32_infer);
         g_glds1_max = mvf_policy_int("conv_glds1", g_glds1_max);
         g_f32_x3 = mvf_policy_int("f32_x3", g_f32_x3);
-        g_x3_wide = mvf_policy_int("x3_wide", g_x3_wide);
-        g_x3_db_min = mvf_policy_int("x3_db", g_x3_db_min);
-        g_big_min = mvf_policy_int("conv_big", g_big_min);
         g_big2_min = mvf_policy_int("conv_big2", g_big2_min);
         g_glds_min = mvf_policy_int("conv_glds", g_glds_min);
-        g_glds_nb = mvf_policy_int("conv_glds_nb", g_glds_nb);      // 3 = two buffers, 8 waves (128 x 128 tile only)
+        g_glds_nb = mvf_policy_int("conv_glds_nb", g_glds_nb);      // 1 or 2 buffers (anything but 1 means 2)
         int dev = 0, cus = 256;
         if (hipGetDevice(&dev) == hipSuccess) {
             hipDeviceProp_t p;
@@ -1921,117 +1788,43 @@ int launch_conv(const ConvArgs& a0, const SkHost& skh, hipStream_t st) {
     const bool x3 = sizeof(ET) == 4 && x3_on(a);
     if (x3) sk_wins = false;
     if ((a.nchunks <= g_lowk_max_chunks && !sk_wins) || a.bn_z || a.ap_scale || a.bw_mode || x3) {      // single LDS buffer: half the LDS, 3-4 workgroups per CU
-        constexpr size_t lds_lk = (size_t)kLowkLds<BM, BN>();
-        static const int epi_spec = mvf_policy_int("conv_epi", 3);     // A/B switch: bit 0 epilogues, bit 1 pointwise loader
-        const bool pw = (epi_spec & 2) && a.KH == 1 && a.KW == 1 && a.pad == 0 && a.pad_w == 0 && a.split_c == 0 && a.dil <= 1;
-        const bool contiguous = (epi_spec & 1) && a.o_s <= 0;
-        const bool train_like = contiguous && !a.bias && !a.relu;
-        const bool infer_like = contiguous && a.bias && a.relu && !a.stats_part;
-        const bool bnsum_epi = (epi_spec & 1) && a.bn_z && !a.relu && !a.res;      // contiguous or a scattered parity class ([r5] + an optional bias)
-        // long K, wide output: the 256 x 128 LDS-DMA tile (policy conv_big = <min chunks>, 0 = off)
+        const int epi_spec = conv_epi_spec(), epi = conv_epi_of(a, epi_spec);
+        const bool infer = infer_like(a, epi_spec), bnsum = bnsum_epi(a, epi_spec);
+        // long K, wide output: the 256 x 256 LDS-DMA tile (policy conv_big2 = <min chunks>, 0 = off)
+        bool big2 = false;
         if (BN == 128 && sizeof(ET) == 2 && g_big2_min > 0 && a.nchunks >= g_big2_min && a.Cout % 256 == 0 && a.o_s <= 0 && !a.ap_scale && !a.bw_mode) {
             const long t2 = (long)((a.M + 255) / 256) * (a.Cout / 256);
             const int cus = slots / 2;
             const long rounds = (t2 + cus - 1) / cus;
             static const bool force2 = mvf_policy_has("conv_big2_force");      // tests: every eligible shape, whatever its tile count
-            if (force2 || (t2 >= cus / 2 && (double)t2 / (double)(rounds * cus) >= 0.75)) {       // the last round at least 3/4 full
-                int rc;
-                // the four-phase ping-pong loop carries the same tile (policy conv_p4=0 -> the two-barrier loop); whole K chunks only
-                static const int p4_on = mvf_policy_int("conv_p4", 1);
-                if (p4_on && a.Cin % 64 == 0 && (a.split_c % 64) == 0) {
-                    if (train_like && a.stats_part && !a.res && !a.bn_z) rc = launch_p4<ET, 1>(st, a);
-                    else if (bnsum_epi) rc = launch_p4<ET, 6>(st, a);
-                    else if (train_like && !a.stats_part && !a.res) rc = launch_p4<ET, 2>(st, a);
-                    else if (train_like && !a.stats_part && a.res) rc = launch_p4<ET, 3>(st, a);
-                    else if (infer_like && !a.res) rc = launch_p4<ET, 4>(st, a);
-                    else if (infer_like && a.res) rc = launch_p4<ET, 5>(st, a);
-                    else rc = launch_p4<ET, 0>(st, a);
-                    if (rc != MVF_OK) return rc;
-                    MVF_LAUNCH_CHECK();
-                    return MVF_OK;
-                }
-                if (train_like && a.stats_part && !a.res && !a.bn_z) rc = launch_big2<ET, 1>(st, a);
-                else if (bnsum_epi) rc = launch_big2<ET, 6>(st, a);
-                else if (train_like && !a.stats_part && !a.res) rc = launch_big2<ET, 2>(st, a);
-                else if (train_like && !a.stats_part && a.res) rc = launch_big2<ET, 3>(st, a);
-                else if (infer_like && !a.res) rc = launch_big2<ET, 4>(st, a);
-                else if (infer_like && a.res) rc = launch_big2<ET, 5>(st, a);
-                else rc = launch_big2<ET, 0>(st, a);
-                if (rc != MVF_OK) return rc;
-                MVF_LAUNCH_CHECK();
-                return MVF_OK;
-            }
-        }
-        if (BN == 128 && g_big_min > 0 && a.nchunks >= g_big_min && a.Cout >= 128 && a.M >= 256 && !a.ap_scale && !a.bw_mode) {
-            int rc;
-            if (train_like && a.stats_part && !a.res && !a.bn_z) rc = launch_big<ET, 1>(st, a);
-            else if (bnsum_epi) rc = launch_big<ET, 6>(st, a);
-            else if (train_like && !a.stats_part && !a.res) rc = launch_big<ET, 2>(st, a);
-            else if (train_like && !a.stats_part && a.res) rc = launch_big<ET, 3>(st, a);
-            else if (infer_like && !a.res) rc = launch_big<ET, 4>(st, a);
-            else if (infer_like && a.res) rc = launch_big<ET, 5>(st, a);
-            else rc = launch_big<ET, 0>(st, a);
-            if (rc != MVF_OK) return rc;
-            MVF_LAUNCH_CHECK();
-            return MVF_OK;
+            big2 = force2 || (t2 >= cus / 2 && (double)t2 / (double)(rounds * cus) >= 0.75);       // the last round at least 3/4 full
         }
         // long K: LDS-DMA staging (policy conv_glds = "<min chunks>[,<buffers 1|2>]", 0 = off)
         // default policy (measured per layer on the R50 train step, bf16): the DMA variant wins 10-15 % from 32 chunks on
         // (K >= 2048: the 3x3 layers of layer3/4) and, for the 128 x 64 tile, from 9 chunks (layer1's 3x3); it loses 10-20 % on
         // the 8-18 chunk pointwise layers, where three register-staged workgroups per CU hide more latency than two DMA ones
+        const bool glds_auto = g_glds_min < 0 && sizeof(ET) == 2 && (a.nchunks >= 32 || (BN == 64 && a.nchunks >= 9));
         // short K: the single-buffer DMA kernel needs no staging registers -> 4 workgroups per CU instead of 3, which hides more
         // of the per-tile fixed latency chain (kernel arguments -> offsets -> first chunk -> epilogue -> store drain) that
         // dominates these launches (ablation: with loads AND MFMAs removed the conv launches still take 58 % of their time).
         // Not for the BatchNorm-sum data gradient (its epilogue spills at 128 registers) and not for fp32 unless forced.
         // (bf16 inference epilogues -- bias + ReLU [+ residual], half-batch launch chains -- keep winning up to 16 chunks: +1.9 %)
         const int glds1_max = x3 ? 0 : g_glds1_max >= 0 ? g_glds1_max
-                              : (sizeof(ET) == 2 ? (infer_like ? 16 : 8) : ((infer_like && g_glds1_f32_infer) ? 8 : 0));
-        if (glds1_max > 0 && a.nchunks <= glds1_max && !((bnsum_epi || a.bw_mode == 10) && g_glds1_max < 0)) {      // (the two sum epilogues spill at 128 registers)
-            int rc;
-            if (a.ap_scale) rc = launch_glds<ET, WM, WN, TM, TN, 8>(1, tiles, st, a);
-            else if (a.bw_mode == 9) rc = launch_glds<ET, WM, WN, TM, TN, 9>(1, tiles, st, a);
-            else if (a.bw_mode == 10) rc = launch_glds<ET, WM, WN, TM, TN, 10>(1, tiles, st, a);
-            else if (train_like && a.stats_part && !a.res && !a.bn_z) rc = launch_glds<ET, WM, WN, TM, TN, 1>(1, tiles, st, a);
-            else if (bnsum_epi) rc = launch_glds<ET, WM, WN, TM, TN, 6>(1, tiles, st, a);
-            else if (train_like && !a.stats_part && !a.res) rc = launch_glds<ET, WM, WN, TM, TN, 2>(1, tiles, st, a);
-            else if (train_like && !a.stats_part && a.res) rc = launch_glds<ET, WM, WN, TM, TN, 3>(1, tiles, st, a);
-            else if (train_like && a.stats_part && a.res && a.out_gate && !a.bn_z) rc = launch_glds<ET, WM, WN, TM, TN, 12>(1, tiles, st, a);
-            else if (infer_like && !a.res) rc = launch_glds<ET, WM, WN, TM, TN, 4>(1, tiles, st, a);
-            else if (infer_like && a.res) rc = launch_glds<ET, WM, WN, TM, TN, 5>(1, tiles, st, a);
-            else rc = launch_glds<ET, WM, WN, TM, TN, 0>(1, tiles, st, a);
-            if (rc != MVF_OK) return rc;
-            MVF_LAUNCH_CHECK();
-            return MVF_OK;
+                              : (sizeof(ET) == 2 ? (infer ? 16 : 8) : ((infer && g_glds1_f32_infer) ? 8 : 0));
+        int rc;
+        if (big2) {
+            // the four-phase ping-pong loop carries the same tile (policy conv_p4=0 -> the two-barrier loop); whole K chunks only
+            static const int p4_on = mvf_policy_int("conv_p4", 1);
+            if (p4_on && a.Cin % 64 == 0 && (a.split_c % 64) == 0) rc = launch_p4<ET>(epi, st, a);
+            else rc = launch_big2<ET>(epi, st, a);
+        } else if (glds1_max > 0 && a.nchunks <= glds1_max && !((bnsum || a.bw_mode == 10) && g_glds1_max < 0)) {      // (the two sum epilogues spill at 128 registers)
+            rc = launch_glds<ET, WM, WN, TM, TN>(1, epi, tiles, st, a);
+        } else if (!x3 && ((g_glds_min > 0 && a.nchunks >= g_glds_min) || glds_auto)) {
+            rc = launch_glds<ET, WM, WN, TM, TN>(g_glds_nb, epi, tiles, st, a);
+        } else {
+            rc = launch_lowk<ET, WM, WN, TM, TN>(epi, tiles, st, a);
         }
-        const bool glds_auto = g_glds_min < 0 && sizeof(ET) == 2 && (a.nchunks >= 32 || (BN == 64 && a.nchunks >= 9));
-        if (!x3 && ((g_glds_min > 0 && a.nchunks >= g_glds_min) || glds_auto)) {
-            int rc;
-            if (a.ap_scale) rc = launch_glds<ET, WM, WN, TM, TN, 8>(g_glds_nb, tiles, st, a);
-            else if (a.bw_mode == 9) rc = launch_glds<ET, WM, WN, TM, TN, 9>(g_glds_nb, tiles, st, a);
-            else if (a.bw_mode == 10) rc = launch_glds<ET, WM, WN, TM, TN, 10>(g_glds_nb, tiles, st, a);
-            else if (train_like && a.stats_part && !a.res && !a.bn_z) rc = launch_glds<ET, WM, WN, TM, TN, 1>(g_glds_nb, tiles, st, a);
-            else if (bnsum_epi) rc = launch_glds<ET, WM, WN, TM, TN, 6>(g_glds_nb, tiles, st, a);
-            else if (train_like && !a.stats_part && !a.res) rc = launch_glds<ET, WM, WN, TM, TN, 2>(g_glds_nb, tiles, st, a);
-            else if (train_like && !a.stats_part && a.res) rc = launch_glds<ET, WM, WN, TM, TN, 3>(g_glds_nb, tiles, st, a);
-            else if (train_like && a.stats_part && a.res && a.out_gate && !a.bn_z) rc = launch_glds<ET, WM, WN, TM, TN, 12>(g_glds_nb, tiles, st, a);
-            else if (infer_like && !a.res) rc = launch_glds<ET, WM, WN, TM, TN, 4>(g_glds_nb, tiles, st, a);
-            else if (infer_like && a.res) rc = launch_glds<ET, WM, WN, TM, TN, 5>(g_glds_nb, tiles, st, a);
-            else rc = launch_glds<ET, WM, WN, TM, TN, 0>(g_glds_nb, tiles, st, a);
-            if (rc != MVF_OK) return rc;
-            MVF_LAUNCH_CHECK();
-            return MVF_OK;
-        }
-        if (a.ap_scale) launch_lowk<ET, WM, WN, TM, TN, 8>(pw, tiles, lds_lk, st, a);
-        else if (a.bw_mode == 9) launch_lowk<ET, WM, WN, TM, TN, 9>(pw, tiles, lds_lk, st, a);
-        else if (a.bw_mode == 10) launch_lowk<ET, WM, WN, TM, TN, 10>(pw, tiles, lds_lk, st, a);
-        else if (train_like && a.stats_part && !a.res && !a.bn_z) launch_lowk<ET, WM, WN, TM, TN, 1>(pw, tiles, lds_lk, st, a);
-        else if (bnsum_epi) launch_lowk<ET, WM, WN, TM, TN, 6>(pw, tiles, lds_lk, st, a);
-        else if (train_like && !a.stats_part && !a.res) launch_lowk<ET, WM, WN, TM, TN, 2>(pw, tiles, lds_lk, st, a);
-        else if (train_like && !a.stats_part && a.res) launch_lowk<ET, WM, WN, TM, TN, 3>(pw, tiles, lds_lk, st, a);
-        else if (train_like && a.stats_part && a.res && a.out_gate && !a.bn_z) launch_lowk<ET, WM, WN, TM, TN, 12>(pw, tiles, lds_lk, st, a);
-        else if (infer_like && !a.res) launch_lowk<ET, WM, WN, TM, TN, 4>(pw, tiles, lds_lk, st, a);
-        else if (infer_like && a.res) launch_lowk<ET, WM, WN, TM, TN, 5>(pw, tiles, lds_lk, st, a);
-        else launch_lowk<ET, WM, WN, TM, TN, 0>(pw, tiles, lds_lk, st, a);
+        if (rc != MVF_OK) return rc;
         MVF_LAUNCH_CHECK();
         return MVF_OK;
     }
