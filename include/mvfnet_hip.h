@@ -192,6 +192,40 @@ int mvf_conv2d_stats_rows(const mvf_conv_desc_t* d);
 int mvf_conv2d_nhwc_fwd_stats(const mvf_conv_desc_t* d, const void* x, const void* x2, const void* w_packed, void* y,
                               float* stats_part, const float* stats_shift, void* ws, size_t ws_bytes, void* stream);
 
+/* Which kernel the calling thread's LAST mvf_conv2d_* call launched: a host-side record (thread-local, plain stores next to each launch; no device
+ * work, no synchronisation) for tests and tools -- the launch policy (csrc/conv_nhwc.hip launch_conv, MVF_POLICY) decides it per shape, and nothing else
+ * tells a caller which kernel family its shape reached.  A call that launches several kernels (a strided data gradient: one per parity class with
+ * taps) leaves the record of its last launch and the count; a call refused before its first launch leaves launches = 0, family = MVF_CONV_FAM_NONE. */
+enum {
+    MVF_CONV_FAM_NONE = 0,
+    MVF_CONV_FAM_REG = 1,          /* register-staged, single LDS buffer (conv_igemm_lowk_kernel)                                  */
+    MVF_CONV_FAM_X3 = 2,           /* the same with fp32 storage on the bf16 matrix cores (conv_igemm_x3_kernel)                    */
+    MVF_CONV_FAM_LDS_DMA = 3,      /* 4-wave LDS-DMA kernel, `buffers` = 1 | 2 (conv_igemm_glds_kernel)                             */
+    MVF_CONV_FAM_T256_2B = 4,      /* 256 x 256 tile, two-barrier loop (conv_igemm_big2_kernel)                                     */
+    MVF_CONV_FAM_T256_P4 = 5,      /* 256 x 256 tile, four-phase loop (conv_igemm_p4_kernel)                                        */
+    MVF_CONV_FAM_DBUF = 6,         /* register-staged, double-buffered (conv_igemm_kernel)                                          */
+    MVF_CONV_FAM_DBUF_PF2 = 7,     /* ... with the two-chunk register prefetch (conv_igemm_pf2_kernel)                              */
+    MVF_CONV_FAM_STREAMK = 8,      /* double-buffered full waves + the stream-K tail (conv_streamk_kernel)                          */
+    MVF_CONV_FAM_GENERIC = 9,      /* generic-shape fallback (conv_igemm_gen_kernel)                                                */
+    MVF_CONV_FAM_MVF_LOADER = 10,  /* MVF fused into the A loader; `buffers` = 0 register-staged, 1 | 2 LDS-DMA                     */
+    MVF_CONV_FAM_STEM_DIRECT = 11, /* csrc/stem_direct.hip                                                                          */
+    MVF_CONV_FAM_PW_SUMS = 12,     /* csrc/pw_sums.hip                                                                              */
+    MVF_CONV_FAM_C3X3_C64 = 13     /* csrc/conv3x3_c64.hip                                                                          */
+};
+typedef struct {
+    int32_t family;                /* MVF_CONV_FAM_*                                                                                */
+    int32_t epi_asked;             /* the epilogue the launch asked for (conv_epi_of; the direct kernels: their own epilogue code)  */
+    int32_t epi_run;               /* the epilogue instantiated: 0 (generic, run-time arguments) when the family has not epi_asked  */
+    int32_t pointwise;             /* 1: the pointwise loader specialisation                                                        */
+    int32_t buffers;               /* LDS A/B buffers of the main loop (0: not applicable)                                          */
+    int32_t tile_m, tile_n;        /* output tile of a workgroup                                                                    */
+    int32_t dtype;                 /* MVF_F32 | MVF_BF16                                                                            */
+    int32_t k_chunks;              /* 128-byte K chunks of the last launch                                                          */
+    int32_t half_k;                /* 1: the half-chunk variant of the LDS-DMA kernel (the bf16 stem)                               */
+    int32_t launches;              /* kernel launches the call made                                                                 */
+} mvf_conv_launch_info_t;
+int mvf_conv2d_last_launch(mvf_conv_launch_info_t* out);
+
 /* w_oihw fp32 (cout, cin, kh, kw) [x scale[cout]] -> packed [cout][kh][kw_pad][cin_pad] in `dtype`
  * (zero padded; kw_pad >= kw, cin_pad >= cin).  bias_out[co] = shift[co] (copied) when given.
  * scale/shift = folded eval BatchNorm2d: scale = gamma/sqrt(var+eps), shift = beta - mean*scale. */

@@ -32,6 +32,17 @@ class ConvDesc(C.Structure):
                 ("res_c0", C.c_int32), ("x_c0", C.c_int32)]
 
 
+class ConvLaunchInfo(C.Structure):
+    """mvf_conv_launch_info_t: which kernel the calling thread's last mvf_conv2d_* call launched (host-side record)."""
+    _fields_ = [("family", C.c_int32), ("epi_asked", C.c_int32), ("epi_run", C.c_int32), ("pointwise", C.c_int32), ("buffers", C.c_int32),
+                ("tile_m", C.c_int32), ("tile_n", C.c_int32), ("dtype", C.c_int32), ("k_chunks", C.c_int32), ("half_k", C.c_int32),
+                ("launches", C.c_int32)]
+
+
+CONV_FAMILIES = {0: "none", 1: "reg", 2: "x3", 3: "lds_dma", 4: "t256_2b", 5: "t256_p4", 6: "dbuf", 7: "dbuf_pf2", 8: "streamk", 9: "generic",
+                 10: "mvf_loader", 11: "stem_direct", 12: "pw_sums", 13: "c3x3_c64"}
+
+
 class PackJob(C.Structure):
     _fields_ = [("w", C.c_void_p), ("out", C.c_void_p), ("cout", C.c_int32), ("cin", C.c_int32), ("kh", C.c_int32), ("kw", C.c_int32),
                 ("kw_pad", C.c_int32), ("cin_pad", C.c_int32), ("kind", C.c_int32), ("first_block", C.c_int32)]
@@ -121,6 +132,8 @@ def _load():
     lib.mvf_conv2d_stats_rows.argtypes = [cp]
     lib.mvf_conv2d_nhwc_fwd_stats.restype = i32
     lib.mvf_conv2d_nhwc_fwd_stats.argtypes = [cp, vp, vp, vp, vp, fp, fp, vp, sz, vp]
+    lib.mvf_conv2d_last_launch.restype = i32
+    lib.mvf_conv2d_last_launch.argtypes = [C.POINTER(ConvLaunchInfo)]
     lib.mvf_pack_conv_weight.restype = i32
     lib.mvf_pack_conv_weight.argtypes = [fp, i32, i32, i32, i32, i32, i32, fp, vp, i32, vp]
     lib.mvf_pack_conv_weights_batched.restype = i32

@@ -56,7 +56,8 @@ struct ConvArgs {
     // store -- the data gradient then hands the block below gm = g * [out > 0] instead of g + sign bits (mvf_conv2d_nhwc_fwd_resmask_gate)
     const unsigned char* out_gate;
     int x_c0;      // [r5] split operand: x holds channels [split_c, Cin) of the contraction at column (channel - x_c0) of its rows (0: at their own offset)
-    int mask_lds;  // stage the gate bytes in LDS (experiment switch policy mask_lds=0)
+    int mask_lds;  // stage the gate bytes in LDS; conv_fwd_impl always sets 1 (the policy switch mask_lds=0 is gone; the byte-load path stays for
+                   // tiles whose gate rows cannot be staged with 16-byte loads)
     int prio;      // experiment switch policy conv_prio=1: raise the wave priority around the MFMA phase of the LDS-DMA loops; in
                    // -DMVF_CONV_ABLATE builds bits 1-5 additionally switch parts of the kernel OFF (timing ablation, wrong results)
     int dil;       // input dilation (generic fallback; the strided data-gradient is normally decomposed into parity classes)
@@ -109,6 +110,15 @@ template <>
 struct TT<bf16_t> {
     static constexpr int ESZ = 2, UE = 8, CE = 64;
 };
+
+// Host-side record of the calling thread's last conv call (mvf_conv2d_last_launch): plain host stores next to each launch, nothing on the device.
+// conv_fwd_impl clears it; every launcher notes the kernel it launched.
+thread_local mvf_conv_launch_info_t t_last_launch = {};
+inline void note_launch(int family, int epi_asked, int epi_run, bool pw, int buffers, int bm, int bn, int esz, int nchunks, bool half_k = false) {
+    mvf_conv_launch_info_t& r = t_last_launch;
+    const int launches = r.launches + 1;
+    r = mvf_conv_launch_info_t{family, epi_asked, epi_run, pw ? 1 : 0, buffers, bm, bn, esz == 4 ? MVF_F32 : MVF_BF16, nchunks, half_k ? 1 : 0, launches};
+}
 
 // n / d for 0 <= n < 2^31 with host-made magic: l = ceil(log2 d), mul = floor(2^32 (2^l - d) / d) + 1, q = (mulhi(n, mul) + n) >> l
 __device__ __forceinline__ int fd_div(int n, unsigned mul, unsigned shr) { return (int)((__umulhi((unsigned)n, mul) + (unsigned)n) >> shr); }
@@ -1433,8 +1443,9 @@ inline bool is_pointwise(const ConvArgs& a) {
 }
 
 inline bool infer_like(const ConvArgs& a, int epi_spec) { return (epi_spec & 1) && a.o_s <= 0 && a.bias && a.relu && !a.stats_part; }
-// contiguous or a scattered parity class ([r5] + an optional bias)
-inline bool bnsum_epi(const ConvArgs& a, int epi_spec) { return (epi_spec & 1) && a.bn_z && !a.relu && !a.res; }
+// contiguous or a scattered parity class ([r5] + an optional bias).  Not under the conv_epi A/B switch: like 8 / 9 / 10 it has no generic form (epilogue 0
+// would write the FORWARD statistics of the gradient into the partials, and did under conv_epi=0 / 2 until the epilogue tests compared them with fp64 sums)
+inline bool bnsum_epi(const ConvArgs& a) { return a.bn_z && !a.relu && !a.res; }
 
 // The epilogue (conv_tile EPI) a launch asks for: the one place that ranks them.  A kernel family that does not instantiate the
 // answer runs the generic epilogue 0 instead (with_epi), which computes the same from the run-time arguments.
@@ -1443,7 +1454,7 @@ int conv_epi_of(const ConvArgs& a, int epi_spec) {
     if (a.ap_scale) return 8;
     if (a.bw_mode == 9 || a.bw_mode == 10) return a.bw_mode;
     if (train_like && a.stats_part && !a.res && !a.bn_z) return 1;
-    if (bnsum_epi(a, epi_spec)) return 6;
+    if (bnsum_epi(a)) return 6;
     if (train_like && !a.stats_part && !a.res) return 2;
     if (train_like && !a.stats_part && a.res) return 3;
     if (train_like && a.stats_part && a.res && a.out_gate && !a.bn_z) return 12;
@@ -1483,6 +1494,7 @@ int launch_big2(int epi, hipStream_t st, const ConvArgs& a0) {
             attr = true;
         }
         hipLaunchKernelGGL(k, dim3(a.tiles_m * a.tiles_n), dim3(512), lds, st, a);
+        note_launch(MVF_CONV_FAM_T256_2B, epi, decltype(e)::value, false, 2, 256, 256, (int)sizeof(ET), a.nchunks);
         return MVF_OK;
     });
 }
@@ -1514,7 +1526,9 @@ int launch_p4(int epi, hipStream_t st, const ConvArgs& a0) {
                 MVF_HIP_OK(hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
                 attr = true;
             }
-            hipLaunchKernelGGL(is_pointwise(a) ? k1 : k0, dim3(a.tiles_m * a.tiles_n), dim3(512), lds, st, a);
+            const bool pw = is_pointwise(a);
+            hipLaunchKernelGGL(pw ? k1 : k0, dim3(a.tiles_m * a.tiles_n), dim3(512), lds, st, a);
+            note_launch(MVF_CONV_FAM_T256_P4, epi, EPI, pw, 2, 256, 256, (int)sizeof(ET), a.nchunks);
             return MVF_OK;
         });
     }
@@ -1532,6 +1546,7 @@ int launch_glds(int nb, int epi, int tiles, hipStream_t st, const ConvArgs& a) {
             if constexpr (BN == 64 && sizeof(ET) == 2 && (EPI == 1 || EPI == 4)) {       // the stem (training: + statistics; inference: bias + ReLU)
                 if (!pw && (size_t)a.Cin * sizeof(ET) <= 64 && a.split_c == 0) {
                     hipLaunchKernelGGL((conv_igemm_glds_kernel<ET, WM, WN, TM, TN, EPI, 1, false, false, true>), dim3(tiles), dim3(kThreads), lds, st, a);
+                    note_launch(MVF_CONV_FAM_LDS_DMA, epi, EPI, false, 1, BM, BN, (int)sizeof(ET), a.nchunks, true);
                     return MVF_OK;
                 }
             }
@@ -1548,6 +1563,7 @@ int launch_glds(int nb, int epi, int tiles, hipStream_t st, const ConvArgs& a) {
             if (pw) hipLaunchKernelGGL((conv_igemm_glds_kernel<ET, WM, WN, TM, TN, EPI, 2, false, true>), dim3(tiles), dim3(kThreads), lds, st, a);
             else hipLaunchKernelGGL((conv_igemm_glds_kernel<ET, WM, WN, TM, TN, EPI, 2>), dim3(tiles), dim3(kThreads), lds, st, a);
         }
+        note_launch(MVF_CONV_FAM_LDS_DMA, epi, EPI, pw, nb == 1 ? 1 : 2, BM, BN, (int)sizeof(ET), a.nchunks);
         return MVF_OK;
     });
 }
@@ -1582,12 +1598,14 @@ int launch_lowk(int epi, int tiles, hipStream_t st, const ConvArgs& a) {
                 constexpr size_t lds3 = (size_t)kLowkLdsX3<BM, BN>();
                 if (pw) hipLaunchKernelGGL((conv_igemm_x3_kernel<WM, WN, TM, TN, EPI, true>), dim3(tiles), dim3(kThreads), lds3, st, a);
                 else hipLaunchKernelGGL((conv_igemm_x3_kernel<WM, WN, TM, TN, EPI, false>), dim3(tiles), dim3(kThreads), lds3, st, a);
+                note_launch(MVF_CONV_FAM_X3, epi, EPI, pw, 1, BM, BN, 4, a.nchunks);
                 return MVF_OK;
             }
         }
         constexpr size_t lds = (size_t)kLowkLds<BM, BN>();
         if (pw) hipLaunchKernelGGL((conv_igemm_lowk_kernel<ET, WM, WN, TM, TN, EPI, true>), dim3(tiles), dim3(kThreads), lds, st, a);
         else hipLaunchKernelGGL((conv_igemm_lowk_kernel<ET, WM, WN, TM, TN, EPI, false>), dim3(tiles), dim3(kThreads), lds, st, a);
+        note_launch(MVF_CONV_FAM_REG, epi, EPI, pw, 1, BM, BN, (int)sizeof(ET), a.nchunks);
         return MVF_OK;
     });
 }
@@ -1729,6 +1747,7 @@ int launch_conv(const ConvArgs& a0, const SkHost& skh, hipStream_t st) {
                 "conv2d: output image too large for tile-relative 32-bit addressing");
     MVF_REQUIRE(!a.bn_z || !(a.dil > 1 || a.KH > 31 || a.KW > 31 || img_bytes * span_imgs >= 0x7ffffff0L), MVF_EUNSUPPORTED,
                 "conv2d_dgrad_bnsums: shape needs the generic kernel, which has no BatchNorm-backward epilogue");
+    MVF_REQUIRE(!a.bn_z || bnsum_epi(a), MVF_EUNSUPPORTED, "conv2d_dgrad_bnsums: the BatchNorm-backward sums come with a plain data gradient only (no ReLU, no residual)");
     MVF_REQUIRE(!a.bw_mode || !(a.dil > 1 || a.KH > 31 || a.KW > 31 || img_bytes * span_imgs >= 0x7ffffff0L || a.o_s > 0), MVF_EUNSUPPORTED,
                 "conv2d_fwd_bnbwd: shape needs the generic kernel / a scattered output, which have no BatchNorm-backward-on-recompute epilogue");
     MVF_REQUIRE(!a.ap_scale || !(a.dil > 1 || a.KH > 31 || a.KW > 31 || img_bytes * span_imgs >= 0x7ffffff0L || a.o_s > 0), MVF_EUNSUPPORTED,
@@ -1741,6 +1760,7 @@ int launch_conv(const ConvArgs& a0, const SkHost& skh, hipStream_t st) {
             gen_attr = true;
         }
         hipLaunchKernelGGL(kern_gen, dim3(tiles), dim3(kThreads), lds, st, a);
+        note_launch(MVF_CONV_FAM_GENERIC, conv_epi_of(a, conv_epi_spec()), 0, false, 2, BM, BN, (int)sizeof(ET), a.nchunks);
         MVF_LAUNCH_CHECK();
         return MVF_OK;
     }
@@ -1780,6 +1800,7 @@ int launch_conv(const ConvArgs& a0, const SkHost& skh, hipStream_t st) {
             }
             hipLaunchKernelGGL(k, dim3(tiles), dim3(kThreads), lds_mvf, st, a);
         }
+        note_launch(MVF_CONV_FAM_MVF_LOADER, 4, 4, fk == 0, fk == 0 ? 1 : (fk == 1 ? 1 : 2), BM, BN, (int)sizeof(ET), a.nchunks);
         MVF_LAUNCH_CHECK();
         return MVF_OK;
     }
@@ -1789,7 +1810,7 @@ int launch_conv(const ConvArgs& a0, const SkHost& skh, hipStream_t st) {
     if (x3) sk_wins = false;
     if ((a.nchunks <= g_lowk_max_chunks && !sk_wins) || a.bn_z || a.ap_scale || a.bw_mode || x3) {      // single LDS buffer: half the LDS, 3-4 workgroups per CU
         const int epi_spec = conv_epi_spec(), epi = conv_epi_of(a, epi_spec);
-        const bool infer = infer_like(a, epi_spec), bnsum = bnsum_epi(a, epi_spec);
+        const bool infer = infer_like(a, epi_spec), bnsum = bnsum_epi(a);
         // long K, wide output: the 256 x 256 LDS-DMA tile (policy conv_big2 = <min chunks>, 0 = off)
         bool big2 = false;
         if (BN == 128 && sizeof(ET) == 2 && g_big2_min > 0 && a.nchunks >= g_big2_min && a.Cout % 256 == 0 && a.o_s <= 0 && !a.ap_scale && !a.bw_mode) {
@@ -1838,11 +1859,13 @@ int launch_conv(const ConvArgs& a0, const SkHost& skh, hipStream_t st) {
     if (!use_sk) {
         const bool pf2 = g_pf2_mode == 2 || (g_pf2_mode == 1 && sizeof(ET) == 2);
         hipLaunchKernelGGL(pf2 ? kern_pf : kern, dim3(tiles), dim3(kThreads), lds, st, a);
+        note_launch(pf2 ? MVF_CONV_FAM_DBUF_PF2 : MVF_CONV_FAM_DBUF, conv_epi_of(a, conv_epi_spec()), 0, false, 2, BM, BN, (int)sizeof(ET), a.nchunks);
         MVF_LAUNCH_CHECK();
         return MVF_OK;
     }
     if (full > 0) {
         hipLaunchKernelGGL(kern, dim3(full), dim3(kThreads), lds, st, a);
+        note_launch(MVF_CONV_FAM_DBUF, conv_epi_of(a, conv_epi_spec()), 0, false, 2, BM, BN, (int)sizeof(ET), a.nchunks);
         MVF_LAUNCH_CHECK();
     }
     SkArgs sk;
@@ -1856,6 +1879,7 @@ int launch_conv(const ConvArgs& a0, const SkHost& skh, hipStream_t st) {
     sk.err = sk.flags + slots;
     MVF_HIP_OK(hipMemsetAsync(sk.flags, 0, (size_t)(slots + 1) * sizeof(unsigned), st));
     hipLaunchKernelGGL(kern_sk, dim3(sk.G), dim3(kThreads), lds, st, a, sk);
+    note_launch(MVF_CONV_FAM_STREAMK, conv_epi_of(a, conv_epi_spec()), 0, false, 2, BM, BN, (int)sizeof(ET), a.nchunks);
     MVF_LAUNCH_CHECK();
     return MVF_OK;
 }
@@ -1865,6 +1889,12 @@ int launch_conv(const ConvArgs& a0, const SkHost& skh, hipStream_t st) {
 extern "C" {
 
 size_t mvf_conv2d_workspace_bytes(const mvf_conv_desc_t*) { return sk_ws_bytes(); }
+
+int mvf_conv2d_last_launch(mvf_conv_launch_info_t* out) {
+    MVF_REQUIRE(out, MVF_EINVAL, "conv2d_last_launch: NULL argument");
+    *out = t_last_launch;
+    return MVF_OK;
+}
 
 int mvf_conv2d_nhwc_fwd(const mvf_conv_desc_t* d, const void* x, const void* x2, const void* w_packed,
                         const float* bias, const void* residual, void* y, void* stream) {
@@ -2010,6 +2040,7 @@ static int conv_fwd_impl(const mvf_conv_desc_t* d, const void* x, const void* x2
                          const void* residual, void* y, float* stats_part, const float* stats_shift, void* ws, size_t ws_bytes,
                          void* stream, const unsigned char* res_mask, const BnBwdSums* bnb, const MvfFuse* mf, const BnApply* ap, const BnBwdRecompute* bw,
                          const unsigned char* out_gate) {
+    t_last_launch = mvf_conv_launch_info_t{};
     MVF_REQUIRE(d && x && w_packed && (y || (stats_part && !bnb)), MVF_EINVAL, "conv2d: NULL argument");      // (y may be NULL for a statistics-only pass)
     MVF_REQUIRE(d->dtype == MVF_F32 || d->dtype == MVF_BF16, MVF_EINVAL, "conv2d: bad dtype %d", d->dtype);
     MVF_REQUIRE(d->n > 0 && d->h > 0 && d->w > 0 && d->cin > 0 && d->cout > 0 && d->kh > 0 && d->kw > 0 &&
@@ -2092,6 +2123,7 @@ static int conv_fwd_impl(const mvf_conv_desc_t* d, const void* x, const void* x2
         if (epi) {
             StemDirectArgs s = {x, w_packed, y, bias, stats_part, stats_shift, a.stats_rows, epi, d->n, d->h, d->w, d->ho, d->wo, a.wK};
             const int rc = mvf_internal::stem_direct_launch(s, st);
+            if (rc == MVF_OK) note_launch(MVF_CONV_FAM_STEM_DIRECT, epi, epi, false, 0, 0, 64, 2, a.nchunks);
             if (rc != -1) return rc;
         }
     }
@@ -2103,6 +2135,7 @@ static int conv_fwd_impl(const mvf_conv_desc_t* d, const void* x, const void* x2
             PwSumsArgs s = {x, w_packed, sums10 ? residual : nullptr, sums10 ? res_mask : nullptr, sums10 ? bw->mean : stats_shift, sums10 ? bw->invstd : nullptr,
                             stats_part, a.stats_rows, sums10 ? 1 : 0, a.M, d->cout, 64, d->x_pix_stride};
             const int rc = mvf_internal::pw_sums_launch(s, st);
+            if (rc == MVF_OK) note_launch(MVF_CONV_FAM_PW_SUMS, sums10 ? 10 : 1, sums10 ? 10 : 1, true, 0, 0, 0, 2, a.nchunks);
             if (rc != -1) return rc;
         }
     }
@@ -2118,6 +2151,7 @@ static int conv_fwd_impl(const mvf_conv_desc_t* d, const void* x, const void* x2
             Conv3x3C64Args s = {x, w_packed, y, bias, stats_part, stats_shift, bnb ? bnb->z : nullptr, bnb ? bnb->mean : nullptr, bnb ? bnb->invstd : nullptr,
                                 bnb ? bnb->scale : nullptr, bnb ? bnb->shift : nullptr, a.stats_rows, epi, d->n, d->h, d->w, d->x_pix_stride, a.wK};
             const int rc = mvf_internal::conv3x3_c64_launch(s, st);
+            if (rc == MVF_OK) note_launch(MVF_CONV_FAM_C3X3_C64, epi, epi, false, 0, 0, 64, 2, a.nchunks);
             if (rc != -1) return rc;
         }
     }

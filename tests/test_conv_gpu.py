@@ -353,13 +353,14 @@ def test_conv_streamk_tail_matches_plain_launch_and_oracle(case, dtype):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("env", ["conv_glds=0", "conv_glds=1,conv_glds_nb=1", "conv_glds=1,conv_glds_nb=2", "conv_big2=1,conv_big2_force=1",
+@pytest.mark.parametrize("env", ["conv_glds=0", "conv_glds=0,conv_glds1=0", "conv_glds=1,conv_glds_nb=1", "conv_glds=1,conv_glds_nb=2", "conv_big2=1,conv_big2_force=1",
                                  "conv_big2=1,conv_big2_force=1,conv_p4=0", "stem_direct=0,conv3x3_direct=0"],
-                         ids=["register_staged_only", "lds_dma_1buf_everywhere", "lds_dma_2buf_everywhere",
+                         ids=["no_long_k_lds_dma_short_k_still_1buf_dma", "register_staged_only", "lds_dma_1buf_everywhere", "lds_dma_2buf_everywhere",
                               "tile_256x256_four_phase_everywhere", "tile_256x256_two_barrier_everywhere", "no_direct_stem_or_layer1_3x3"])
 def test_conv_kernel_variants_forced_by_env(env):
     """The loader variant is a per-process policy (environment, read once), so each forced policy re-runs this file's oracle
-    comparisons in a child process: register staging only, the LDS-DMA loop with one and two buffers for EVERY launch (the
+    comparisons in a child process: conv_glds=0 alone (bf16 launches of up to 8 K chunks, 16 for the inference epilogues, still take the single-buffer
+    LDS-DMA kernel), register staging only (conv_glds1=0 as well), the LDS-DMA loop with one and two buffers for EVERY launch (the
     default policy uses it from 32 K chunks on) and the 8-wave
     256 x 256 tile (default policy: bf16, >= 16 chunks, tile counts that fill the 256 single-workgroup slots) for every bf16
     Cout % 256 == 0 launch whatever its size."""
