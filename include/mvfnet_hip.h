@@ -539,9 +539,42 @@ int mvf_conv2d_nhwc_wgrad(const mvf_conv_desc_t* d, const void* dz, const void* 
                           int cin_real, int kw_packed, int cin_packed, float* dw_oihw, void* ws, size_t ws_bytes,
                           void* stream);
 /* [r5] the same GEMM with the workgroup count to aim at named by the caller (the library's own plans size weight gradients for a side stream: half the
- * chip); results differ from mvf_conv2d_nhwc_wgrad only by the fp32 summation order of the pixel split. */
+ * chip); results differ from mvf_conv2d_nhwc_wgrad only by the fp32 summation order of the pixel split.  `wgs` (8 .. 4096) is a count to AIM at: where it
+ * asks for more pixel splits than the workspace of mvf_conv2d_wgrad_workspace_bytes holds slabs, the rows per split are raised to the smallest multiple of
+ * 64 that fits, so every wgs of the range runs in the published workspace. */
 int mvf_conv2d_nhwc_wgrad_wgs(const mvf_conv_desc_t* d, const void* dz, const void* x, const void* x2, int kw_real,
                               int cin_real, int kw_packed, int cin_packed, float* dw_oihw, void* ws, size_t ws_bytes, int wgs, void* stream);
+/* Which kernel the calling thread's LAST mvf_conv2d_nhwc_wgrad[_wgs] call launched: the weight gradient's counterpart of mvf_conv2d_last_launch (host-side,
+ * thread-local, plain stores next to the launches; no device work).  A call refused before its first launch leaves launches = 0, family =
+ * MVF_WGRAD_FAM_NONE.  The two direct kernels report nsplit = their partial-slab count (one per workgroup) and rows_per_split = 0. */
+enum {
+    MVF_WGRAD_FAM_NONE = 0,
+    MVF_WGRAD_FAM_F32_REG = 1,     /* wgrad_kernel<float>, register-staged loaders (exact-fp32 MFMA)                                */
+    MVF_WGRAD_FAM_F32_DMA = 2,     /* wgrad_kernel<float, .., DMA>: the same with LDS-DMA loaders                                   */
+    MVF_WGRAD_FAM_X3 = 3,          /* wgrad_x3_kernel: fp32 storage on the bf16 matrix cores                                        */
+    MVF_WGRAD_FAM_BF16_WIDEN = 4,  /* wgrad_kernel<bf16_t>: bf16 widened to fp32 on the way into LDS (channel counts % 8 != 0)      */
+    MVF_WGRAD_FAM_BF16_REG = 5,    /* wgrad_bf16_kernel, register-staged loaders                                                    */
+    MVF_WGRAD_FAM_BF16_DMA2 = 6,   /* wgrad_bf16_kernel, two-buffer LDS-DMA                                                         */
+    MVF_WGRAD_FAM_BF16_PIPE = 7,   /* wgrad_bf16_pipe_kernel<stages>: `stages` = 3 | 4                                              */
+    MVF_WGRAD_FAM_T256_2B = 8,     /* 256 x 256 tile, two-barrier loop (wgrad_bf16_kernel<2, 4, true, 4>)                           */
+    MVF_WGRAD_FAM_T256_P4 = 9,     /* 256 x 256 tile, four-phase loop (wgrad_bf16_p4_kernel)                                        */
+    MVF_WGRAD_FAM_C3X3_C64 = 10,   /* csrc/wgrad3x3_c64.hip                                                                         */
+    MVF_WGRAD_FAM_STEM = 11        /* csrc/wgrad_stem.hip                                                                           */
+};
+typedef struct {
+    int32_t family;                /* MVF_WGRAD_FAM_*                                                                               */
+    int32_t stages;                /* LDS ring depth of the main loop (BF16_PIPE: 3 | 4; the other LDS-DMA loops: 2; else 0)        */
+    int32_t tile_co, tile_k;       /* output tile of a workgroup (the direct kernels: the whole 64 x K slab)                        */
+    int32_t dtype;                 /* MVF_F32 | MVF_BF16                                                                            */
+    int32_t nsplit;                /* pixel splits = fp32 partial slabs the reduce sums                                             */
+    int32_t rows_per_split;        /* pixels per split                                                                              */
+    int32_t xcd_rr;                /* 1: splits round-robin over the XCDs; 0: contiguous balanced ranges of (split, tile) pairs     */
+    int32_t split_operand;         /* 1: channels < split_c were read from x2                                                       */
+    int32_t gram;                  /* 1: the Gram plan (dz == x, pointwise, cin == cout; policy gram_wgs workgroups)                */
+    int32_t wgs_target;            /* the workgroup count the pixel split aimed at (the caller's for _wgs; 0: the direct kernels)    */
+    int32_t launches;              /* kernel launches the call made (the GEMM and the slab reduce: 2)                               */
+} mvf_wgrad_launch_info_t;
+int mvf_conv2d_wgrad_last_launch(mvf_wgrad_launch_info_t* out);
 /* Every weight pack of a training step in one launch.  jobs_dev = DEVICE array of njobs records sorted by first_block;
  * job k owns workgroups [first_block, first_block + ceil(elements / 2048)), total_blocks = their sum.  kind 0 = the forward
  * pack of mvf_pack_conv_weight (no scale), kind 1 = the data-gradient pack of mvf_pack_conv_weight_dgrad.  kind 2 / 3 = the

@@ -43,6 +43,17 @@ CONV_FAMILIES = {0: "none", 1: "reg", 2: "x3", 3: "lds_dma", 4: "t256_2b", 5: "t
                  10: "mvf_loader", 11: "stem_direct", 12: "pw_sums", 13: "c3x3_c64"}
 
 
+class WgradLaunchInfo(C.Structure):
+    """mvf_wgrad_launch_info_t: which kernel the calling thread's last mvf_conv2d_nhwc_wgrad[_wgs] call launched (host-side record)."""
+    _fields_ = [("family", C.c_int32), ("stages", C.c_int32), ("tile_co", C.c_int32), ("tile_k", C.c_int32), ("dtype", C.c_int32),
+                ("nsplit", C.c_int32), ("rows_per_split", C.c_int32), ("xcd_rr", C.c_int32), ("split_operand", C.c_int32), ("gram", C.c_int32),
+                ("wgs_target", C.c_int32), ("launches", C.c_int32)]
+
+
+WGRAD_FAMILIES = {0: "none", 1: "f32_reg", 2: "f32_dma", 3: "x3", 4: "bf16_widen", 5: "bf16_reg", 6: "bf16_dma2", 7: "bf16_pipe", 8: "t256_2b", 9: "t256_p4",
+                  10: "c3x3_c64", 11: "stem"}
+
+
 class PackJob(C.Structure):
     _fields_ = [("w", C.c_void_p), ("out", C.c_void_p), ("cout", C.c_int32), ("cin", C.c_int32), ("kh", C.c_int32), ("kw", C.c_int32),
                 ("kw_pad", C.c_int32), ("cin_pad", C.c_int32), ("kind", C.c_int32), ("first_block", C.c_int32)]
@@ -238,6 +249,8 @@ def _load():
     lib.mvf_conv2d_nhwc_wgrad.argtypes = [cp, vp, vp, vp, i32, i32, i32, i32, fp, vp, sz, vp]
     lib.mvf_conv2d_nhwc_wgrad_wgs.restype = i32
     lib.mvf_conv2d_nhwc_wgrad_wgs.argtypes = [cp, vp, vp, vp, i32, i32, i32, i32, fp, vp, sz, i32, vp]
+    lib.mvf_conv2d_wgrad_last_launch.restype = i32
+    lib.mvf_conv2d_wgrad_last_launch.argtypes = [C.POINTER(WgradLaunchInfo)]
     lib.mvf_pack_conv_weight_dgrad.restype = i32
     lib.mvf_pack_conv_weight_dgrad.argtypes = [fp, i32, i32, i32, i32, vp, i32, vp]
     lib.mvf_nhwc_stencil.restype = i32

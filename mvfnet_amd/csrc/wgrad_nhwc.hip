@@ -35,6 +35,9 @@ struct WgArgs {
     int abl;             // -DMVF_WGRAD_ABLATE builds only (timing ablation, wrong results): 1 no main loop, 2 no partial-slab stores
 };
 
+// Host-side record of the calling thread's last weight-gradient call (mvf_conv2d_wgrad_last_launch): plain host stores next to the launches, nothing on the device.
+thread_local mvf_wgrad_launch_info_t t_last_wgrad = {};
+
 // n / d for 0 <= n < 2^31 with host-made magic: l = ceil(log2 d), mul = floor(2^32 (2^l - d) / d) + 1, q = (mulhi(n, mul) + n) >> l
 __device__ __forceinline__ int wg_fd_div(int n, unsigned mul, unsigned shr) { return (int)((__umulhi((unsigned)n, mul) + (unsigned)n) >> shr); }
 // Workgroup -> (output tile, pixel split).  All tiles of one split read the SAME dz / x rows, so they should share an XCD (each has its own
@@ -1053,7 +1056,7 @@ __global__ __launch_bounds__(512) void wgrad_bf16_p4_kernel(WgArgs a) {
 }
 
 template <int TM, int TN>
-int launch_wgrad_bf16(const WgArgs& a, int tiles, int nsplit, hipStream_t st) {
+int launch_wgrad_bf16(const WgArgs& a, int tiles, int nsplit, hipStream_t st, int& fam, int& stages) {
     constexpr int BCO = 2 * TM * 32, BK = 2 * TN * 32;
     const size_t lds = (size_t)2 * BMR16 * (BCO * 2 + BK * 2);
     // LDS-DMA loaders by default where they measured faster (R50 bf16 train step, per layer): +6-15 % on the 3x3 and the wide
@@ -1077,6 +1080,7 @@ int launch_wgrad_bf16(const WgArgs& a, int tiles, int nsplit, hipStream_t st) {
         if (stages_env >= 4) hipLaunchKernelGGL(k4, dim3(nsplit * tiles), dim3(kThreads), lds_p, st, a);
         else hipLaunchKernelGGL(k3, dim3(nsplit * tiles), dim3(kThreads), lds_p, st, a);
         MVF_LAUNCH_CHECK();
+        fam = MVF_WGRAD_FAM_BF16_PIPE; stages = stages_env >= 4 ? 4 : 3;
         return MVF_OK;
     }
     if (dma) {
@@ -1088,6 +1092,7 @@ int launch_wgrad_bf16(const WgArgs& a, int tiles, int nsplit, hipStream_t st) {
         }
         hipLaunchKernelGGL(kd, dim3(nsplit * tiles), dim3(kThreads), lds, st, a);
         MVF_LAUNCH_CHECK();
+        fam = MVF_WGRAD_FAM_BF16_DMA2; stages = 2;
         return MVF_OK;
     }
     auto kern = wgrad_bf16_kernel<TM, TN>;
@@ -1098,10 +1103,12 @@ int launch_wgrad_bf16(const WgArgs& a, int tiles, int nsplit, hipStream_t st) {
     }
     hipLaunchKernelGGL(kern, dim3(nsplit * tiles), dim3(kThreads), lds, st, a);
     MVF_LAUNCH_CHECK();
+    fam = MVF_WGRAD_FAM_BF16_REG; stages = 0;
     return MVF_OK;
 }
 
-int launch_wgrad_bf16_big(const WgArgs& a, int tiles, int nsplit, hipStream_t st) {
+int launch_wgrad_bf16_big(const WgArgs& a, int tiles, int nsplit, hipStream_t st, int& fam, int& stages) {
+    stages = 2;
     constexpr size_t lds = (size_t)2 * BMR16 * (256 * 2 + 256 * 2);
     auto kd = wgrad_bf16_kernel<2, 4, true, 4>;
     auto kp = wgrad_bf16_p4_kernel;
@@ -1116,10 +1123,12 @@ int launch_wgrad_bf16_big(const WgArgs& a, int tiles, int nsplit, hipStream_t st
     if (p4_on && a.Cin % 64 == 0) {
         hipLaunchKernelGGL(kp, dim3(nsplit * tiles), dim3(512), lds, st, a);
         MVF_LAUNCH_CHECK();
+        fam = MVF_WGRAD_FAM_T256_P4;
         return MVF_OK;
     }
     hipLaunchKernelGGL(kd, dim3(nsplit * tiles), dim3(512), lds, st, a);
     MVF_LAUNCH_CHECK();
+    fam = MVF_WGRAD_FAM_T256_2B;
     return MVF_OK;
 }
 
@@ -1246,9 +1255,10 @@ __global__ __launch_bounds__(256) void pack_batched_kernel(const mvf_pack_job_t*
     }
 }
 
-int plan_split(int M, int tiles, int target_override = 0) {
+int plan_split(int M, int tiles, int target_override = 0, int* target_used = nullptr) {
     static const int target_env = std::max(64, mvf_policy_int("wgrad_wgs", 1024));     // workgroups aimed at per launch (A/B switch)
     const int target = target_override > 0 ? target_override : target_env;
+    if (target_used) *target_used = target;
     int want = std::max(1, target / std::max(tiles, 1));
     int rows = std::max((M + want - 1) / want, 256);
     rows = (rows + 63) / 64 * 64;          // multiple of both chunk heights (32 fp32 / 64 bf16)
@@ -1289,14 +1299,14 @@ static bool wg_big_shape(const mvf_conv_desc_t* d) {
     return big_env && d->dtype == MVF_BF16 && d->cout % 256 == 0 && K % 256 == 0 && d->cin % 8 == 0 && d->x_pix_stride % 4 == 0 &&
            (d->split_c == 0 || (d->split_c % 256 == 0 && d->cin % 256 == 0));
 }
-static int wg_big_rows(const mvf_conv_desc_t* d, int wgs_override = 0) {
+static int wg_big_rows(const mvf_conv_desc_t* d, int wgs_override = 0, int* target_used = nullptr) {
     const int M = d->n * d->ho * d->wo, K = d->kh * d->kw * d->cin;
     // [r5] 128 workgroups (half the CUs), not one per CU: these GEMMs run on the side stream beside the launch stream's kernels, and the two queues share the chip
     // work-conservingly -- what the weight gradients cost the step is their FOOTPRINT (a 256 x 256 workgroup owns its CU's whole register file), not their own
     // length.  Measured in the step (alternating runs; ms, C3 / C4): 256 workgroups 19.20 / 33.08, 192: 18.95 / 32.72, 128: 18.88 / 32.36 on one box; 128: 18.34 / 31.45,
     // 96: 18.35 / 31.91, 64: 18.50 / 32.38 on another.  (Round 2 measured 128 = 256 on a step whose launch stream still carried 7 ms of BatchNorm passes.)
     static const int big_wgs = std::max(32, mvf_policy_int("wgrad_big_wgs", 128));      // A/B switch
-    return plan_split(M, (d->cout / 256) * (K / 256), wgs_override > 0 ? wgs_override : big_wgs);
+    return plan_split(M, (d->cout / 256) * (K / 256), wgs_override > 0 ? wgs_override : big_wgs, target_used);
 }
 
 // [r4] layer1's 3x3 (64 -> 64 channels, stride 1, pad 1, bf16) on the direct kernel of wgrad3x3_c64.hip (policy wgrad3x3_direct=0: the implicit GEMM)
@@ -1329,6 +1339,7 @@ size_t mvf_conv2d_wgrad_workspace_bytes(const mvf_conv_desc_t* d) {
 }  // extern "C"
 static int wgrad_impl(const mvf_conv_desc_t* d, const void* dz, const void* x, const void* x2, int kw_real, int cin_real,
                       int kw_packed, int cin_packed, float* dw_oihw, void* ws, size_t ws_bytes, void* stream, int wgs_target) {
+    t_last_wgrad = mvf_wgrad_launch_info_t{};
     MVF_REQUIRE(d && dz && x && dw_oihw, MVF_EINVAL, "wgrad: NULL argument");
     MVF_REQUIRE(d->dtype == MVF_F32 || d->dtype == MVF_BF16, MVF_EINVAL, "wgrad: bad dtype");
     MVF_REQUIRE(d->cin % 4 == 0 && d->cout % 4 == 0 && d->x_pix_stride > 0, MVF_ESHAPE, "wgrad: cin/cout must be multiples of 4");
@@ -1340,13 +1351,19 @@ static int wgrad_impl(const mvf_conv_desc_t* d, const void* dz, const void* x, c
         Wgrad3x3C64Args w = {dz, x, (float*)ws, d->n, d->h, d->w, d->x_pix_stride, mvf_internal::wgrad3x3_c64_wgs(d->n, d->h)};
         const int rc = mvf_internal::wgrad3x3_c64_launch(w, st0);
         if (rc != MVF_OK) return rc;
-        return launch_wgrad_reduce((const float*)ws, w.nwg, 64, 64, 3, 3, 3, 64, dw_oihw, st0);
+        t_last_wgrad = mvf_wgrad_launch_info_t{MVF_WGRAD_FAM_C3X3_C64, 0, 64, 576, MVF_BF16, w.nwg, 0, 0, 0, 0, 0, 1};
+        const int rr = launch_wgrad_reduce((const float*)ws, w.nwg, 64, 64, 3, 3, 3, 64, dw_oihw, st0);
+        if (rr == MVF_OK) t_last_wgrad.launches = 2;
+        return rr;
     }
     if (wg_direct_stem(d) && kw_real == 7 && cin_real == 3 && kw_packed == 8 && cin_packed == 4 && ((uintptr_t)dz | (uintptr_t)x) % 16 == 0) {
         WgradStemArgs w = {dz, x, (float*)ws, d->n, d->h, d->w, d->ho, d->wo, mvf_internal::wgrad_stem_wgs(d->n, d->ho)};
         const int rc = mvf_internal::wgrad_stem_launch(w, st0);
         if (rc != MVF_OK) return rc;
-        return launch_wgrad_reduce((const float*)ws, w.nwg, 64, 3, 7, 7, 8, 4, dw_oihw, st0);
+        t_last_wgrad = mvf_wgrad_launch_info_t{MVF_WGRAD_FAM_STEM, 0, 64, 224, MVF_BF16, w.nwg, 0, 0, 0, 0, 0, 1};
+        const int rr = launch_wgrad_reduce((const float*)ws, w.nwg, 64, 3, 7, 7, 8, 4, dw_oihw, st0);
+        if (rr == MVF_OK) t_last_wgrad.launches = 2;
+        return rr;
     }
     WgArgs a = {};
     a.dz = dz; a.x = x; a.x2 = x2; a.part = (float*)ws;
@@ -1362,7 +1379,8 @@ static int wgrad_impl(const mvf_conv_desc_t* d, const void* dz, const void* x, c
     // 33.1, 16: 19.16 / 33.3, 8: 19.30 / 33.6 on another.
     static const int gram_env = std::max(8, mvf_policy_int("gram_wgs", 32));
     // (wgs_target > 0, mvf_conv2d_nhwc_wgrad_wgs: the caller names the workgroup count to aim at -- a GEMM the LAUNCH stream waits for wants the whole chip)
-    const int gram_wgs = wgs_target > 0 ? wgs_target : (dz == x && !x2 && d->kh == 1 && d->kw == 1 && d->cin == d->cout) ? gram_env : 0;
+    const bool gram = wgs_target <= 0 && dz == x && !x2 && d->kh == 1 && d->kw == 1 && d->cin == d->cout;
+    const int gram_wgs = wgs_target > 0 ? wgs_target : gram ? gram_env : 0;
     // 256 x 256 tile: the shapes of wg_big_shape() when the LDS-DMA address ranges and alignments hold and every split has >= 4 chunks
     // (a caller-named workgroup count takes the 128 x 128 plans)
     bool big = wg_big_shape(d) && wgs_target <= 0 && ((uintptr_t)dz | (uintptr_t)x | (uintptr_t)(x2 ? x2 : x)) % 16 == 0 &&
@@ -1384,9 +1402,16 @@ static int wgrad_impl(const mvf_conv_desc_t* d, const void* dz, const void* x, c
     // [r5] bf16 128 x 128 plans aim at 256 workgroups instead of 1024 for the same reason (with the big tile at 128; ms, C3 / C4: 1024: 18.34 / 31.45, 512: 18.20 / 31.29,
     // 384: 18.21 / 31.23, 256: 18.15 / 31.30)
     const int bf16_wgs = (d->dtype == MVF_BF16 && !wgs_forced) ? 256 : 0;
-    a.rows_per_split = big ? wg_big_rows(d, gram_wgs) : plan_split(a.M, tiles, gram_wgs ? gram_wgs : (x3 && !wgs_forced ? 768 : bf16_wgs));
+    int target_used = 0;
+    a.rows_per_split = big ? wg_big_rows(d, gram_wgs, &target_used) : plan_split(a.M, tiles, gram_wgs ? gram_wgs : (x3 && !wgs_forced ? 768 : bf16_wgs), &target_used);
+    if (wgs_target > 0) {
+        // the caller's count is one to aim at: where it asks for more slabs than the published workspace holds (its plans aim at fewer workgroups than the
+        // 4096 a caller may name), the splits grow to the smallest multiple of 64 rows that fits
+        const long fit = std::max<long>(1, (long)(mvf_conv2d_wgrad_workspace_bytes(d) / ((size_t)d->cout * a.K * sizeof(float))));
+        if ((a.M + a.rows_per_split - 1) / a.rows_per_split > fit) a.rows_per_split = std::max(a.rows_per_split, (int)(((a.M + fit - 1) / fit + 63) / 64 * 64));
+    }
     x3 = x3 && ((long)a.rows_per_split + 64) * d->cout * 4 < 0x7ffffff0L;
-    if (d->dtype == MVF_F32 && !x3 && !wgs_forced && !gram_wgs) a.rows_per_split = plan_split(a.M, tiles);
+    if (d->dtype == MVF_F32 && !x3 && !wgs_forced && !gram_wgs) a.rows_per_split = plan_split(a.M, tiles, 0, &target_used);
     const int nsplit = (a.M + a.rows_per_split - 1) / a.rows_per_split;
     MVF_REQUIRE(ws_bytes >= (size_t)nsplit * d->cout * a.K * sizeof(float), MVF_EWS, "wgrad: workspace too small for %d slabs", nsplit);
     a.tiles = tiles;
@@ -1405,15 +1430,19 @@ static int wgrad_impl(const mvf_conv_desc_t* d, const void* dz, const void* x, c
                        (a.split_c == 0 || (a.split_c % t.bk == 0 && a.Cin % t.bk == 0)) &&
                        ((uintptr_t)dz | (uintptr_t)x | (uintptr_t)(x2 ? x2 : x)) % 16 == 0 &&
                        (long)a.N * a.H * a.W * std::max(a.xps, a.x2ps) * 4 < 0x7ffffff0L && ((long)a.rows_per_split + 64) * d->cout * 4 < 0x7ffffff0L;
+    int fam = MVF_WGRAD_FAM_NONE, stages = 0;
     if (x3) {
+        fam = MVF_WGRAD_FAM_X3;
         if (t.bco == 64) hipLaunchKernelGGL((wgrad_x3_kernel<1, 2>), dim3(nsplit * tiles), dim3(256), 0, st, a);
         else if (t.bk == 64) hipLaunchKernelGGL((wgrad_x3_kernel<2, 1>), dim3(nsplit * tiles), dim3(256), 0, st, a);
         else hipLaunchKernelGGL((wgrad_x3_kernel<2, 2>), dim3(nsplit * tiles), dim3(256), 0, st, a);
     } else if (dma32) {
+        fam = MVF_WGRAD_FAM_F32_DMA; stages = 2;
         if (t.bco == 64) hipLaunchKernelGGL((wgrad_kernel<float, 1, 2, true>), dim3(nsplit * tiles), dim3(kThreads), 0, st, a);
         else if (t.bk == 64) hipLaunchKernelGGL((wgrad_kernel<float, 2, 1, true>), dim3(nsplit * tiles), dim3(kThreads), 0, st, a);
         else hipLaunchKernelGGL((wgrad_kernel<float, 2, 2, true>), dim3(nsplit * tiles), dim3(kThreads), 0, st, a);
     } else if (d->dtype == MVF_F32) {
+        fam = MVF_WGRAD_FAM_F32_REG;
         if (t.bco == 64) hipLaunchKernelGGL((wgrad_kernel<float, 1, 2>), dim3(nsplit * tiles), dim3(kThreads), 0, st, a);
         else if (t.bk == 64) hipLaunchKernelGGL((wgrad_kernel<float, 2, 1>), dim3(nsplit * tiles), dim3(kThreads), 0, st, a);
         else hipLaunchKernelGGL((wgrad_kernel<float, 2, 2>), dim3(nsplit * tiles), dim3(kThreads), 0, st, a);
@@ -1421,19 +1450,23 @@ static int wgrad_impl(const mvf_conv_desc_t* d, const void* dz, const void* x, c
                ((uintptr_t)dz | (uintptr_t)x | (uintptr_t)(x2 ? x2 : x)) % 16 == 0 &&
                ((long)a.rows_per_split + 6 * 64) * d->cout * 2 < 0x7ffffff0L) {      // 32-bit split-relative dz offsets (incl. look-ahead chunks)
         int rc;
-        if (big) rc = launch_wgrad_bf16_big(a, tiles, nsplit, st);
-        else if (t.bco == 64) rc = launch_wgrad_bf16<1, 2>(a, tiles, nsplit, st);
-        else if (t.bk == 64) rc = launch_wgrad_bf16<2, 1>(a, tiles, nsplit, st);
-        else rc = launch_wgrad_bf16<2, 2>(a, tiles, nsplit, st);
+        if (big) rc = launch_wgrad_bf16_big(a, tiles, nsplit, st, fam, stages);
+        else if (t.bco == 64) rc = launch_wgrad_bf16<1, 2>(a, tiles, nsplit, st, fam, stages);
+        else if (t.bk == 64) rc = launch_wgrad_bf16<2, 1>(a, tiles, nsplit, st, fam, stages);
+        else rc = launch_wgrad_bf16<2, 2>(a, tiles, nsplit, st, fam, stages);
         if (rc) return rc;
     } else {     // odd channel counts: widen to fp32 on the way into LDS
+        fam = MVF_WGRAD_FAM_BF16_WIDEN;
         if (t.bco == 64) hipLaunchKernelGGL((wgrad_kernel<bf16_t, 1, 2>), dim3(nsplit * tiles), dim3(kThreads), 0, st, a);
         else if (t.bk == 64) hipLaunchKernelGGL((wgrad_kernel<bf16_t, 2, 1>), dim3(nsplit * tiles), dim3(kThreads), 0, st, a);
         else hipLaunchKernelGGL((wgrad_kernel<bf16_t, 2, 2>), dim3(nsplit * tiles), dim3(kThreads), 0, st, a);
     }
     MVF_LAUNCH_CHECK();
+    t_last_wgrad = mvf_wgrad_launch_info_t{fam, stages, t.bco, t.bk, d->dtype, nsplit, a.rows_per_split, a.xcd_rr, a.split_c > 0 ? 1 : 0, gram ? 1 : 0, target_used, 1};
     const int kh_p = d->kh * d->kw * d->cin / (kw_packed * cin_packed);
-    return launch_wgrad_reduce(a.part, nsplit, d->cout, cin_real, kh_p, kw_real, kw_packed, cin_packed, dw_oihw, st);
+    const int rr = launch_wgrad_reduce(a.part, nsplit, d->cout, cin_real, kh_p, kw_real, kw_packed, cin_packed, dw_oihw, st);
+    if (rr == MVF_OK) t_last_wgrad.launches = 2;
+    return rr;
 }
 extern "C" {
 
@@ -1446,8 +1479,15 @@ int mvf_conv2d_nhwc_wgrad(const mvf_conv_desc_t* d, const void* dz, const void* 
 // same results up to the fp32 summation order of the pixel split
 int mvf_conv2d_nhwc_wgrad_wgs(const mvf_conv_desc_t* d, const void* dz, const void* x, const void* x2, int kw_real, int cin_real,
                               int kw_packed, int cin_packed, float* dw_oihw, void* ws, size_t ws_bytes, int wgs, void* stream) {
+    t_last_wgrad = mvf_wgrad_launch_info_t{};
     MVF_REQUIRE(wgs >= 8 && wgs <= 4096, MVF_EINVAL, "wgrad_wgs: wgs=%d outside 8 .. 4096", wgs);
     return wgrad_impl(d, dz, x, x2, kw_real, cin_real, kw_packed, cin_packed, dw_oihw, ws, ws_bytes, stream, wgs);
+}
+
+int mvf_conv2d_wgrad_last_launch(mvf_wgrad_launch_info_t* out) {
+    MVF_REQUIRE(out, MVF_EINVAL, "conv2d_wgrad_last_launch: NULL argument");
+    *out = t_last_wgrad;
+    return MVF_OK;
 }
 
 int mvf_pack_conv_weights_batched(const mvf_pack_job_t* jobs_dev, int njobs, int total_blocks, int dtype, void* stream) {

@@ -116,3 +116,27 @@ def test_head_and_optimizer_argument_failures_return_before_any_launch():
     assert b"multiple of 4" in lib.mvf_last_error()
     assert lib.mvf_head_pool_fc(a, 1, 1, 1, 6, a, a, 1, a, a, 0, None) == ESHAPE
     assert b"multiple of 4" in lib.mvf_last_error()
+
+
+def test_refused_weight_gradient_calls_leave_an_empty_launch_record():
+    """mvf_conv2d_wgrad_last_launch is a host-side record: a call refused before its first launch -- checked here from host addresses that are never read -- leaves
+    launches = 0 and family NONE, also after the caller-named entry point refuses its workgroup count."""
+    import ctypes as C
+    from mvfnet_amd import _lib
+    lib = _lib.lib
+    host = (C.c_float * 64)()
+    a = C.cast(host, C.c_void_p)
+    info = _lib.WgradLaunchInfo()
+    assert C.sizeof(info) == 12 * 4 and len(_lib.WGRAD_FAMILIES) == 12
+    d = _lib.ConvDesc(2, 4, 4, 64, 64, 1, 1, 1, 0, 4, 4, 64, _lib.MVF_BF16, 0, 0, 0, 0, 0, 0)
+    nb = lib.mvf_conv2d_wgrad_workspace_bytes(C.byref(d))
+    assert nb > 0
+    for rc_want, call in ((-3, lambda: lib.mvf_conv2d_nhwc_wgrad(C.byref(d), a, a, None, 1, 64, 1, 64, a, a, nb - 1, None)),
+                          (-1, lambda: lib.mvf_conv2d_nhwc_wgrad(C.byref(d), a, a, None, 1, 64, 2, 64, a, a, nb, None)),
+                          (-1, lambda: lib.mvf_conv2d_nhwc_wgrad_wgs(C.byref(d), a, a, None, 1, 64, 1, 64, a, a, nb, 7, None)),
+                          (-1, lambda: lib.mvf_conv2d_nhwc_wgrad_wgs(C.byref(d), a, a, None, 1, 64, 1, 64, a, a, nb, 4097, None))):
+        info.family, info.launches = 99, 99
+        assert call() == rc_want
+        assert lib.mvf_conv2d_wgrad_last_launch(C.byref(info)) == 0
+        assert (info.family, info.launches, info.nsplit) == (0, 0, 0)
+    assert lib.mvf_conv2d_wgrad_last_launch(None) == -1
