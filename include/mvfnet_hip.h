@@ -724,6 +724,38 @@ int mvf_bn_stats_snapshot(const mvf_stat_segment_t* seg, int nseg, long n, float
                           void* stream);
 int mvf_bn_stats_restore(const mvf_stat_segment_t* seg, int nseg, long n, const float* flat, long long* counters, long ncount,
                          const long long* counters_copy, const int* guard, void* stream);
+/* clip_grad_norm_(max_norm) on grad_scale * grads, then torch.optim.AdamW (decoupled = 1) or torch.optim.Adam (decoupled = 0), non-amsgrad, non-maximize, on
+ * flat fp32 device buffers that need only 4-byte alignment -- ONE entry point beside mvf_sgd_step_guarded, with its conventions: caller-owned workspace
+ * (mvf_adamw_workspace_bytes, 8-byte aligned), every check before any launch, no atomics, a grid that depends only on n, bit-identical from run to run.
+ * Per trained element, in fp32, with coef = norm_out[1] and t the step count AFTER this step:
+ *     d  = g * grad_scale * coef
+ *     decoupled = 0:  d = d + wd_i * p            decoupled = 1:  p = p * (1 - lr_i * wd_i)
+ *     m' = b1 * m + (1 - b1) * d
+ *     v' = b2 * v + (1 - b2) * d^2
+ *     p' = p - (lr_i / (1 - b1^t)) * m' / (sqrt(v') / sqrt(1 - b2^t) + eps)
+ * hyper is HOST memory, read during the call; its fields are doubles because 1 - beta1, 1 - beta2, 1 - lr_i * wd_i and lr_i / (1 - b1^t) are formed in double
+ * and rounded to fp32 once, as torch does with its Python scalars (1 - 0.999f misses 1 - 0.999 by 1.3e-5 relative, which would land in exp_avg_sq).
+ * applied_steps: one long long in DEVICE memory, 8-byte aligned, owned by the caller, zero at the start of a run: the number of steps applied so far.  The
+ * lane that finishes the norm writes norm_out and the guard counters, increments *applied_steps and leaves the two bias-correction factors of the new t (formed
+ * in double) in the workspace for the update kernel.  With guard != NULL and a non-finite scaled norm it does neither: the skipped step does not count, the
+ * next good step is corrected with the t it would have had -- torch's GradScaler, under which optimizer.step() is not called and state['step'] does not move.
+ * segments: the table of mvf_sgd_step_segments (lr * lr_mult, weight_decay * decay_mult per segment; lr_mult < 0 = excluded: the gradient stays outside the
+ * norm, params, exp_avg, exp_avg_sq and ema keep their bits); NULL (nseg ignored) = flat, bit-identical to the one-segment table {0, 1, 1}.
+ * ema: NULL (ema_momentum ignored) = none; else ema[i] = ema_step(ema[i], p', ema_momentum) where p' is in a register, bit-identical to the plain step
+ * followed by mvf_ema_update.  guard: NULL = unguarded; else the four counters of mvf_sgd_step_guarded with the same rule, every workgroup of the update
+ * kernel returns before any store when the flag is set, and with the flag clear the results are bit-identical to guard == NULL.
+ * MVF_EINVAL, nothing launched: a NULL params / grads / exp_avg / exp_avg_sq / norm_out / hyper / applied_steps, n <= 0, segments with nseg <= 0, a misaligned
+ * operand (applied_steps, ws and segments 8 bytes, the others 4), any two operands that overlap (the four arrays, ema, guard, applied_steps, norm_out, ws, the
+ * segment table), a beta outside [0, 1), eps <= 0, a negative lr or weight_decay, a NaN anywhere in the struct, decoupled other than 0 / 1, an ema_momentum
+ * outside [0, 1] (or NaN) when ema is given.  MVF_EWS: a NULL or short workspace. */
+typedef struct mvf_adamw_hyper {
+    double lr, beta1, beta2, eps, weight_decay;
+    int decoupled;
+} mvf_adamw_hyper_t;
+size_t mvf_adamw_workspace_bytes(long n);
+int mvf_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long n, float grad_scale, float max_norm,
+                   const mvf_adamw_hyper_t* hyper, const mvf_sgd_segment_t* segments, int nseg, float* ema, float ema_momentum, int* guard,
+                   long long* applied_steps, float* norm_out, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * [r6] Launch-table replay.  One training step (the reference's batch_processor + DistOptimizerHook.after_train_iter, codes/core/train.py:45-60,

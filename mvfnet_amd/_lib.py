@@ -68,6 +68,11 @@ class SgdSegment(C.Structure):
     _fields_ = [("first", C.c_int64), ("lr_mult", C.c_float), ("decay_mult", C.c_float)]
 
 
+class AdamwHyper(C.Structure):
+    """mvf_adamw_hyper_t: the hyper-parameters of mvf_adamw_step, doubles in HOST memory (the library rounds 1 - beta and 1 - lr * wd to fp32 once)."""
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double), ("decoupled", C.c_int32)]
+
+
 class StatSegment(C.Structure):
     """mvf_stat_segment_t: one BatchNorm statistic buffer in the flat shadow layout of the precise-BN entry points (csrc/precise_bn.hip)."""
     _fields_ = [("ptr", C.c_void_p), ("first", C.c_long)]
@@ -287,6 +292,10 @@ def _load():
     lib.mvf_bn_stats_snapshot.argtypes = [vp, i32, i64, fp, vp, i64, vp, vp]
     lib.mvf_bn_stats_restore.restype = i32
     lib.mvf_bn_stats_restore.argtypes = [vp, i32, i64, fp, vp, i64, vp, vp, vp]
+    lib.mvf_adamw_workspace_bytes.restype = sz
+    lib.mvf_adamw_workspace_bytes.argtypes = [i64]
+    lib.mvf_adamw_step.restype = i32
+    lib.mvf_adamw_step.argtypes = [fp, fp, fp, fp, i64, f32, f32, C.POINTER(AdamwHyper), vp, i32, fp, f32, vp, vp, fp, vp, sz, vp]
     lib.mvf_plan_run.restype = i32
     lib.mvf_plan_run.argtypes = [C.POINTER(PlanOp), i32, C.POINTER(C.c_ulonglong), C.POINTER(C.c_float), C.POINTER(C.c_int)]
     # Callers pass device pointers as plain Python ints (train_engine._p): without declared argtypes ctypes would truncate them to c_int silently.  Every

@@ -149,3 +149,55 @@ def sgd_momentum_buffers(opt_state, n_params):
         st = state.get(i, state.get(str(i)))
         bufs.append(None if not st else st.get("momentum_buffer"))
     return bufs, dict(groups[0])
+
+
+# ---- optimizer state: torch.optim.AdamW's / Adam's state_dict layout (the engine's fused Adam forms, train_engine._apply_adamw) ---------
+def adamw_state_dict(step, exp_avgs, exp_avg_sqs, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=True, multipliers=None, initial_lr=None):
+    """{'state': {i: {'step', 'exp_avg', 'exp_avg_sq'}}, 'param_groups': [...]} over n parameters in model.parameters() order; exp_avgs[i] is None for a
+    parameter that has not been stepped (torch creates its state at the first step).  `step` is the number of APPLIED steps, stored per parameter as a
+    float32 scalar tensor as torch stores it.  One param group -- or, with `multipliers` = [(lr_mult, decay_mult)] per parameter, one group per parameter, as
+    sgd_state_dict makes them.  Keys of a group = torch.optim.AdamW's (decoupled_weight_decay tells Adam from AdamW; older torch ignores the newer keys on
+    load).  `lr` is the current rate, `initial_lr` the schedule's base rate, stored as sgd_state_dict stores it."""
+    n = len(exp_avgs)
+    state = {i: {"step": torch.tensor(float(step), dtype=torch.float32), "exp_avg": m, "exp_avg_sq": v}
+             for i, (m, v) in enumerate(zip(exp_avgs, exp_avg_sqs)) if m is not None}
+    base = lr if initial_lr is None else initial_lr
+
+    def group(ids, lr_, wd_, base_):
+        return dict(lr=lr_, initial_lr=base_, betas=(float(betas[0]), float(betas[1])), eps=float(eps), weight_decay=wd_, amsgrad=False, maximize=False,
+                    foreach=None, capturable=False, differentiable=False, fused=None, decoupled_weight_decay=bool(decoupled), params=ids)
+
+    if multipliers is None:
+        return {"state": state, "param_groups": [group(list(range(n)), lr, weight_decay, base)]}
+    return {"state": state, "param_groups": [group([i], lr * a, weight_decay * b, base * a) for i, (a, b) in enumerate(multipliers)]}
+
+
+def adamw_moments(opt_state, n_params):
+    """Inverse: (step, exp_avgs, exp_avg_sqs, first group): the moments per parameter (None where absent) in parameter order and the ONE step count the
+    stepped parameters share -- the engine keeps a single counter, so a state whose parameters disagree is refused.  amsgrad / maximize states are refused."""
+    groups = opt_state.get("param_groups")
+    if not isinstance(groups, (list, tuple)) or "state" not in opt_state:
+        raise ValueError("not a torch optimizer state_dict (keys: %s)" % sorted(opt_state))
+    for g in groups:
+        for k in ("amsgrad", "maximize"):
+            if g.get(k):
+                raise NotImplementedError("optimizer state with %s=True: not built" % k)
+    ids = [i for g in groups for i in g["params"]]
+    if len(ids) != n_params:
+        raise ValueError("optimizer state covers %d parameters, the model has %d" % (len(ids), n_params))
+    state = opt_state["state"]
+    ms, vs, steps = [], [], set()
+    for i in ids:
+        st = state.get(i, state.get(str(i)))
+        if not st:
+            ms.append(None)
+            vs.append(None)
+            continue
+        if "exp_avg" not in st or "exp_avg_sq" not in st or "step" not in st:
+            raise ValueError("optimizer state of parameter %s has no step / exp_avg / exp_avg_sq (keys: %s): not an Adam / AdamW state" % (i, sorted(st)))
+        ms.append(st["exp_avg"])
+        vs.append(st["exp_avg_sq"])
+        steps.add(int(round(float(st["step"]))))
+    if len(steps) > 1:
+        raise ValueError("optimizer state: the parameters' step counts differ (%s); the fused optimizer keeps one" % sorted(steps))
+    return (steps.pop() if steps else 0), ms, vs, dict(groups[0])

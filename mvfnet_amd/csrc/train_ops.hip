@@ -1523,6 +1523,104 @@ int sgd_step_segments_impl(const char* who, float* params, const float* grads, f
     return MVF_OK;
 }
 
+// ---- optimizer: clip + Adam / AdamW (mvf_adamw_step) on the same flat buffers, beside the SGD kernels above, which it leaves as they are ----
+// The norm's partial sums come from sqsum_partial_kernel / sqsum_segments_kernel.  The lane that finishes the norm applies norm_finalize_kernel's rule
+// (norm, clip coefficient, guard counters) and ALSO keeps the step count: *steps is the number of APPLIED steps, so a step the guard skips does not move it
+// and the next good step is bias-corrected with the t it would have had without the skipped one (torch: GradScaler does not call optimizer.step(), and
+// state['step'] stays).  For the update kernel the lane leaves bc[0] = 1 / (1 - b1^t) and bc[1] = sqrt(1 - b2^t), formed in double from the new t.
+template <bool GUARD>
+__global__ void adamw_norm_finalize_kernel(const float* part, int nblk, float max_norm, float gscale, float* out /*[0]=norm,[1]=coef*/, int* guard,
+                                           long long* steps, double b1, double b2, double* bc) {
+    __shared__ double red[64];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < nblk; i += 64) acc += part[i];
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        double s = 0.0;
+        for (int i = 0; i < 64; ++i) s += red[i];
+        const float nrm = fabsf(gscale) * (float)sqrt(s);
+        out[0] = nrm;
+        float coef = max_norm > 0.f ? max_norm / (nrm + 1e-6f) : 1.f;     // torch clip_grad_norm_
+        out[1] = coef < 1.f ? coef : 1.f;
+        int bad = 0;
+        if (GUARD) {
+            bad = (__float_as_uint(nrm) & 0x7f800000u) == 0x7f800000u;
+            guard[0] = bad;
+            guard[1] += bad;
+            guard[2] = bad ? guard[2] + 1 : 0;
+            guard[3] += 1;
+        }
+        if (!bad) {
+            const long long t = *steps + 1;
+            *steps = t;
+            bc[0] = 1.0 / (1.0 - pow(b1, (double)t));
+            bc[1] = sqrt(1.0 - pow(b2, (double)t));
+        }
+    }
+}
+
+// the hyper-parameters as the update kernel takes them: lr and weight_decay stay double (a segment's lr * lr_mult, 1 - lr_i * wd_i and lr_i / (1 - b1^t) are
+// formed in double and rounded to fp32 ONCE, as torch rounds its Python scalars); the betas, their complements and eps are rounded once on the host
+struct AdamwConst {
+    double lr, wd;
+    float b1, omb1, b2, omb2, eps;
+    int decoupled;
+};
+
+// One element: d = g * coef [+ wd_i * p], m' = b1 m + (1 - b1) d, v' = b2 v + (1 - b2) d^2, p' = p [* (1 - lr_i wd_i)] - step_i * m' / (sqrt(v') / bc2 + eps).
+// SEG = false is the one-segment table {0, 1, 1}: the same expressions with both multipliers 1 (lr * 1.0 is lr), hoisted out of the loop by the compiler.
+template <bool SEG, bool EMA, bool GUARD>
+__global__ void adamw_kernel(float* p, const float* g, float* m, float* v, long n, const float* coef_ptr, float gscale, AdamwConst k, const double* bc,
+                             const mvf_sgd_segment_t* seg, int nseg, float* ema, float ema_m, const int* guard) {
+    if (GUARD) { if (guard[0] != 0) return; }
+    const float coef = coef_ptr[1] * gscale;
+    const double inv_bc1 = bc[0];
+    const float bc2 = (float)bc[1];
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        float lr_mult = 1.f, decay_mult = 1.f;
+        if (SEG) {
+            const int lo = seg_of(seg, nseg, i);
+            lr_mult = seg[lo].lr_mult;
+            decay_mult = seg[lo].decay_mult;
+            if (lr_mult < 0.f) continue;                     // excluded from training: parameter, both moments and the average untouched
+        }
+        const double lr_i = k.lr * (double)lr_mult, wd_i = k.wd * (double)decay_mult;
+        const float step = (float)(lr_i * inv_bc1);
+        float pv = p[i];
+        float d = g[i] * coef;
+        if (k.decoupled) pv = pv * (float)(1.0 - lr_i * wd_i);
+        else d = d + (float)wd_i * pv;
+        const float mn = k.b1 * m[i] + k.omb1 * d;
+        const float vn = k.b2 * v[i] + k.omb2 * (d * d);
+        m[i] = mn;
+        v[i] = vn;
+        const float pn = pv - step * (mn / (sqrtf(vn) / bc2 + k.eps));
+        p[i] = pn;
+        if (EMA) ema[i] = ema_step(ema[i], pn, ema_m);
+    }
+}
+
+constexpr size_t kAdamwPartBytes = 1024 * sizeof(float);      // the norm's partial sums; the two bias-correction doubles follow them
+
+template <bool SEG, bool EMA, bool GUARD>
+int adamw_launch(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long n, float grad_scale, float max_norm, const AdamwConst& k,
+                 double b1, double b2, const mvf_sgd_segment_t* segments, int nseg, float* ema, float ema_m, int* guard, long long* steps, float* norm_out,
+                 void* ws, hipStream_t st) {
+    float* part = (float*)ws;
+    double* bc = (double*)((char*)ws + kAdamwPartBytes);
+    const int nb = (int)std::min<long>((n + 255) / 256, 1024);
+    if (SEG) hipLaunchKernelGGL(sqsum_segments_kernel, dim3(nb), dim3(256), 0, st, grads, n, segments, nseg, part);
+    else hipLaunchKernelGGL(sqsum_partial_kernel, dim3(nb), dim3(256), 0, st, grads, n, part);
+    MVF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(adamw_norm_finalize_kernel<GUARD>, dim3(1), dim3(64), 0, st, part, nb, max_norm, grad_scale, norm_out, guard, steps, b1, b2, bc);
+    MVF_LAUNCH_CHECK();
+    hipLaunchKernelGGL((adamw_kernel<SEG, EMA, GUARD>), dim3(grid_for(n)), dim3(256), 0, st, params, grads, exp_avg, exp_avg_sq, n, norm_out, grad_scale, k,
+                       (const double*)bc, segments, nseg, ema, ema_m, (const int*)guard);
+    MVF_LAUNCH_CHECK();
+    return MVF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2175,6 +2273,65 @@ int mvf_sgd_step_guarded(float* params, const float* grads, float* momentum_buf,
                                                   segments, nseg, ema, ema_momentum, norm_out, ws, ws_bytes, stream, guard);
     return sgd_step_segments_impl<false, true>(who, params, grads, momentum_buf, n, grad_scale, max_norm, lr, momentum, weight_decay, first_step, nesterov, segments,
                                                nseg, nullptr, 0.f, norm_out, ws, ws_bytes, stream, guard);
+}
+
+// clip_grad_norm_ + torch.optim.Adam / AdamW on the flat buffers (mvfnet_hip.h).  Every check comes before the first launch.
+size_t mvf_adamw_workspace_bytes(long n) { return kAdamwPartBytes + 2 * sizeof(double); }
+
+int mvf_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long n, float grad_scale, float max_norm,
+                   const mvf_adamw_hyper_t* hyper, const mvf_sgd_segment_t* segments, int nseg, float* ema, float ema_momentum, int* guard,
+                   long long* applied_steps, float* norm_out, void* ws, size_t ws_bytes, void* stream) {
+    const char* who = "adamw_step";
+    MVF_REQUIRE(params && grads && exp_avg && exp_avg_sq && norm_out && n > 0 && (!segments || nseg > 0), MVF_EINVAL, "%s: bad argument", who);
+    MVF_REQUIRE(hyper, MVF_EINVAL, "%s: NULL hyper", who);
+    const double lr = hyper->lr, b1 = hyper->beta1, b2 = hyper->beta2, eps = hyper->eps, wd = hyper->weight_decay;
+    MVF_REQUIRE(lr == lr && b1 == b1 && b2 == b2 && eps == eps && wd == wd, MVF_EINVAL, "%s: NaN in the hyper-parameters", who);
+    MVF_REQUIRE(b1 >= 0.0 && b1 < 1.0 && b2 >= 0.0 && b2 < 1.0, MVF_EINVAL, "%s: betas (%g, %g) are outside [0, 1)", who, b1, b2);
+    MVF_REQUIRE(eps > 0.0, MVF_EINVAL, "%s: eps=%g must be positive", who, eps);
+    MVF_REQUIRE(lr >= 0.0 && wd >= 0.0, MVF_EINVAL, "%s: lr=%g and weight_decay=%g must not be negative", who, lr, wd);
+    MVF_REQUIRE(hyper->decoupled == 0 || hyper->decoupled == 1, MVF_EINVAL, "%s: decoupled=%d is neither 0 (Adam) nor 1 (AdamW)", who, hyper->decoupled);
+    MVF_REQUIRE(applied_steps && (uintptr_t)applied_steps % 8 == 0, MVF_EINVAL, "%s: applied_steps must be a non-NULL, 8-byte aligned device pointer", who);
+    if (ema) MVF_REQUIRE(ema_momentum >= 0.f && ema_momentum <= 1.f, MVF_EINVAL, "%s: ema_momentum=%g is outside [0, 1]", who, (double)ema_momentum);      // (NaN fails both)
+    // every operand, its extent in bytes and the alignment it needs; no two of them may overlap
+    const uintptr_t len = (uintptr_t)n * 4;
+    const struct { const char* name; uintptr_t at, bytes, align; } ops[10] = {
+        {"params", (uintptr_t)params, len, 4},           {"grads", (uintptr_t)grads, len, 4},
+        {"exp_avg", (uintptr_t)exp_avg, len, 4},         {"exp_avg_sq", (uintptr_t)exp_avg_sq, len, 4},
+        {"ema", (uintptr_t)ema, len, 4},                 {"guard", (uintptr_t)guard, 4 * sizeof(int), 4},
+        {"applied_steps", (uintptr_t)applied_steps, sizeof(long long), 8},
+        {"norm_out", (uintptr_t)norm_out, 2 * sizeof(float), 4},
+        {"the workspace", (uintptr_t)ws, (uintptr_t)ws_bytes, 8},
+        {"the segment table", (uintptr_t)segments, segments ? (uintptr_t)nseg * sizeof(mvf_sgd_segment_t) : 0, 8}};
+    for (int a = 0; a < 10; ++a) {
+        if (!ops[a].at) continue;
+        MVF_REQUIRE(ops[a].at % ops[a].align == 0, MVF_EINVAL, "%s: %s must be %d-byte aligned", who, ops[a].name, (int)ops[a].align);
+        for (int b = a + 1; b < 10; ++b)
+            MVF_REQUIRE(!ops[b].at || ops[a].at + ops[a].bytes <= ops[b].at || ops[b].at + ops[b].bytes <= ops[a].at, MVF_EINVAL, "%s: %s and %s overlap", who,
+                        ops[a].name, ops[b].name);
+    }
+    MVF_REQUIRE(ws && ws_bytes >= mvf_adamw_workspace_bytes(n), MVF_EWS, "%s: workspace too small", who);
+    AdamwConst k;
+    k.lr = lr;
+    k.wd = wd;
+    k.b1 = (float)b1;
+    k.omb1 = (float)(1.0 - b1);          // rounded once from the double: forming 1 - beta2 from a float 0.999 misses it by 1.3e-5 relative
+    k.b2 = (float)b2;
+    k.omb2 = (float)(1.0 - b2);
+    k.eps = (float)eps;
+    k.decoupled = hyper->decoupled;
+    hipStream_t st = (hipStream_t)stream;
+#define MVF_ADAMW_GO(SEG, EMA, GUARD)                                                                                                                   \
+    return adamw_launch<SEG, EMA, GUARD>(params, grads, exp_avg, exp_avg_sq, n, grad_scale, max_norm, k, b1, b2, segments, nseg, ema, ema_momentum, guard, \
+                                         applied_steps, norm_out, ws, st)
+    if (segments) {
+        if (ema) { if (guard) MVF_ADAMW_GO(true, true, true); MVF_ADAMW_GO(true, true, false); }
+        if (guard) MVF_ADAMW_GO(true, false, true);
+        MVF_ADAMW_GO(true, false, false);
+    }
+    if (ema) { if (guard) MVF_ADAMW_GO(false, true, true); MVF_ADAMW_GO(false, true, false); }
+    if (guard) MVF_ADAMW_GO(false, false, true);
+    MVF_ADAMW_GO(false, false, false);
+#undef MVF_ADAMW_GO
 }
 
 }  // extern "C"

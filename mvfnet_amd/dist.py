@@ -119,7 +119,7 @@ class MMDistributedDataParallel(torch.nn.Module):
 
 
 def _engine_backed_iter(optimizer, loss, grad_clip, exchange):
-    """The hook sequence for `build_optimizer`'s EngineSGD (the reference's _dist_train pairing, train.py:159-196): its step() updates
+    """The hook sequence for `build_optimizer`'s EngineSGD / EngineAdamW (the reference's _dist_train pairing, train.py:159-196): its step() updates
     from the engine's FLAT gradient buffer, which `loss.backward()` has just filled -- the parameters' .grad are autograd's copies, so
     an all-reduce or clip_grad_norm_ on them would never reach the update.  The exchange (/ world), the global L2 clip and the
     update therefore all run inside the engine on the flat buffer: one collective, one fused kernel.  Returns the pre-clip norm,

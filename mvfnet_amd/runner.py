@@ -9,7 +9,8 @@ iters from ratio 0.01; mmcv 0.4.3 semantics).  `train_recognizer.
 
 What is different by design: the optimizer is not a torch.optim object stepping 161 tensors but a facade (`EngineSGD`) over the
 train engine's fused clip + SGD kernel on ONE flat parameter buffer -- same hyper-parameters, same `state_dict()` wire format
-(torch.optim.SGD's), same per-parameter `paramwise_options`; `fp16 = dict(loss_scale=...)` in a config selects the engine's
+(torch.optim.SGD's), same per-parameter `paramwise_options` -- and `EngineAdamW` over its fused Adam / AdamW step for
+`optimizer = dict(type='AdamW' | 'Adam', ...)`, with `lr_config` policies 'cosine' and 'poly' beside 'step'; `fp16 = dict(loss_scale=...)` in a config selects the engine's
 bf16 storage mode (fp32 master weights / gradients / statistics as the reference's Fp16OptimizerHook keeps them,
 codes/core/fp16/hooks.py:12-136; bf16's exponent range makes the loss scale a no-op, it is accepted and ignored).
 Host batches are staged through pinned memory and uploaded on a copy stream one batch ahead (the reference's scatter
@@ -70,6 +71,63 @@ def step_lr(base_lr, epoch, it, steps=(90, 130), gamma=0.1, warmup="linear", war
     if warmup == "exp":
         return lr * warmup_ratio ** (1 - it / float(warmup_iters))
     raise NotImplementedError("lr_config warmup %r (mmcv LrUpdaterHook knows None, 'constant', 'linear', 'exp')" % (warmup,))
+
+
+def _progress(epoch, it, by_epoch, max_epochs, max_iters, who):
+    progress, max_progress = (epoch, max_epochs) if by_epoch else (it, max_iters)
+    if not max_progress or max_progress <= 0:
+        raise ValueError("%s: %s is not known (Runner.run sets it; pass it when calling the function directly)" % (who, "max_epochs" if by_epoch else "max_iters"))
+    return progress / float(max_progress)
+
+
+def cosine_lr(base_lr, epoch, it, max_epochs=None, max_iters=None, min_lr=None, min_lr_ratio=None, by_epoch=True, warmup=None, warmup_iters=0,
+              warmup_ratio=0.1):
+    """lr at (epoch, global iteration) -- mmcv CosineAnnealingLrUpdaterHook:
+
+        target + 0.5 * (base - target) * (1 + cos(pi * progress / max_progress)),      target = min_lr, or base * min_lr_ratio
+
+    exactly one of min_lr / min_lr_ratio is given.  by_epoch (default): progress / max_progress = epoch / max_epochs -- the rate is constant within an epoch --
+    else iter / max_iters.  The warm-up forms of step_lr are applied on top, as step_lr applies them (to the annealed rate, while iter < warmup_iters)."""
+    if (min_lr is None) == (min_lr_ratio is None):
+        raise ValueError("cosine lr policy: give exactly one of min_lr and min_lr_ratio")
+    target = base_lr * min_lr_ratio if min_lr_ratio is not None else min_lr
+    f = _progress(epoch, it, by_epoch, max_epochs, max_iters, "cosine lr policy")
+    lr = target + 0.5 * (base_lr - target) * (1.0 + np.cos(np.pi * f))
+    return step_lr(float(lr), 0, it, (), 1.0, warmup, warmup_iters, warmup_ratio)
+
+
+def poly_lr(base_lr, epoch, it, max_epochs=None, max_iters=None, power=1.0, min_lr=0.0, by_epoch=True, warmup=None, warmup_iters=0, warmup_ratio=0.1):
+    """lr at (epoch, global iteration) -- mmcv PolyLrUpdaterHook:
+
+        (base - min_lr) * (1 - progress / max_progress) ** power + min_lr
+
+    with progress / max_progress = epoch / max_epochs when by_epoch (default), else iter / max_iters; warm-up on top as in step_lr."""
+    f = _progress(epoch, it, by_epoch, max_epochs, max_iters, "poly lr policy")
+    lr = (base_lr - min_lr) * (1.0 - f) ** power + min_lr
+    return step_lr(float(lr), 0, it, (), 1.0, warmup, warmup_iters, warmup_ratio)
+
+
+def check_lr_policy(cfg):
+    """lr_config / Runner(lr_policy=): None or dict(policy='step') -> None (the step schedule of lr_steps / lr_gamma); dict(policy='cosine', min_lr= |
+    min_lr_ratio=, by_epoch=True) or dict(policy='poly', power=1.0, min_lr=0.0, by_epoch=True) -> a checked copy.  Keys that belong to the step policy or the
+    warm-up (step, gamma, warmup, warmup_iters, warmup_ratio) are the runner's own arguments and are ignored here."""
+    if cfg is None:
+        return None
+    cfg = dict(cfg)
+    policy = cfg.get("policy", "step")
+    if not isinstance(policy, str) or policy.lower() not in ("step", "cosine", "cosineannealing", "poly"):
+        raise NotImplementedError("lr_config policy %r: 'step', 'cosine' and 'poly' are built" % (policy,))
+    policy = {"cosineannealing": "cosine"}.get(policy.lower(), policy.lower())
+    if policy == "step":
+        return None
+    out = dict(policy=policy, by_epoch=bool(cfg.get("by_epoch", True)))
+    if policy == "cosine":
+        out.update(min_lr=cfg.get("min_lr"), min_lr_ratio=cfg.get("min_lr_ratio"))
+        if (out["min_lr"] is None) == (out["min_lr_ratio"] is None):
+            raise ValueError("lr_config policy 'cosine': give exactly one of min_lr and min_lr_ratio")
+    else:
+        out.update(power=float(cfg.get("power", 1.0)), min_lr=float(cfg.get("min_lr", 0.0)))
+    return out
 
 
 def parse_losses(losses):
@@ -155,15 +213,62 @@ class EngineSGD(object):
         g.update(lr=self.engine.lr, momentum=self.engine.momentum, weight_decay=self.engine.weight_decay, nesterov=self.engine.nesterov)
 
 
+class EngineAdamW(object):
+    """What `build_optimizer` returns for type='AdamW' | 'Adam': torch.optim.AdamW's surface (param_groups, state_dict, load_state_dict, zero_grad, step) over
+    the train engine's fused Adam step (mvf_adamw_step on the flat buffers: exp_avg / exp_avg_sq laid out like the parameters, the step count on the device).
+    `step()` = all-reduce / world (when a process group is up) + global L2 clip (if `grad_clip` was given) + the update, one fused launch sequence."""
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, maximize=False, decoupled=True, paramwise=None,
+                 dtype=None, **unknown):
+        if amsgrad:
+            raise NotImplementedError("AdamW amsgrad=True is not built")
+        if maximize:
+            raise NotImplementedError("AdamW maximize=True is not built")
+        unknown = {k: v for k, v in unknown.items() if k not in ("foreach", "capturable", "differentiable", "fused") or v}
+        if unknown:
+            raise TypeError("optimizer config: unexpected keys %s" % sorted(unknown))
+        model = model.module if hasattr(model, "module") else model
+        opt = dict(lr=lr, weight_decay=weight_decay, max_norm=None, optimizer="adamw" if decoupled else "adam", betas=betas, eps=eps)
+        if dtype is not None:
+            opt["dtype"] = dtype
+        self.model, self.engine = model, model.train_engine(**opt)
+        self.grad_clip = None
+        self.engine.max_norm = None
+        self.engine.set_param_options(paramwise)
+        self.param_groups = [dict(lr=lr, initial_lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False,
+                                  decoupled_weight_decay=bool(decoupled), params=list(model.parameters()))]
+
+    zero_grad = EngineSGD.zero_grad
+
+    def step(self, lr=None):
+        g = self.param_groups[0]
+        self.engine.weight_decay = g["weight_decay"]
+        if tuple(g["betas"]) != self.engine.betas or g["eps"] != self.engine.eps:
+            self.engine.set_optimizer(self.engine.optimizer, betas=g["betas"], eps=g["eps"])
+        return self.engine.step(g["lr"] if lr is None else lr)
+
+    def state_dict(self):
+        self.engine.lr = self.param_groups[0]["lr"]
+        self.engine.initial_lr = self.param_groups[0].get("initial_lr", self.engine.lr)
+        return self.engine.optimizer_state_dict()
+
+    def load_state_dict(self, sd):
+        self.engine.load_optimizer_state_dict(sd)
+        self.param_groups[0].update(lr=self.engine.lr, betas=self.engine.betas, eps=self.engine.eps, weight_decay=self.engine.weight_decay)
+
+
 def build_optimizer(model, optimizer_cfg, dtype=None):
     """reference train.py:79-156 for the optimizer the MVFNet configs use: dict(type='SGD', lr, momentum, weight_decay, nesterov
-    [, paramwise_options=dict(bias_lr_mult, bias_decay_mult, norm_decay_mult)])."""
+    [, paramwise_options=dict(bias_lr_mult, bias_decay_mult, norm_decay_mult)]) -> EngineSGD, and for fine-tuning configs
+    dict(type='AdamW' | 'Adam', lr, betas, eps, weight_decay[, paramwise_options]) -> EngineAdamW (amsgrad / maximize are refused)."""
     cfg = dict(optimizer_cfg)
     kind = cfg.pop("type", "SGD")
-    if kind != "SGD":
-        raise NotImplementedError("optimizer type %r: the fused HIP optimizer is SGD (the MVFNet configs' choice)" % kind)
+    if kind not in ("SGD", "AdamW", "Adam"):
+        raise NotImplementedError("optimizer type %r: the fused HIP optimizers are SGD, AdamW and Adam" % kind)
     paramwise = cfg.pop("paramwise_options", None)
     target = model.module if hasattr(model, "module") else model
+    if kind != "SGD" and not hasattr(target, "train_engine"):
+        raise NotImplementedError("optimizer type %r: the fused Adam step lives in a recognizer's train engine; %s has none" % (kind, type(target).__name__))
     mult = None
     if paramwise is not None:
         if not isinstance(paramwise, dict):
@@ -171,6 +276,10 @@ def build_optimizer(model, optimizer_cfg, dtype=None):
         if ("bias_decay_mult" in paramwise or "norm_decay_mult" in paramwise) and cfg.get("weight_decay") is None:
             raise ValueError("weight_decay must be given explicitly when a decay multiplier is")        # train.py:123-125
         mult = paramwise_multipliers(target, paramwise)
+    if kind != "SGD":
+        if kind == "Adam":
+            cfg.setdefault("weight_decay", 0.0)          # (torch.optim.Adam's default; AdamW's is 1e-2)
+        return EngineAdamW(target, paramwise=mult, dtype=dtype, decoupled=(kind == "AdamW"), **cfg)
     return EngineSGD(target, paramwise=mult, dtype=dtype, **cfg)
 
 
@@ -297,8 +406,11 @@ class Runner(object):
 
     def __init__(self, model, work_dir=None, lr=0.015, momentum=0.9, weight_decay=1e-4, max_norm=40.0, lr_steps=(90, 130),
                  warmup_iters=25070, warmup_ratio=0.01, ckpt_interval=10, log_interval=20, logger=print, optimizer=None, dtype=None,
-                 warmup="linear", lr_gamma=0.1, accumulate=1, ema=None, precise_bn=None, nonfinite_guard=None):
-        """nonfinite_guard = dict(max_consecutive=100) (an empty dict gives the default): an optimizer step whose clip norm is not finite -- a NaN / inf in a
+                 warmup="linear", lr_gamma=0.1, accumulate=1, ema=None, precise_bn=None, nonfinite_guard=None, lr_policy=None):
+        """lr_policy = None (the step schedule of lr_steps / lr_gamma), dict(policy='cosine', min_lr= | min_lr_ratio=, by_epoch=True) or dict(policy='poly',
+        power=1.0, min_lr=0.0, by_epoch=True): mmcv's CosineAnnealing / Poly updater hooks (cosine_lr / poly_lr) with the same warm-up on top; max_epochs and
+        max_iters (optimizer steps) are learned in run().
+        nonfinite_guard = dict(max_consecutive=100) (an empty dict gives the default): an optimizer step whose clip norm is not finite -- a NaN / inf in a
         gradient, or a sum of squares beyond fp32 -- is skipped on the device and the BatchNorm statistics go back to before it (TrainEngine.enable_step_guard);
         the counters are read where the loop synchronises anyway (the log interval, and always at epoch end): the log line gains `skipped N`, and
         max_consecutive skipped steps in a row raise FloatingPointError -- nothing has been poisoned by then, the live state and the last checkpoint are both
@@ -312,6 +424,8 @@ class Runner(object):
         reference's 8 x 12-clip recipe on one GPU with videos_per_gpu=12, accumulate=8.  `iter`, the warm-up and the log interval then count OPTIMIZER steps."""
         self.model, self.work_dir = model, work_dir
         self.accumulate = check_accumulate(accumulate)
+        self.lr_policy = check_lr_policy(lr_policy)
+        self.max_epochs = self.max_iters = None      # known once run() is called: the cosine / poly schedules need them
         self.ema = check_ema(ema)                    # (refused before anything is built)
         self.precise_bn = check_precise_bn(precise_bn)
         self.nonfinite_guard = check_nonfinite_guard(nonfinite_guard)
@@ -353,6 +467,11 @@ class Runner(object):
         return hook
 
     def current_lr(self):
+        if self.lr_policy is not None:
+            pol = {k: v for k, v in self.lr_policy.items() if k != "policy"}
+            fn = cosine_lr if self.lr_policy["policy"] == "cosine" else poly_lr
+            return fn(self.base_lr, self.epoch, self.iter, self.max_epochs, self.max_iters, warmup=self.warmup, warmup_iters=self.warmup_iters,
+                      warmup_ratio=self.warmup_ratio, **pol)
         return step_lr(self.base_lr, self.epoch, self.iter, self.lr_steps, self.lr_gamma, self.warmup, self.warmup_iters, self.warmup_ratio)
 
     def _check_guard(self):
@@ -419,6 +538,9 @@ class Runner(object):
     def run(self, loader, max_epochs):
         if isinstance(loader, (list, tuple)) and loader and not isinstance(loader[0], dict):
             loader = loader[0]        # mmcv Runner.run(data_loaders, workflow, max_epochs): the train loader is first (a list of dicts is a loader of batches)
+        self.max_epochs = max_epochs
+        if hasattr(loader, "__len__"):               # mmcv: max_iters = max_epochs * len(loader); under accumulation an iter is an optimizer step
+            self.max_iters = max_epochs * (-(-len(loader) // self.accumulate))
         while self.epoch < max_epochs:
             if hasattr(getattr(loader, "sampler", None), "set_epoch"):
                 loader.sampler.set_epoch(self.epoch)            # DistSamplerSeedHook
@@ -442,7 +564,8 @@ class Runner(object):
 
     def resume(self, filename):
         """mmcv Runner.resume: weights, epoch / iter from meta, optimizer state (torch.optim.SGD's layout -- a checkpoint written
-        by the reference resumes here and vice versa; round 1's own flat layout is still read)."""
+        by the reference resumes here and vice versa; round 1's own flat layout is still read -- or torch.optim.AdamW's under the
+        fused Adam forms: both moments and the device step count, so the next step equals the uninterrupted run's bit for bit)."""
         ckpt = load_checkpoint(self.model, filename, strict=True)
         meta = ckpt.get("meta", {})
         self.epoch, self.iter = meta.get("epoch", 0), meta.get("iter", 0)
@@ -451,8 +574,11 @@ class Runner(object):
         opt = ckpt.get("optimizer")
         if opt:
             lr, mom, wd = self.engine.lr, self.engine.momentum, self.engine.weight_decay
+            kind, betas, eps = self.engine.optimizer, self.engine.betas, self.engine.eps
             self.engine.load_optimizer_state_dict(opt)
             self.engine.lr, self.engine.momentum, self.engine.weight_decay = lr, mom, wd      # the config's values win (lr follows the schedule)
+            if kind != "sgd":
+                self.engine.set_optimizer(kind, betas=betas, eps=eps)                          # (likewise; the moments and the step count are the checkpoint's)
         if ckpt.get("ema"):
             self.engine.load_ema_state_dict(ckpt["ema"])
             if self.ema is not None:                 # the config's momentum / warm-up win; the averaged weights and the update count are the checkpoint's
@@ -482,7 +608,7 @@ def as_config(cfg):
 def train_network(model, dataset, cfg, distributed=False, validate=False, logger=None):
     """reference train.py:63-76 + _dist_train / _non_dist_train :159-252: loaders, model on the GPU (parameters broadcast from
     rank 0 when distributed), optimizer from cfg.optimizer, grad clip from cfg.optimizer_config, lr schedule from cfg.lr_config,
-    checkpoints from cfg.checkpoint_config, logging interval from cfg.log_config, optional fp16 section, resume_from /
+    (policy 'step', or 'cosine' / 'poly' as mmcv's CosineAnnealing / Poly updater hooks: Runner(lr_policy=...)), checkpoints from cfg.checkpoint_config, logging interval from cfg.log_config, optional fp16 section, resume_from /
     load_from, then run cfg.total_epochs.  cfg.ema_config = dict(momentum=..., warmup_steps=...) keeps averaged weights (Runner(ema=...)).
     cfg.precise_bn = dict(num_iters=..., interval=..., weights=...) recomputes the BatchNorm running statistics at epoch end (Runner(precise_bn=...)).
     cfg.nonfinite_guard = dict(max_consecutive=100) skips optimizer steps with a non-finite gradient norm on the device (Runner(nonfinite_guard=...)).
@@ -497,6 +623,8 @@ def train_network(model, dataset, cfg, distributed=False, validate=False, logger
     nonfinite_guard = check_nonfinite_guard(cfg.get("nonfinite_guard"))
     if precise_bn is not None and precise_bn["weights"] != "live" and ema is None:
         raise ValueError("precise_bn: weights=%r needs averaged weights; set ema_config as well" % precise_bn["weights"])
+    lrc = cfg.get("lr_config") or {}
+    lr_policy = check_lr_policy({k: _cfg_get(lrc, k) for k in ("policy", "by_epoch", "min_lr", "min_lr_ratio", "power") if _cfg_get(lrc, k) is not None})
     log = (logger.info if logger is not None and hasattr(logger, "info") else (logger or print))
     is_list_of_sets = isinstance(dataset, (list, tuple)) and dataset and not isinstance(dataset[0], dict)     # (a list of dicts = ready batches)
     datasets = dataset if is_list_of_sets else [dataset]
@@ -512,9 +640,6 @@ def train_network(model, dataset, cfg, distributed=False, validate=False, logger
     optimizer = build_optimizer(model, cfg.optimizer, dtype=dtype)
     ocfg = cfg.get("optimizer_config") or {}
     clip = _cfg_get(ocfg, "grad_clip")
-    lrc = cfg.get("lr_config") or {}
-    if _cfg_get(lrc, "policy", "step") != "step":
-        raise NotImplementedError("lr_config policy %r: 'step' is built (the MVFNet configs' policy)" % _cfg_get(lrc, "policy"))
     steps = _cfg_get(lrc, "step", ())
     ck = cfg.get("checkpoint_config") or {}
     lg = cfg.get("log_config") or {}
@@ -523,7 +648,7 @@ def train_network(model, dataset, cfg, distributed=False, validate=False, logger
                     warmup_iters=_cfg_get(lrc, "warmup_iters", 0), warmup_ratio=_cfg_get(lrc, "warmup_ratio", 0.1),
                     lr_gamma=_cfg_get(lrc, "gamma", 0.1), ckpt_interval=_cfg_get(ck, "interval", 0) or 0,
                     log_interval=_cfg_get(lg, "interval", 0) or 0, logger=log, optimizer=optimizer, accumulate=accumulate, ema=ema, precise_bn=precise_bn,
-                    nonfinite_guard=nonfinite_guard)
+                    nonfinite_guard=nonfinite_guard, lr_policy=lr_policy)
     if clip and _cfg_get(clip, "norm_type", 2) != 2:
         raise NotImplementedError("grad_clip norm_type %r: the fused clip is the L2 norm" % _cfg_get(clip, "norm_type"))
     if validate:

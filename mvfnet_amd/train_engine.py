@@ -1341,8 +1341,15 @@ class _ParamStore(object):
         return tabs[key]
 
     def apply_sgd(self, lr=None, world=1):
-        """clip_grad_norm_(max_norm) + SGD on the flat buffers (gradient scaled by 1 / world): one fused launch sequence."""
-        return self._apply_sgd(self.flat_grads, 1.0 / world, lr)
+        """clip_grad_norm_(max_norm) + the selected optimizer (SGD, or Adam / AdamW: see `optimizer`) on the flat buffers (gradient scaled by 1 / world): one
+        fused launch sequence."""
+        return self._apply_optimizer(self.flat_grads, 1.0 / world, lr)
+
+    def _apply_optimizer(self, grads, grad_scale, lr=None):
+        """What every optimizer path goes through (apply_sgd, step, train_step, apply_accumulated): the SGD sequence below, or mvf_adamw_step when selected."""
+        if self._adam is not None:
+            return self._apply_adamw(grads, grad_scale, lr)
+        return self._apply_sgd(grads, grad_scale, lr)
 
     def _apply_sgd(self, grads, grad_scale, lr=None):
         """The optimizer's launch sequence on `grads` (a flat fp32 tensor laid out like flat_grads: flat_grads itself, or the accumulator of
@@ -1389,11 +1396,100 @@ class _ParamStore(object):
             ema = (_p(self.flat_ema[off:]), C.c_float(_ema_momentum_at(self.ema_momentum, self.ema_warmup_steps, self.ema_updates)))
             self.ema_updates += 1
         check(lib.mvf_sgd_step_guarded(*(args + ema + (_p(g["buf"]),) + tail)), "sgd step (guarded)")
+        self._guard_restore()
+
+    def _guard_restore(self):
+        """Behind a guarded optimizer step: the conditional restore of the BatchNorm statistics snapshot taken before the step's first forward."""
+        g = self._guard
         snap, g["snap"] = g["snap"], None
         if snap is not None:
             tab, flat_stats = snap
             check(lib.mvf_bn_stats_restore(_p(tab.dev), tab.nseg, tab.n, _p(flat_stats), _p(self._nbt_flat), self._nbt_flat.numel(), _p(g["nbt"]), _p(g["buf"]),
                                            _st()), "bn stats restore")
+
+    # ---- Adam / AdamW: the fused step of mvf_adamw_step in place of the SGD sequence -----------------------------------------------------------------------
+    # Selected with TrainEngine(optimizer='adamw' | 'adam', betas=, eps=) or by assigning `optimizer` before the first step.  flat_mom serves as exp_avg; flat_var
+    # (exp_avg_sq, laid out like flat_params) and the 8-byte device step counter exist only while selected.  The counter holds the APPLIED steps: the lane that
+    # finishes the clip norm increments it, except for a step the non-finite guard skips, so the bias correction after a skipped step uses the t torch would
+    # (GradScaler does not call optimizer.step()).  The host never reads it outside optimizer_state_dict().  trainable_offset() / _segments() cut off a frozen
+    # prefix and handle paramwise options and scattered frozen parameters exactly as for SGD; lr is the engine's lr (or the step's), weight_decay the engine's.
+    # An engine that never selects it allocates and launches exactly what it did (flat_var is None, _apply_optimizer goes straight to _apply_sgd).
+    _adam = None
+    flat_var = None
+
+    @property
+    def optimizer(self):
+        """'sgd' (default), 'adamw' (decoupled weight decay: p *= 1 - lr * wd) or 'adam' (g += wd * p).  Assignable before the engine's first step."""
+        return "sgd" if self._adam is None else ("adamw" if self._adam["decoupled"] else "adam")
+
+    @optimizer.setter
+    def optimizer(self, kind):
+        self.set_optimizer(kind)
+
+    betas = property(lambda self: self._adam["betas"] if self._adam is not None else None)
+    eps = property(lambda self: self._adam["eps"] if self._adam is not None else None)
+
+    def set_optimizer(self, kind, betas=None, eps=None):
+        """Select the optimizer; betas / eps (Adam forms only) default to what is set, else (0.9, 0.999) / 1e-8.  Changing the KIND is allowed before the first
+        step only: the moments of one optimizer mean nothing to another."""
+        kind = str(kind).lower()
+        if kind not in ("sgd", "adamw", "adam"):
+            raise ValueError("optimizer %r: the fused HIP optimizers are 'sgd', 'adamw' and 'adam'" % (kind,))
+        if not self.rehomed:
+            raise RuntimeError("set_optimizer: this store does not own its parameters (stand-alone Bottleneck.forward)")
+        if kind != self.optimizer and self.steps > 0:
+            raise RuntimeError("the optimizer cannot be switched from %r to %r after the engine's first step" % (self.optimizer, kind))
+        if kind == "sgd":
+            if betas is not None or eps is not None:
+                raise ValueError("betas / eps belong to optimizer='adamw' | 'adam'")
+            self._adam = self.flat_var = None
+            return
+        old = self._adam or {}
+        betas = tuple(float(b) for b in (betas if betas is not None else old.get("betas", (0.9, 0.999))))
+        eps = float(eps if eps is not None else old.get("eps", 1e-8))
+        if len(betas) != 2 or not all(0.0 <= b < 1.0 for b in betas):
+            raise ValueError("betas must be two numbers in [0, 1), got %r" % (betas,))
+        if not eps > 0.0:
+            raise ValueError("eps must be positive, got %r" % (eps,))
+        if self._adam is None:
+            self.flat_var = torch.zeros_like(self.flat_params)          # new allocations beside the others: no recorded plan holds their addresses
+            self._adam = dict(count=torch.zeros(1, dtype=torch.int64, device=self.device), hyper=_lib.AdamwHyper())
+        self._adam.update(decoupled=int(kind == "adamw"), betas=betas, eps=eps)
+
+    def applied_steps(self):
+        """The device counter of APPLIED Adam / AdamW steps (skipped ones do not count).  An 8-byte read that waits for the device: checkpoint time only."""
+        if self._adam is None:
+            raise RuntimeError("applied_steps: the optimizer is SGD")
+        return int(self._adam["count"].item())
+
+    def _apply_adamw(self, grads, grad_scale, lr=None):
+        """mvf_adamw_step on `grads` scaled by grad_scale: norm + clip + Adam / AdamW (+ the averaged weights, + the guard) in one launch sequence."""
+        off = self.trainable_offset()
+        n = self.flat_params.numel() - off
+        if n <= 0:
+            return None
+        if self._ema_swapped:
+            raise RuntimeError("apply_sgd inside averaged_weights(): the parameters are the averaged ones; leave the block before training")
+        a = self._adam
+        ws = self.workspace(lib.mvf_adamw_workspace_bytes(n))
+        h = a["hyper"]
+        h.lr, h.weight_decay = float(self.lr if lr is None else lr), float(self.weight_decay or 0.0)
+        h.beta1, h.beta2, h.eps, h.decoupled = a["betas"][0], a["betas"][1], a["eps"], a["decoupled"]
+        tab, nseg = (None, 0)
+        if self.param_options or self._scattered_frozen:
+            tab, nseg = self._segments(off)
+        ema, ema_m = None, 0.0
+        if self.flat_ema is not None:
+            ema, ema_m = _p(self.flat_ema[off:]), _ema_momentum_at(self.ema_momentum, self.ema_warmup_steps, self.ema_updates)
+            self.ema_updates += 1
+        guard = _p(self._guard["buf"]) if self._guard is not None else None
+        check(lib.mvf_adamw_step(_p(self.flat_params[off:]), _p(grads[off:]), _p(self.flat_mom[off:]), _p(self.flat_var[off:]), n, C.c_float(grad_scale),
+                                 C.c_float(self.max_norm or 0.0), C.byref(h), _p(tab) if tab is not None else None, nseg, ema, C.c_float(ema_m), guard,
+                                 _p(a["count"]), _p(self.norm_out), _p(ws), ws.numel(), _st()), "adamw step")
+        if self._guard is not None:
+            self._guard_restore()
+        self.steps += 1
+        return self.norm_out
 
     # ---- averaged weights: an exponential moving average of the parameters, one update per OPTIMIZER step ------------------------------------------------
     # e' = fmaf(m_t, p' - e, e) in fp32 (csrc/common.h ema_step), m_t = ema.momentum_at(momentum, warmup_steps, t).  flat_ema is laid out like flat_params; the
@@ -1519,6 +1615,8 @@ class _ParamStore(object):
         """What torch.optim.SGD(model.parameters(), ...).state_dict() would hold after the same steps: per-parameter
         `momentum_buffer` in model.parameters() order + one param group -- so `{meta, state_dict, optimizer}` checkpoints written
         here resume under the reference's runner (optimizer.load_state_dict) and the other way round."""
+        if self._adam is not None:
+            return self._adamw_state_dict()
         from .checkpoint import sgd_state_dict
         params = list(self.model.parameters())
         off = self.trainable_offset()
@@ -1534,6 +1632,8 @@ class _ParamStore(object):
 
     def load_optimizer_state_dict(self, opt):
         """Accepts torch.optim.SGD's state_dict (the reference's checkpoints) or round 1's {'momentum_buffer': flat, 'steps': n}."""
+        if self._adam is not None:
+            return self._load_adamw_state_dict(opt)
         from .checkpoint import sgd_momentum_buffers
         if "momentum_buffer" in opt and "state" not in opt:          # round-1 layout of this repo
             self.flat_mom.copy_(opt["momentum_buffer"].to(self.flat_mom.device))
@@ -1555,6 +1655,54 @@ class _ParamStore(object):
             if k in group:          # (per-parameter groups carry multiplied lr / weight_decay values: the base values stay the engine's)
                 setattr(self, k, group[k])
         self.steps = max(self.steps, 1) if any_buf else 0          # torch creates a buffer at a parameter's first step
+
+    def _adamw_state_dict(self):
+        """torch.optim.AdamW's / Adam's wire format after the same steps: `step` (float32 scalar = the device counter of applied steps), `exp_avg`, `exp_avg_sq`
+        per stepped parameter; one param group, or one per parameter under paramwise options.  Reading the counter waits for the device."""
+        from .checkpoint import adamw_state_dict
+        a = self._adam
+        params = list(self.model.parameters())
+        off = self.trainable_offset()
+        t = self.applied_steps()
+        ms, vs = [], []
+        for p in params:
+            first = self._grad_view[id(p)].storage_offset()
+            stepped = t > 0 and first >= off and p.requires_grad
+            ms.append(self.flat_mom[first:first + p.numel()].view(p.shape).detach().cpu().clone() if stepped else None)
+            vs.append(self.flat_var[first:first + p.numel()].view(p.shape).detach().cpu().clone() if stepped else None)
+        mult = [self.param_options.get(id(p), (1.0, 1.0)) for p in params] if self.param_options else None
+        return adamw_state_dict(t, ms, vs, self.lr, a["betas"], a["eps"], self.weight_decay, bool(a["decoupled"]), multipliers=mult,
+                                initial_lr=getattr(self, "initial_lr", None))
+
+    def _load_adamw_state_dict(self, opt):
+        """Inverse: torch.optim.AdamW's / Adam's state_dict into flat_mom / flat_var and the device counter.  With one param group its lr, betas, eps and
+        weight_decay become the engine's (per-parameter groups carry multiplied values: the base values stay the engine's)."""
+        from .checkpoint import adamw_moments
+        params = list(self.model.parameters())
+        t, ms, vs, group = adamw_moments(opt, len(params))
+        if "decoupled_weight_decay" in group and bool(group["decoupled_weight_decay"]) != bool(self._adam["decoupled"]):
+            raise ValueError("optimizer state: written by %s, the engine's optimizer is %r" % ("AdamW" if group["decoupled_weight_decay"] else "Adam", self.optimizer))
+        for p, m, v in zip(params, ms, vs):
+            if m is not None and (tuple(m.shape) != tuple(p.shape) or tuple(v.shape) != tuple(p.shape)):
+                raise ValueError("optimizer state: exp_avg %s / exp_avg_sq %s do not match parameter %s" % (tuple(m.shape), tuple(v.shape), tuple(p.shape)))
+        self.flat_mom.zero_()
+        self.flat_var.zero_()
+        any_state = False
+        for p, m, v in zip(params, ms, vs):
+            if m is None:
+                continue
+            first = self._grad_view[id(p)].storage_offset()
+            self.flat_mom[first:first + p.numel()].view(p.shape).copy_(m.to(device=self.device, dtype=torch.float32))
+            self.flat_var[first:first + p.numel()].view(p.shape).copy_(v.to(device=self.device, dtype=torch.float32))
+            any_state = True
+        self._adam["count"].fill_(int(t) if any_state else 0)
+        if "betas" in group:
+            self.set_optimizer(self.optimizer, betas=group["betas"], eps=group.get("eps"))
+        if len(opt["param_groups"]) == 1:
+            for k in ("lr", "weight_decay"):
+                if k in group:
+                    setattr(self, k, group[k])
+        self.steps = max(self.steps, 1) if any_state else 0
 
     def attach_grads(self):
         """Expose the flat gradient views as .grad of the parameters (for external optimizers / inspection)."""
@@ -1607,12 +1755,16 @@ class BlockTrainer(_ParamStore):
 class TrainEngine(_ParamStore):
     """One-GPU training step for a mvfnet_amd Recognizer2D (fp32)."""
 
-    def __init__(self, model, lr=0.015, momentum=0.9, weight_decay=1e-4, max_norm=40.0, dtype=torch.float32):
-        """dtype = storage type of activations and packed weights (float32 | bfloat16).  With bfloat16 the accumulation,
+    def __init__(self, model, lr=0.015, momentum=0.9, weight_decay=1e-4, max_norm=40.0, dtype=torch.float32, optimizer="sgd", betas=None, eps=None):
+        """optimizer = 'sgd' (default) | 'adamw' | 'adam' with betas = (0.9, 0.999), eps = 1e-8: the fused Adam forms (_ParamStore.set_optimizer); lr and
+        weight_decay are then theirs, momentum is unused.
+        dtype = storage type of activations and packed weights (float32 | bfloat16).  With bfloat16 the accumulation,
         BatchNorm statistics, all parameter gradients, the master weights and the optimizer stay fp32 (what the
         reference's own fp16 mode keeps in fp32, codes/core/fp16/hooks.py:12-136; no loss scaling is needed for bf16)."""
         self._init_store(model, dtype)
         self.lr, self.momentum, self.weight_decay, self.max_norm = lr, momentum, weight_decay, max_norm
+        if str(optimizer).lower() != "sgd" or betas is not None or eps is not None:
+            self.set_optimizer(optimizer, betas=betas, eps=eps)
         bb = model.backbone
         self.stem, self.stem_bn = _TConv(bb.conv1, self, stem=True), _BN(bb.bn1, self, "bn1")
         self.blocks = [_TBlock(blk, self) for name in bb.res_layers for blk in getattr(bb, name)]
@@ -1771,7 +1923,7 @@ class TrainEngine(_ParamStore):
     def _uses_soft_head(self, lab):
         return self.blending is not None or self.label_smooth_eps > 0.0 or lab.is_floating_point()
 
-    def set_options(self, lr=None, momentum=None, weight_decay=None, max_norm=None, dtype=None):
+    def set_options(self, lr=None, momentum=None, weight_decay=None, max_norm=None, dtype=None, optimizer=None, betas=None, eps=None):
         """Update the optimizer hyper-parameters of an existing engine (Recognizer2D.train_engine(**opt) on a model that already
         has one); the storage dtype is fixed at construction."""
         if dtype is not None and dtype != self.tdtype:
@@ -1779,6 +1931,8 @@ class TrainEngine(_ParamStore):
         for k, v in (("lr", lr), ("momentum", momentum), ("weight_decay", weight_decay), ("max_norm", max_norm)):
             if v is not None:
                 setattr(self, k, v)
+        if optimizer is not None or betas is not None or eps is not None:
+            self.set_optimizer(optimizer if optimizer is not None else self.optimizer, betas=betas, eps=eps)
 
     def _forward(self, imgs, labels, stages=None, prepared=None):
         b, t = imgs.shape[0], imgs.shape[1]
@@ -2194,7 +2348,7 @@ class TrainEngine(_ParamStore):
                 import torch.distributed as dist
                 dist.all_reduce(self.flat_acc)
                 world = dist.get_world_size()
-            if self._apply_sgd(self.flat_acc, 1.0 / (count * world), lr) is not None:
+            if self._apply_optimizer(self.flat_acc, 1.0 / (count * world), lr) is not None:
                 for m_ in (self.model.backbone, self.model.cls_head):
                     if hasattr(m_, "invalidate_engine"):
                         m_.invalidate_engine()
