@@ -756,6 +756,34 @@ size_t mvf_adamw_workspace_bytes(long n);
 int mvf_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long n, float grad_scale, float max_norm,
                    const mvf_adamw_hyper_t* hyper, const mvf_sgd_segment_t* segments, int nseg, float* ema, float ema_momentum, int* guard,
                    long long* applied_steps, float* norm_out, void* ws, size_t ws_bytes, void* stream);
+/* Device-side accuracy: top-k hits and confusion counts of a (rows, classes) fp32 score matrix against integer labels, summed into a state array that stays
+ * on the device (evaluation without one readback per video, training accuracy in the log without a readback per step).
+ *
+ * state: a flat int64 array in device memory, 8-byte aligned, owned by the caller, zero at the start of a window; mvf_metrics_state_words(classes,
+ * with_confusion) words (0 for classes < 1, or for classes * classes beyond int32 with the matrix on).  int64 so that a SUM all-reduce of the array merges ranks.
+ *   word 0          rows seen
+ *   word 1          rows whose label is outside [0, classes)
+ *   word 2          rows holding a NaN score
+ *   words 3..7      reserved (zero)
+ *   words 8..15     hits for ks[0..nk)                               (MVF_METRICS_HITS; words 8 + nk .. 15 stay zero)
+ *   words 16..      only with_confusion: the classes x classes confusion matrix, row = real label, column = prediction      (MVF_METRICS_CONFUSION)
+ *
+ * Per row, with label y and scores s:
+ *   - a label outside [0, classes), or a NaN anywhere in the row, increments word 1 or word 2 (a bad label wins; word 0 as well) and touches nothing else;
+ *     for a bad label no score of the row -- and no memory outside the row -- is read.  rank_out / pred_out get -1 for such a row.
+ *   - rank = #{j : s_j > s_y, or s_j == s_y and j < y}; hit_k holds iff rank < k.  Ties go to the lower class index; +inf and -inf are ordinary values.
+ *   - pred = the lowest index of the maximum (np.argmax of a NaN-free row).  Hence hits(k = 1) == trace(confusion).
+ *   - k >= classes always hits on a valid row.
+ * rank_out / pred_out: NULL, or `rows` ints each in device memory (the per-row record: a whole-dataset prediction dump in one read).
+ * One wavefront per row with a strided loop over the classes (any classes >= 1); counters are integers added with integer atomics (per workgroup in LDS,
+ * then one global atomic per non-zero word), so the state does not depend on the order of accumulation.  Asynchronous on `stream`.
+ * ks is HOST memory, read during the call.  Checked before any launch: a NULL scores / labels / state / ks, or a misaligned operand (labels and state 8
+ * bytes, the others 4) is MVF_EINVAL; classes < 1, rows < 0, nk outside [1, 8], any k < 1, or classes * classes beyond int32 with the matrix on is
+ * MVF_ESHAPE.  rows == 0 is MVF_OK without a launch. */
+enum { MVF_METRICS_ROWS = 0, MVF_METRICS_BAD_LABEL = 1, MVF_METRICS_NAN_ROWS = 2, MVF_METRICS_HITS = 8, MVF_METRICS_MAX_K = 8, MVF_METRICS_CONFUSION = 16 };
+size_t mvf_metrics_state_words(int classes, int with_confusion);
+int mvf_metrics_update(const float* scores, int rows, int classes, const long long* labels, const int* ks, int nk, long long* state, int with_confusion,
+                       int* rank_out, int* pred_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * [r6] Launch-table replay.  One training step (the reference's batch_processor + DistOptimizerHook.after_train_iter, codes/core/train.py:45-60,

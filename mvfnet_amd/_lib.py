@@ -16,6 +16,7 @@ MVF_F32, MVF_BF16 = 0, 1
 MVF_NCHW, MVF_NHWC = 0, 1
 VIEW_T, VIEW_H, VIEW_W = 1, 2, 4
 MODE_BITS = {"T": 1, "TH": 3, "THW": 7}
+METRICS_ROWS, METRICS_BAD_LABEL, METRICS_NAN_ROWS, METRICS_HITS, METRICS_MAX_K, METRICS_CONFUSION = 0, 1, 2, 8, 8, 16      # state words of mvf_metrics_update
 ERRNAMES = {-1: "MVF_EINVAL", -2: "MVF_ESHAPE", -3: "MVF_EWS", -4: "MVF_EHIP", -5: "MVF_EUNSUPPORTED"}
 
 
@@ -296,6 +297,10 @@ def _load():
     lib.mvf_adamw_workspace_bytes.argtypes = [i64]
     lib.mvf_adamw_step.restype = i32
     lib.mvf_adamw_step.argtypes = [fp, fp, fp, fp, i64, f32, f32, C.POINTER(AdamwHyper), vp, i32, fp, f32, vp, vp, fp, vp, sz, vp]
+    lib.mvf_metrics_state_words.restype = sz
+    lib.mvf_metrics_state_words.argtypes = [i32, i32]
+    lib.mvf_metrics_update.restype = i32
+    lib.mvf_metrics_update.argtypes = [fp, i32, i32, ll, vp, i32, ll, i32, vp, vp, vp]
     lib.mvf_plan_run.restype = i32
     lib.mvf_plan_run.argtypes = [C.POINTER(PlanOp), i32, C.POINTER(C.c_ulonglong), C.POINTER(C.c_float), C.POINTER(C.c_int)]
     # Callers pass device pointers as plain Python ints (train_engine._p): without declared argtypes ctypes would truncate them to c_int silently.  Every

@@ -87,23 +87,61 @@ class EvalTopKAccuracyHook(object):
     (eval_hooks.py:17-104; the reference exchanges pickled temp files through `work_dir`, here the rows travel as one
     all_gather of float tensors)."""
 
-    def __init__(self, loader, labels, interval=1, k=(1, 5), weights="live"):
+    def __init__(self, loader, labels, interval=1, k=(1, 5), weights="live", on_device=False, mean_class=False):
         """weights = 'live' (the parameters being trained), 'ema' (the averaged parameters the engine keeps: Runner(ema=...) / cfg.ema_config; scored inside
-        engine.averaged_weights(), figures labelled 'ema top1 acc', ...) or 'both' (two passes over the validation set, both sets of figures)."""
+        engine.averaged_weights(), figures labelled 'ema top1 acc', ...) or 'both' (two passes over the validation set, both sets of figures).
+        on_device = True: the pass is runner.device_test -- no score row leaves the device, the hits are counted there (metrics.DeviceMetrics), one all-reduce
+        of the counters merges the ranks and ONE read ends the pass.  It needs one score row per video (test_cfg.average_clips 'prob' or 'score') and one
+        integer label per video; ties at the k-th place go to the lower class index, where the host path leaves them to numpy's argsort.
+        mean_class = True adds 'mean_class acc' (evaluation.mean_class_accuracy) to the figures of either path."""
         if weights not in WEIGHTS:
             raise ValueError("weights must be one of %s, got %r" % (", ".join(map(repr, WEIGHTS)), weights))
         self.loader, self.labels, self.interval, self.k, self.weights = loader, list(labels), interval, tuple(k), weights
+        self.on_device, self.mean_class = bool(on_device), bool(mean_class)
+        self._metrics, self._share = None, None      # the device counters (built at the first pass); (rank, world) of the loader's share, None = the process group's
         self.history = []
 
     def _score(self, runner, prefix):
+        if self.on_device:
+            return self._score_on_device(runner, prefix)
         from .runner import multi_gpu_test
         was_training = runner.model.training
         results = multi_gpu_test(runner.model, self.loader, size=len(self.labels))
         runner.model.train(was_training)
         if results is None:                          # not rank 0
             return None
-        acc = top_k_accuracy([np.asarray(r).squeeze() for r in results], self.labels, k=self.k)
-        return {"%stop%d acc" % (prefix, kk): float(a) for kk, a in zip(self.k, acc)}
+        rows = [np.asarray(r).squeeze() for r in results]
+        acc = top_k_accuracy(rows, self.labels, k=self.k)
+        out = {"%stop%d acc" % (prefix, kk): float(a) for kk, a in zip(self.k, acc)}
+        if self.mean_class:
+            out["%smean_class acc" % prefix] = float(mean_class_accuracy(np.stack(rows), np.asarray(self.labels[:len(rows)], dtype=np.int64)))
+        return out
+
+    def _score_on_device(self, runner, prefix):
+        from .dist import get_dist_info
+        from .metrics import DeviceMetrics
+        from .runner import device_test
+        model = runner.model.module if hasattr(runner.model, "module") else runner.model
+        test_cfg = getattr(model, "test_cfg", None)
+        if test_cfg is None or test_cfg.get("average_clips") is None:
+            raise ValueError("evaluation hook with on_device=True: test_cfg.average_clips=None leaves several score rows per video; the device counters "
+                             "take one row per video (average_clips='prob' or 'score'), or use the host path (on_device=False)")
+        if self._metrics is None:
+            self._metrics = DeviceMetrics(model.cls_head.num_classes, k=self.k, confusion=self.mean_class)
+        self._metrics.reset()
+        rank, world = self._share if self._share is not None else get_dist_info()
+        was_training = runner.model.training
+        device_test(runner.model, self.loader, self.labels, self._metrics, rank=rank, world=world)
+        runner.model.train(was_training)
+        if world > 1:
+            self._metrics.all_reduce()
+        fig = self._metrics.compute()                # every rank holds the figures; rank 0 reports them
+        if get_dist_info()[0] != 0:
+            return None
+        out = {"%stop%d acc" % (prefix, kk): float(fig["top%d" % kk]) for kk in self.k}
+        if self.mean_class:
+            out["%smean_class acc" % prefix] = float(fig["mean_class_acc"])
+        return out
 
     def after_train_epoch(self, runner):
         if (runner.epoch % self.interval) != 0:
@@ -176,7 +214,7 @@ class DistEvalTopKAccuracyHook(EvalTopKAccuracyHook):
     here -- pass the object).  Every rank scores items `rank::world` one by one, as DistEvalHook.after_train_epoch does
     (collate([data], samples_per_gpu=1) = a batch dimension of one), the rows are gathered on rank 0 and top-k accuracy is logged."""
 
-    def __init__(self, dataset, interval=1, k=(1,), dist=True, weights="live"):
+    def __init__(self, dataset, interval=1, k=(1,), dist=True, weights="live", on_device=False, mean_class=False):
         if isinstance(dataset, dict):
             raise TypeError("DistEvalTopKAccuracyHook: a dataset CONFIG dict needs the reference's dataset classes (out of scope here); "
                             "pass the Dataset object")
@@ -184,7 +222,9 @@ class DistEvalTopKAccuracyHook(EvalTopKAccuracyHook):
             raise TypeError("dataset must be a Dataset object or a dict, not {}".format(type(dataset)))      # the reference's message
         self.dataset, self.dist = dataset, dist
         labels = [dataset.video_infos[i]["label"] for i in range(len(dataset))]
-        super().__init__(_RankShare(dataset, dist), labels, interval, k, weights)
+        super().__init__(_RankShare(dataset, dist), labels, interval, k, weights, on_device=on_device, mean_class=mean_class)
+        if not dist:
+            self._share = (0, 1)                     # every process scores every video: nothing to merge
 
 
 class _RankShare(object):

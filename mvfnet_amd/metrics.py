@@ -1,0 +1,153 @@
+"""Device-side accuracy: top-k hits and confusion counts that stay on the device (csrc/metrics.hip, mvf_metrics_update).
+
+`DeviceMetrics` owns the int64 state array whose layout include/mvfnet_hip.h publishes.  `update()` is one asynchronous launch on the current stream,
+`all_reduce()` one SUM collective of the array, and `compute()` the ONE call that waits for the device: evaluation reads a few words per pass
+(runner.device_test, EvalTopKAccuracyHook(on_device=True)) instead of one score row per video, and the train engine counts every step's score matrix for the
+log line (TrainEngine.enable_train_accuracy, Runner(train_accuracy=...)).  The rules -- ties to the lower class index, rows with a bad label or a NaN counted
+apart -- are the header's; tests/metrics_numpy.py restates them in numpy.
+
+`check_train_accuracy` is the configuration check of the runner option, beside guard.check_nonfinite_guard."""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+
+HEADER_WORDS = _lib.METRICS_CONFUSION
+MAX_K = _lib.METRICS_MAX_K
+TRAIN_ACCURACY_KEYS = ("k",)
+TRAIN_ACCURACY_DEFAULTS = dict(k=(1, 5))
+
+
+def check_k(k, who="k"):
+    """A tuple of 1..8 integers >= 1 (an int is taken as a 1-tuple; a bool is not an integer here)."""
+    if isinstance(k, (int, np.integer)) and not isinstance(k, bool):
+        k = (k,)
+    if not isinstance(k, (tuple, list)) or not 1 <= len(k) <= MAX_K:
+        raise ValueError("%s must be a tuple of 1 to %d integers >= 1, got %r" % (who, MAX_K, k))
+    for v in k:
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError("%s must be a tuple of 1 to %d integers >= 1, got %r" % (who, MAX_K, k))
+    return tuple(int(v) for v in k)
+
+
+def check_train_accuracy(cfg):
+    """cfg.train_accuracy / Runner(train_accuracy=): None (off) or dict(k=(1, 5)); an empty dict gives the default.  Returns None or a dict with the key; an
+    unknown key, or a k that is not 1 to 8 integers >= 1, is refused.  The log line shows one `top<k>` figure per entry of k."""
+    if cfg is None:
+        return None
+    if not hasattr(cfg, "keys"):
+        raise ValueError("train_accuracy must be None or dict(k=(1, 5)), got %r" % (cfg,))
+    unknown = sorted(k for k in cfg.keys() if k not in TRAIN_ACCURACY_KEYS)
+    if unknown:
+        raise ValueError("train_accuracy: unknown key %s (known: %s)" % (", ".join(map(repr, unknown)), ", ".join(TRAIN_ACCURACY_KEYS)))
+    out = dict(TRAIN_ACCURACY_DEFAULTS)
+    out.update({k: cfg[k] for k in cfg.keys()})
+    return dict(k=check_k(out["k"], "train_accuracy: k"))
+
+
+def mean_class_from_confusion(cf):
+    """evaluation.mean_class_accuracy from the full classes x classes matrix: the mean, over the classes that occur as a label or as a prediction, of
+    hits / videos of the class; a class that is only predicted contributes 0.  nan when the matrix is empty."""
+    cf = np.asarray(cf, dtype=np.float64)
+    cnt, hit = cf.sum(axis=1), np.diag(cf)
+    occurs = (cnt > 0) | (cf.sum(axis=0) > 0)
+    if not occurs.any():
+        return float("nan")
+    return float(np.mean(np.where(cnt > 0, hit / np.where(cnt > 0, cnt, 1.0), 0.0)[occurs]))
+
+
+def figures_from_state(state, num_classes, k, confusion, strict=True):
+    """The dict compute() returns, from a host copy of the state array."""
+    state = np.asarray(state, dtype=np.int64).reshape(-1)
+    want = HEADER_WORDS + (num_classes * num_classes if confusion else 0)
+    if state.size != want:
+        raise ValueError("metrics state of %d words for %d classes (confusion=%s): expected %d" % (state.size, num_classes, bool(confusion), want))
+    count, invalid, nan_rows = (int(state[i]) for i in (_lib.METRICS_ROWS, _lib.METRICS_BAD_LABEL, _lib.METRICS_NAN_ROWS))
+    if strict and (invalid or nan_rows):
+        raise ValueError("device metrics: %d of %d rows have a label outside [0, %d) and %d hold a NaN score; compute(strict=False) returns the figures "
+                         "with those rows counted as misses" % (invalid, count, num_classes, nan_rows))
+    out = dict(count=count)
+    for i, kk in enumerate(k):
+        out["top%d" % kk] = int(state[_lib.METRICS_HITS + i]) / count if count else float("nan")
+    cf = state[HEADER_WORDS:].reshape(num_classes, num_classes).copy() if confusion else None
+    out.update(mean_class_acc=mean_class_from_confusion(cf) if confusion else None, confusion=cf, invalid=invalid, nan_rows=nan_rows)
+    return out
+
+
+class DeviceMetrics(object):
+    """Top-k accuracy, mean class accuracy and the confusion matrix of everything passed to update() since the last reset(), counted on the device.
+
+        m = DeviceMetrics(400, k=(1, 5))
+        for scores, labels in ...:          # (rows, 400) fp32 and (rows,) int64, both on the device
+            m.update(scores, labels)        # one launch on the current stream, no readback
+        m.all_reduce()                      # under a process group: every rank then holds the totals
+        m.compute()                         # the one synchronising call: dict(count, top1, top5, mean_class_acc, confusion, invalid, nan_rows)
+
+    confusion=False keeps the 16 header words only (mean_class_acc and confusion come back as None).  record=n keeps the per-row rank (how many classes beat
+    the label; -1 for a bad row) and prediction of up to n rows in two int32 device arrays, filled at a running offset the host keeps: records()."""
+
+    def __init__(self, num_classes, k=(1, 5), confusion=True, record=0, device=None):
+        if isinstance(num_classes, bool) or not isinstance(num_classes, (int, np.integer)) or num_classes < 1:
+            raise ValueError("num_classes must be an integer >= 1, got %r" % (num_classes,))
+        if isinstance(record, bool) or not isinstance(record, (int, np.integer)) or record < 0:
+            raise ValueError("record must be an integer >= 0 (rows to keep), got %r" % (record,))
+        self.num_classes, self.k, self.confusion, self.record = int(num_classes), check_k(k), bool(confusion), int(record)
+        words = _lib.lib.mvf_metrics_state_words(self.num_classes, int(self.confusion))
+        if words == 0:
+            raise ValueError("num_classes=%d: the confusion matrix has more than 2^31 - 1 cells; pass confusion=False" % self.num_classes)
+        self.device = torch.device(device if device is not None else "cuda")
+        self.state = torch.zeros(words, dtype=torch.int64, device=self.device)
+        self._ks = (C.c_int * len(self.k))(*self.k)
+        self._rank = self._pred = None
+        if self.record:
+            self._rank = torch.full((self.record,), -1, dtype=torch.int32, device=self.device)
+            self._pred = torch.full((self.record,), -1, dtype=torch.int32, device=self.device)
+        self.recorded = 0            # rows in the record arrays: the running offset, kept on the host
+
+    def update(self, scores, labels):
+        """scores (rows, num_classes) fp32 contiguous, labels (rows,) or (rows, 1) int64, both on this object's device.  Asynchronous on the current stream."""
+        if not (torch.is_tensor(scores) and torch.is_tensor(labels) and scores.is_cuda and labels.is_cuda):
+            raise RuntimeError("DeviceMetrics.update: device tensors required (the host path is evaluation.top_k_accuracy); no CPU fallback")
+        if scores.device != self.state.device or labels.device != self.state.device:
+            raise RuntimeError("DeviceMetrics.update: scores on %s, labels on %s, state on %s" % (scores.device, labels.device, self.state.device))
+        if scores.dtype != torch.float32 or scores.dim() != 2 or scores.shape[1] != self.num_classes or not scores.is_contiguous():
+            raise ValueError("DeviceMetrics.update: scores must be a contiguous float32 (rows, %d) tensor, got %s %s" % (self.num_classes, scores.dtype, tuple(scores.shape)))
+        rows = scores.shape[0]
+        if labels.dtype != torch.int64 or tuple(labels.shape) not in ((rows,), (rows, 1)) or not labels.is_contiguous():
+            raise ValueError("DeviceMetrics.update: labels must be a contiguous int64 (%d,) or (%d, 1) tensor, got %s %s" % (rows, rows, labels.dtype, tuple(labels.shape)))
+        rank = pred = None
+        if self.record:
+            if self.recorded + rows > self.record:
+                raise RuntimeError("DeviceMetrics.update: %d rows after %d recorded ones do not fit record=%d" % (rows, self.recorded, self.record))
+            rank, pred = self._rank.data_ptr() + 4 * self.recorded, self._pred.data_ptr() + 4 * self.recorded
+        _lib.check(_lib.lib.mvf_metrics_update(scores.data_ptr(), rows, self.num_classes, labels.data_ptr(), self._ks, len(self.k), self.state.data_ptr(),
+                                               int(self.confusion), rank, pred, torch.cuda.current_stream(self.state.device).cuda_stream), "metrics_update")
+        if self.record:
+            self.recorded += rows
+
+    def reset(self):
+        self.state.zero_()
+        if self.record:
+            self._rank.fill_(-1)
+            self._pred.fill_(-1)
+        self.recorded = 0
+
+    def all_reduce(self):
+        """Sum the state over the default process group (every rank then holds the totals); nothing without one.  The record arrays stay per rank."""
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            dist.all_reduce(self.state)
+
+    def compute(self, strict=True):
+        """The one synchronising call: dict(count, top{k}..., mean_class_acc, confusion, invalid, nan_rows).  Top-k = hits / rows seen (bad rows are misses);
+        mean_class_acc by the formula of evaluation.mean_class_accuracy from the confusion matrix (an int64 (classes, classes) numpy array).  strict=True
+        raises ValueError naming the counts when a row had a label outside [0, num_classes) or a NaN score."""
+        return figures_from_state(self.state.cpu().numpy(), self.num_classes, self.k, self.confusion, strict)
+
+    def records(self):
+        """(rank, pred): the int32 device arrays of the rows recorded so far, in update order (views: one .cpu() each is the whole prediction dump)."""
+        if not self.record:
+            raise RuntimeError("DeviceMetrics.records: built with record=0")
+        return self._rank[:self.recorded], self._pred[:self.recorded]

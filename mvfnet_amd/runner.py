@@ -27,6 +27,7 @@ from .checkpoint import load_checkpoint, save_checkpoint
 from .dist import get_dist_info, init_dist  # noqa: F401  (re-exported: train_recognizer.py imports init_dist from the core package)
 from .ema import check_ema, check_precise_bn
 from .guard import check_nonfinite_guard
+from .metrics import check_train_accuracy
 
 
 def set_random_seed(seed):
@@ -406,8 +407,12 @@ class Runner(object):
 
     def __init__(self, model, work_dir=None, lr=0.015, momentum=0.9, weight_decay=1e-4, max_norm=40.0, lr_steps=(90, 130),
                  warmup_iters=25070, warmup_ratio=0.01, ckpt_interval=10, log_interval=20, logger=print, optimizer=None, dtype=None,
-                 warmup="linear", lr_gamma=0.1, accumulate=1, ema=None, precise_bn=None, nonfinite_guard=None, lr_policy=None):
-        """lr_policy = None (the step schedule of lr_steps / lr_gamma), dict(policy='cosine', min_lr= | min_lr_ratio=, by_epoch=True) or dict(policy='poly',
+                 warmup="linear", lr_gamma=0.1, accumulate=1, ema=None, precise_bn=None, nonfinite_guard=None, lr_policy=None, train_accuracy=None):
+        """train_accuracy = dict(k=(1, 5)) (an empty dict gives the default): the engine counts the top-k hits of every step's score matrix on the device
+        (TrainEngine.enable_train_accuracy: one small launch per forward, outside the launch plans) and the log line gains ` top1 %.4f top5 %.4f` -- the
+        accuracy over the steps since the previous log line -- after grad_norm, read where the loop synchronises anyway.  Steps under blending or with soft
+        labels are not counted; a window without counted rows logs nan.  Under a process group each rank counts its own share and rank 0 logs its own.
+        lr_policy = None (the step schedule of lr_steps / lr_gamma), dict(policy='cosine', min_lr= | min_lr_ratio=, by_epoch=True) or dict(policy='poly',
         power=1.0, min_lr=0.0, by_epoch=True): mmcv's CosineAnnealing / Poly updater hooks (cosine_lr / poly_lr) with the same warm-up on top; max_epochs and
         max_iters (optimizer steps) are learned in run().
         nonfinite_guard = dict(max_consecutive=100) (an empty dict gives the default): an optimizer step whose clip norm is not finite -- a NaN / inf in a
@@ -429,6 +434,7 @@ class Runner(object):
         self.ema = check_ema(ema)                    # (refused before anything is built)
         self.precise_bn = check_precise_bn(precise_bn)
         self.nonfinite_guard = check_nonfinite_guard(nonfinite_guard)
+        self.train_accuracy = check_train_accuracy(train_accuracy)
         if self.precise_bn is not None and self.precise_bn["weights"] != "live" and self.ema is None:
             raise ValueError("precise_bn: weights=%r needs averaged weights; set ema (ema_config) as well" % self.precise_bn["weights"])
         self.train_loader = None
@@ -453,6 +459,8 @@ class Runner(object):
             self.engine.enable_ema(**self.ema)
         if self.nonfinite_guard is not None:
             self.engine.enable_step_guard()
+        if self.train_accuracy is not None:
+            self.engine.enable_train_accuracy(**self.train_accuracy)
         if self.precise_bn is not None:
             from .evaluation import PreciseBNHook
             self.register_hook(PreciseBNHook(None, **self.precise_bn))
@@ -487,6 +495,14 @@ class Runner(object):
                 % (st["consecutive"], self.nonfinite_guard["max_consecutive"], self.iter - st["consecutive"] + 1, self.iter, self.epoch + 1))
         return " skipped %d" % st["skipped"]
 
+    def _accuracy_note(self):
+        """' top1 %.4f top5 %.4f' for the log line: the engine's window since the previous line (a synchronising 128-byte read, made on the logging rank only,
+        where the line's loss and norm are read anyway), or '' with the option off."""
+        if self.train_accuracy is None:
+            return ""
+        fig = self.engine.train_accuracy()
+        return "".join(" top%d %.4f" % (kk, fig["top%d" % kk]) for kk in self.train_accuracy["k"])
+
     def _apply_accumulated(self, rank):
         lr = self.current_lr()
         self.engine.apply_accumulated(lr=lr)
@@ -494,8 +510,8 @@ class Runner(object):
         if self.log_interval and self.iter % self.log_interval == 0:
             note = self._check_guard()               # on every rank: all of them take the same decisions, so all of them stop together
             if rank == 0:
-                self.log("Epoch [%d] iter %d lr %.5f loss_cls %.4f grad_norm %.3f%s" % (
-                    self.epoch + 1, self.iter, lr, float(self.engine.accumulated_loss), float(self.engine.norm_out[0]), note))
+                self.log("Epoch [%d] iter %d lr %.5f loss_cls %.4f grad_norm %.3f%s%s" % (
+                    self.epoch + 1, self.iter, lr, float(self.engine.accumulated_loss), float(self.engine.norm_out[0]), self._accuracy_note(), note))
 
     def _train_epoch_accumulated(self, loader, rank):
         """One micro-step per loader batch; the optimizer runs after every k-th batch and after the epoch's last one (a shorter trailing group is applied
@@ -524,8 +540,8 @@ class Runner(object):
             if self.log_interval and self.iter % self.log_interval == 0:
                 note = self._check_guard()           # on every rank: all of them take the same decisions, so all of them stop together
                 if rank == 0:
-                    self.log("Epoch [%d] iter %d lr %.5f loss_cls %.4f grad_norm %.3f%s" % (
-                        self.epoch + 1, self.iter, lr, float(loss), float(self.engine.norm_out[0]), note))
+                    self.log("Epoch [%d] iter %d lr %.5f loss_cls %.4f grad_norm %.3f%s%s" % (
+                        self.epoch + 1, self.iter, lr, float(loss), float(self.engine.norm_out[0]), self._accuracy_note(), note))
         self._check_guard()                          # always at epoch end, before a checkpoint is written
         self.epoch += 1
         if rank == 0 and self.work_dir and self.ckpt_interval and self.epoch % self.ckpt_interval == 0:
@@ -612,6 +628,8 @@ def train_network(model, dataset, cfg, distributed=False, validate=False, logger
     load_from, then run cfg.total_epochs.  cfg.ema_config = dict(momentum=..., warmup_steps=...) keeps averaged weights (Runner(ema=...)).
     cfg.precise_bn = dict(num_iters=..., interval=..., weights=...) recomputes the BatchNorm running statistics at epoch end (Runner(precise_bn=...)).
     cfg.nonfinite_guard = dict(max_consecutive=100) skips optimizer steps with a non-finite gradient norm on the device (Runner(nonfinite_guard=...)).
+    cfg.train_accuracy = dict(k=(1, 5)) adds the training top-k accuracy, counted on the device, to the log line (Runner(train_accuracy=...)).
+    cfg.evaluation = dict(on_device=True) makes the validation hook of `validate` count its hits on the device (runner.device_test) instead of gathering rows.
     cfg.optimizer_config.accumulate = k (an integer >= 1, default 1) makes one optimizer step of k loader batches
     (gradient accumulation, Runner(accumulate=k)).  `dataset`: a torch Dataset of dict(img_group, label) items, a ready loader, or an
     iterable of batches (or a list whose first entry is the training one).  `validate` registers the reference's
@@ -621,6 +639,7 @@ def train_network(model, dataset, cfg, distributed=False, validate=False, logger
     ema = check_ema(cfg.get("ema_config"))
     precise_bn = check_precise_bn(cfg.get("precise_bn"))
     nonfinite_guard = check_nonfinite_guard(cfg.get("nonfinite_guard"))
+    train_accuracy = check_train_accuracy(cfg.get("train_accuracy"))
     if precise_bn is not None and precise_bn["weights"] != "live" and ema is None:
         raise ValueError("precise_bn: weights=%r needs averaged weights; set ema_config as well" % precise_bn["weights"])
     lrc = cfg.get("lr_config") or {}
@@ -648,7 +667,7 @@ def train_network(model, dataset, cfg, distributed=False, validate=False, logger
                     warmup_iters=_cfg_get(lrc, "warmup_iters", 0), warmup_ratio=_cfg_get(lrc, "warmup_ratio", 0.1),
                     lr_gamma=_cfg_get(lrc, "gamma", 0.1), ckpt_interval=_cfg_get(ck, "interval", 0) or 0,
                     log_interval=_cfg_get(lg, "interval", 0) or 0, logger=log, optimizer=optimizer, accumulate=accumulate, ema=ema, precise_bn=precise_bn,
-                    nonfinite_guard=nonfinite_guard, lr_policy=lr_policy)
+                    nonfinite_guard=nonfinite_guard, lr_policy=lr_policy, train_accuracy=train_accuracy)
     if clip and _cfg_get(clip, "norm_type", 2) != 2:
         raise NotImplementedError("grad_clip norm_type %r: the fused clip is the L2 norm" % _cfg_get(clip, "norm_type"))
     if validate:
@@ -663,7 +682,9 @@ def train_network(model, dataset, cfg, distributed=False, validate=False, logger
                 raise NotImplementedError("validate=True: put the validation Dataset object under cfg.data.val (or a hook under cfg.eval_hook); "
                                           "building datasets from a config dict is out of scope")
             from .evaluation import DistEvalTopKAccuracyHook
-            runner.register_hook(DistEvalTopKAccuracyHook(val, interval=cfg.get("eval_interval", 1), k=(1, 5), dist=distributed))
+            ev = cfg.get("evaluation") or {}
+            runner.register_hook(DistEvalTopKAccuracyHook(val, interval=cfg.get("eval_interval", 1), k=(1, 5), dist=distributed,
+                                                          on_device=bool(_cfg_get(ev, "on_device", False))))
     if cfg.get("resume_from"):
         runner.resume(cfg.get("resume_from"))
     elif cfg.get("load_from"):
@@ -685,6 +706,45 @@ def single_gpu_test(model, loader):
                 img = img.cuda(non_blocking=True)
             results.append(model(return_loss=False, img_group=img))
     return results
+
+
+def device_test(model, loader, labels, metrics, rank=None, world=None):
+    """single_gpu_test without the per-video readback: every item's score rows stay on the device (forward_test(return_numpy=False)) and are counted there,
+    `metrics.update(score, labels[i : i + rows])` with i the item's index in the full label list -- `rank + n * world` for the n-th item of a rank that scores
+    the `rank::world` share, the order collect_results assumes.  `labels` (one integer per video; a list, an array, or an int64 device tensor) are uploaded once.  Nothing inside the loop waits for the
+    device; the caller ends the pass with metrics.all_reduce() / metrics.compute().  A failing launch raises from the forward as it always did.
+    rank / world default to the process group's.  Returns `metrics`."""
+    if rank is None or world is None:
+        rank, world = get_dist_info()
+    if torch.is_tensor(labels) and labels.is_cuda:       # already uploaded (int64, one per video)
+        lab_dev = labels.reshape(-1)
+    else:
+        try:
+            lab = np.asarray(labels.cpu() if torch.is_tensor(labels) else labels, dtype=np.int64).reshape(-1)
+        except (TypeError, ValueError):
+            raise ValueError("device_test: one integer label per video is required (multi-label videos: the host path, single_gpu_test + top_k_accuracy)")
+        lab_dev = torch.from_numpy(lab).to(metrics.state.device)
+    total = lab_dev.shape[0]
+    model.eval()
+    n = 0
+    with torch.no_grad():
+        for data in loader:
+            img = data["img_group"]
+            if torch.is_tensor(img) and not img.is_cuda and torch.cuda.is_available():
+                img = img.cuda(non_blocking=True)
+            score = model(return_loss=False, return_numpy=False, img_group=img)
+            score = score.reshape(-1, score.shape[-1])
+            rows = score.shape[0]
+            if world > 1 and rows != 1:
+                raise ValueError("device_test: %d score rows from one item of a rank::world share; a distributed pass takes one video per item" % rows)
+            i = rank + n * world
+            if i + rows > total:
+                raise ValueError("device_test: item %d brings rows [%d, %d) but there are %d labels" % (n, i, i + rows, total))
+            if score.dtype != torch.float32 or not score.is_contiguous():
+                score = score.float().contiguous()
+            metrics.update(score, lab_dev[i:i + rows])
+            n += rows
+    return metrics
 
 
 def collect_results(part, size=None):

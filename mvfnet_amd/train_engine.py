@@ -2202,7 +2202,13 @@ class TrainEngine(_ParamStore):
         if key is None:
             loss = self.forward(imgs, labels)
             self.backward(exchange=exchange)
-            return loss
+        else:
+            loss = self._planned_forward_backward(imgs, labels, key)
+        if self._train_acc is not None:
+            self._count_train_accuracy(imgs, labels)      # behind the plan-or-eager branch: never inside a recorded region
+        return loss
+
+    def _planned_forward_backward(self, imgs, labels, key):
         st = self.__dict__.setdefault("_plans", {}).setdefault(key, dict(eager=0, tries=0, cand=None, plan=None))
         prepared = self._step_tensors(imgs, labels)
         plan = st["plan"]
@@ -2292,6 +2298,43 @@ class TrainEngine(_ParamStore):
         check(lib.mvf_bn_stats_snapshot(_p(tab.dev), tab.nseg, tab.n, _p(flat), _p(self._nbt_flat), self._nbt_flat.numel(), _p(g["nbt"]),
                                         C.c_void_p(torch.cuda.current_stream().cuda_stream)), "bn stats snapshot")
         g["snap"] = ent
+
+    # ---- training accuracy: top-k hits of every step's score matrix, counted on the device ----------------------------------------------------------------
+    # The head leaves the step's (B, classes) scores in the persistent `scores` buffer; with the option on, ONE mvf_metrics_update (no confusion matrix: 16
+    # int64 words of state) reads it and the step's integer labels after forward + backward, on the launch stream, outside any launch plan: plans, plan keys
+    # and recorded signatures are what they were, and a replayed step is counted exactly like an eager one.  Steps without hard labels -- blending, or a
+    # floating-point label matrix -- are not counted (mmaction2 omits the figures there too); label smoothing over integer labels is.  Under accumulation
+    # every micro-step counts its own rows.  train_accuracy() is the one call that synchronises.  An engine that never enables it allocates and launches
+    # exactly what it did without it.
+    _train_acc = None
+
+    def enable_train_accuracy(self, k=(1, 5)):
+        """Start counting: a fresh window (metrics.DeviceMetrics without the confusion matrix; an allocation of its own, part of no plan key)."""
+        from .metrics import DeviceMetrics
+        self._train_acc = DeviceMetrics(self.num_classes, k=k, confusion=False, device=self.device)
+
+    def disable_train_accuracy(self):
+        self._train_acc = None
+
+    def train_accuracy(self):
+        """dict(count, top{k}..., invalid, nan_rows) of the rows counted since the last call, and the window starts again.  A 128-byte read that waits for the
+        device: the only synchronising call of the option.  Rows with a NaN score (a step the non-finite guard would skip) or a bad label are misses, reported
+        under nan_rows / invalid; top{k} is nan while the window is empty."""
+        if self._train_acc is None:
+            raise RuntimeError("train_accuracy: the option is off; call enable_train_accuracy() (Runner(train_accuracy=...), cfg.train_accuracy) first")
+        out = self._train_acc.compute(strict=False)
+        self._train_acc.reset()
+        return {k: v for k, v in out.items() if k not in ("mean_class_acc", "confusion")}
+
+    def _count_train_accuracy(self, imgs, labels):
+        if self.blending is not None or self._soft_labels(imgs, labels):
+            return                                   # no hard labels in this step
+        b = imgs.shape[0]
+        scores = self._bufs.get(("scores", (b, self.num_classes), torch.float32))
+        if scores is None:
+            raise RuntimeError("train accuracy: the step left no (%d, %d) score buffer" % (b, self.num_classes))
+        lab = labels.reshape(-1).to(device=imgs.device, dtype=torch.int64).contiguous()      # what _step_tensors made of them (no launch for int64 device labels)
+        self._train_acc.update(scores, lab)
 
     # ---- gradient accumulation: one optimizer step over k micro-batches (the reference's 8 ranks x 12 clips run one after another on one GPU) ------------
     # Micro-batch i's forward + backward leave g_i in flat_grads (the gradient of ITS mean loss under ITS OWN BatchNorm batch statistics: exactly what rank i of
