@@ -529,6 +529,27 @@ int mvf_ce_loss_soft(const float* scores, const float* targets, int clips, int c
 int mvf_head_train_fwd_soft(const void* feat, int clips, int t, int hw, int c, const float* fc_w, const float* fc_b, int classes,
                             const float* targets, const float* drop_mask /* (clips*t, c) pre-scaled keep mask or NULL */,
                             float* pooled, float* scores, float* dscores, float* loss_part, float* loss, int dtype, void* stream);
+/* RandomErasing (timm's, as PySlowFast and mmaction2 use it) on the stem operand, IN PLACE.  xp = (planes, hp, wp, 4) in `dtype` as mvf_stem_prep lays it
+ * out, 16-byte aligned; no plane reads another plane.  One table per step, three DEVICE arrays:
+ *   boxes int32  (planes, max_boxes, 5): y0, x0, y1, x1, mode -- a half-open box in image pixels (before the pad), 0 <= y0 <= y1 <= H, 0 <= x0 <= x1 <= W;
+ *                                        mode 0 = unused slot, 1 = constant colour, 2 = per-element noise, any other value = unused.  1 <= max_boxes <= 8;
+ *                                        where boxes of one plane overlap, the box with the higher index wins.
+ *   fill  fp32   (planes, max_boxes, 4): mode 1: the colour of channels 0..2 in normalised space, rounded once to `dtype`; word 3 is ignored
+ *   key   uint32 (2):                    the step's generator key (in device memory: a replayed launch plan gets fresh noise from the same address)
+ * Noise (mode 2), the specification: for image pixel (y, x) of plane p
+ *   (w0, w1, w2, w3) = Philox4x32-10(counter = (x, y, p, 0), key = (key[0], key[1]))       (Salmon et al., SC'11; multiply-high in plain integer arithmetic)
+ *   u1 = ((w0 >> 8) + 1) * 2^-24,  u2 = (w1 >> 8) * 2^-24,  u3 = ((w2 >> 8) + 1) * 2^-24,  u4 = (w3 >> 8) * 2^-24
+ *   channel 0 = sqrt(-2 ln u1) * cos(2 pi u2),  channel 1 = sqrt(-2 ln u1) * sin(2 pi u2),  channel 2 = sqrt(-2 ln u3) * cos(2 pi u4)
+ * N(0, 1) values with |n| <= sqrt(48 ln 2) < 5.77, each computed in fp32 with the accurate math functions (no fast intrinsics, no fast-math) and rounded once
+ * to `dtype`.  The counter holds image coordinates, never the storage layout: fp32 and bf16 operands see the same noise before the final rounding, and it
+ * depends neither on the box index nor on how the grid is cut.
+ * The border of `pad` pixels and the padding columns up to wp are never written; the fourth channel of an erased pixel is stored as the zero it already is;
+ * every element outside all boxes keeps its bits.  No atomics: bit-identical from run to run for the same table and key.  The kernel clamps every box to
+ * the operand's interior, (hp - 2 pad) x (wp - 2 pad), as mvf_stem_blend does: a bad table cannot address outside the tensor (rejecting bad tables is the caller's job: mvfnet_amd.erasing.check_erase_table).
+ * MVF_EINVAL: NULL pointer, dtype, max_boxes outside [1, 8], 2 * pad > hp or wp, misalignment; MVF_ESHAPE: a bf16 plane that is not a whole number of
+ * 16-byte units, a plane beyond int -- all before any launch. */
+int mvf_stem_erase(void* xp, int planes, int hp, int wp, int pad, const int* boxes, int max_boxes, const float* fill, const unsigned int* key, int dtype,
+                   void* stream);
 /* conv weight gradient dw_oihw (cout, cin_real, kh, kw_real) fp32; d describes the FORWARD conv (x dims, ho/wo = dz dims).
  * kw_packed*cin_packed == d->kw*d->cin; they differ from (kw_real, cin_real) only for the stem view (8x4 vs 7x3).
  * fp32 accumulation over the pixels in a fixed order (per-split partial tiles, then a split-lane reduce): deterministic, no atomics.  fp32

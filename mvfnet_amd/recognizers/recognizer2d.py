@@ -60,6 +60,10 @@ class Recognizer2D(nn.Module):
         from ..blending import build_blending
         blend_cfg = train_cfg.get("blending") if hasattr(train_cfg, "get") else getattr(train_cfg, "blending", None)
         self.blending = build_blending(blend_cfg)
+        # train_cfg=dict(erasing=dict(type='RandomErasing', probability=..., mode='pixel' | 'rand' | 'const', ...)): RandomErasing on the device, likewise
+        from ..erasing import build_erasing
+        erase_cfg = train_cfg.get("erasing") if hasattr(train_cfg, "get") else getattr(train_cfg, "erasing", None)
+        self.erasing = build_erasing(erase_cfg)
         self.module_cfg = dict(module_cfg) if module_cfg else module_cfg
         self.in_channels = 3
         if self.module_cfg:
@@ -138,16 +142,17 @@ class Recognizer2D(nn.Module):
         return self
 
     def _set_soft_options(self, eng, training):
-        """The ONE place train_cfg['blending'] and the head's label_smooth_eps reach the engine: only while the model trains.  Called when the engine is
-        created, whenever the mode changes (train() / eval()) and by forward_train.  engine.blending / engine.label_smooth_eps are plain attributes:
-        whoever drives engine.train_step directly may also set them by hand, until the next of these calls."""
+        """The ONE place train_cfg['blending'], train_cfg['erasing'] and the head's label_smooth_eps reach the engine: only while the model trains.  Called
+        when the engine is created, whenever the mode changes (train() / eval()) and by forward_train.  engine.blending / engine.erasing /
+        engine.label_smooth_eps are plain attributes: whoever drives engine.train_step directly may also set them by hand, until the next of these calls."""
         eng.blending = self.blending if training else None
+        eng.erasing = self.erasing if training else None
         eng.label_smooth_eps = float(getattr(self.cls_head, "label_smooth_eps", 0.0)) if training else 0.0
 
     def forward_train(self, imgs, labels, **kwargs):
         """imgs [B, T, 3, H, W], labels [B, 1] -> {'loss_cls': scalar tensor} (reference recognizer2d.py:132-149).
-        labels may also be a floating-point (B, num_classes) matrix of soft labels.  While self.training, train_cfg['blending'] (Mixup / CutMix) and the
-        head's label_smooth_eps are applied on the device (mvfnet_amd/blending.py).
+        labels may also be a floating-point (B, num_classes) matrix of soft labels.  While self.training, train_cfg['erasing'] (RandomErasing),
+        train_cfg['blending'] (Mixup / CutMix) and the head's label_smooth_eps are applied on the device (mvfnet_amd/erasing.py, mvfnet_amd/blending.py).
         The returned loss supports .backward(): gradients land in the parameters' .grad (copies of the engine's flat gradient
         buffer; after engine.attach_grads() the .grad tensors ARE views of it), as the reference's DistOptimizerHook expects.
         A gather table (preprocess.gather_rows: a `src` column) is refused with a ValueError: training makes one image per frame.  An

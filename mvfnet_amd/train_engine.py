@@ -1805,6 +1805,10 @@ class TrainEngine(_ParamStore):
         # (_plan_key); with None / 0.0 and integer labels the step issues exactly the launches it issued without them.
         self.blending, self.label_smooth_eps = None, 0.0
         self._blend_table = None
+        # RandomErasing (erasing.py: an object with draw(batch, t, h, w) -> (boxes, fill, key); None = off): a per-sample transform on the stem operand, before
+        # the blend.  Part of the plan key; with None the step issues exactly the launches it issued without it.
+        self.erasing = None
+        self._erase_table = None
 
     def _pack_all(self, kind):
         """All forward (kind 0) or data-gradient (kind 1) weight packs in ONE launch (mvf_pack_conv_weights_batched); the job
@@ -1867,6 +1871,17 @@ class TrainEngine(_ParamStore):
             rows, wts = self.blending.draw(b, h, w)
             check_blend_rows(rows, wts, b, h, w)
             self._blend_table = self._upload_blend_table(rows, wts, b)
+        self._erase_table = None
+        if self.erasing is not None:
+            # as above: key, boxes and colours live in a persistent device buffer filled here, so a replayed plan erases with each step's own table and noise
+            from .erasing import check_erase_table
+            b, t = imgs.shape[0], imgs.shape[1]
+            h, w = self._input_hw(imgs)
+            boxes, fill, key = self.erasing.draw(b, t, h, w)
+            check_erase_table(boxes, fill, key, b * t, h, w)
+            if getattr(self.erasing, "max_boxes", None) not in (None, boxes.shape[1]):     # (the plan key carries the width the object names)
+                raise ValueError("TrainEngine: the erasing table holds %d boxes per frame, its object names max_boxes=%r" % (boxes.shape[1], self.erasing.max_boxes))
+            self._erase_table = self._upload_erase_table(boxes, fill, key)
         mask = None
         if self.dropout > 0.0:
             nt, cc = imgs.shape[0] * imgs.shape[1], self.fc_w.shape[1]
@@ -1890,31 +1905,48 @@ class TrainEngine(_ParamStore):
             h, w = imgs.shape[3:]
         return int(h), int(w)
 
-    _BLEND_STAGES = 4       # pinned staging slots of the blending table: as many steps may be in flight before the host waits for the oldest copy
+    _TABLE_STAGES = 4       # pinned staging slots of a step table: as many steps may be in flight before the host waits for the oldest copy
 
-    def _upload_blend_table(self, rows, wts, b):
-        """ONE non-blocking host-to-device copy of the step's table: [rows (b, 5) int32 | wts (b, 2) fp32] packed as 7 b 32-bit words, from a pinned staging
-        slot (a copy from pageable memory would make the host wait for everything queued on the stream, i.e. for the previous step, and lose the
-        launch-ahead the plans exist for).  A slot is reused only after the copy that read it has completed (its event).  Returns the two device views
-        blend_rows (b, 5) int32 and blend_wts (b, 2) fp32 of the persistent buffer."""
+    def _upload_table(self, name, parts):
+        """ONE non-blocking host-to-device copy of a step's table: `parts` (numpy arrays of 32-bit elements) packed one after another as 32-bit words, from a
+        pinned staging slot (a copy from pageable memory would make the host wait for everything queued on the stream, i.e. for the previous step, and lose
+        the launch-ahead the plans exist for).  A slot is reused only after the copy that read it has completed (its event).  Returns one flat int32 device
+        view per part of the persistent buffer `name`."""
         import numpy as np
-        table = self.buf("blend_table", (7 * b,), torch.int32)
-        ring = self.__dict__.setdefault("_blend_stages", {}).get(b)
+        n = sum(int(p.size) for p in parts)
+        table = self.buf(name, (n,), torch.int32)
+        ring = self.__dict__.setdefault("_table_stages", {}).get((name, n))
         if ring is None:
-            ring = self._blend_stages[b] = dict(next=0, used=set(), slots=[(torch.empty(7 * b, dtype=torch.int32).pin_memory(), torch.cuda.Event())
-                                                                          for _ in range(self._BLEND_STAGES)])
+            ring = self._table_stages[(name, n)] = dict(next=0, used=set(), slots=[(torch.empty(n, dtype=torch.int32).pin_memory(), torch.cuda.Event())
+                                                                                   for _ in range(self._TABLE_STAGES)])
         k = ring["next"]
-        ring["next"] = (k + 1) % self._BLEND_STAGES
+        ring["next"] = (k + 1) % self._TABLE_STAGES
         host, ev = ring["slots"][k]
         if k in ring["used"]:
             ev.synchronize()
         hn = host.numpy()
-        hn[:5 * b] = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
-        hn[5 * b:] = np.ascontiguousarray(wts, dtype=np.float32).reshape(-1).view(np.int32)
+        views, off = [], 0
+        for p in parts:
+            hn[off:off + p.size] = p.reshape(-1).view(np.int32)
+            views.append(table[off:off + p.size])
+            off += p.size
         table.copy_(host, non_blocking=True)
         ev.record()
         ring["used"].add(k)
-        return table[:5 * b].view(b, 5), table[5 * b:].view(torch.float32).view(b, 2)
+        return views
+
+    def _upload_blend_table(self, rows, wts, b):
+        """[rows (b, 5) int32 | wts (b, 2) fp32] packed as 7 b words; returns the two device views blend_rows (b, 5) int32 and blend_wts (b, 2) fp32."""
+        import numpy as np
+        rows_d, wts_d = self._upload_table("blend_table", [np.ascontiguousarray(rows, dtype=np.int32), np.ascontiguousarray(wts, dtype=np.float32)])
+        return rows_d.view(b, 5), wts_d.view(torch.float32).view(b, 2)
+
+    def _upload_erase_table(self, boxes, fill, key):
+        """[key (2) uint32 | boxes (planes, max_boxes, 5) int32 | fill (planes, max_boxes, 4) fp32]; returns (boxes, fill, key) device views and max_boxes."""
+        import numpy as np
+        key_d, boxes_d, fill_d = self._upload_table("erase_table", [np.ascontiguousarray(key, dtype=np.uint32), np.ascontiguousarray(boxes, dtype=np.int32),
+                                                                    np.ascontiguousarray(fill, dtype=np.float32)])
+        return boxes_d, fill_d, key_d, int(boxes.shape[1])
 
     def _soft_labels(self, imgs, labels):
         """The caller hands the (B, num_classes) soft-label matrix itself (floating point) instead of integer labels."""
@@ -1959,6 +1991,10 @@ class TrainEngine(_ParamStore):
             self.input_pipeline.to_stem(imgs, self.input_window, 3, wp, self.tdtype, out=xp)
         else:
             check(lib.mvf_stem_prep(_p(x), nt, 3, h, w, 3, wp, _p(xp), self.dt, _st()), "stem_prep")
+        if self.erasing is not None:
+            # in place, per sample, BEFORE the batch blend (as in timm and mmaction2): saved['xp'] is the erased, then blended, operand
+            boxes_d, fill_d, key_d, max_boxes = self._erase_table
+            check(lib.mvf_stem_erase(_p(xp), nt, hp, wp, 3, _p(boxes_d), max_boxes, _p(fill_d), _p(key_d), self.dt, _st()), "stem_erase")
         if self.blending is not None:
             # out of place (clip i reads its partner clip); xp_blend is what the stem reads AND what backward's stem weight gradient sees (saved['xp'])
             rows_d, wts_d = self._blend_table
@@ -2150,6 +2186,8 @@ class TrainEngine(_ParamStore):
             return None
         if not all(m_.training for m_ in self._nbt_mods):
             return None                  # frozen statistics are folded per step by torch calls (_BN.use_running_stats)
+        if self.erasing is not None and getattr(self.erasing, "max_boxes", None) is None:
+            return None                  # an erasing object that does not name its table width (max_boxes) may change it from step to step
         sw = self.__dict__.get("_switch_names")
         if sw is None:
             sw = self._switch_names = sorted(k for c_ in type(self).__mro__ for k, v in vars(c_).items()
@@ -2157,7 +2195,9 @@ class TrainEngine(_ParamStore):
         return (tuple(imgs.shape), tuple(labels.shape), labels.dtype, str(imgs.device), torch.cuda.current_stream().cuda_stream, self._ddp_active(),
                 self.dropout > 0.0, tuple(p.requires_grad for p in self.model.parameters()), tuple(getattr(self, k) for k in sw),
                 # a plan recorded without blending / smoothing / soft labels is never replayed with them (other launches, and eps is a frozen float word)
-                self.blending is not None, float(self.label_smooth_eps), self._soft_labels(imgs, labels))
+                self.blending is not None, float(self.label_smooth_eps), self._soft_labels(imgs, labels)) + (
+                    # erasing off: the key of every existing configuration is what it was.  The table's width is a frozen integer word of the recorded call.
+                    (("erasing", int(self.erasing.max_boxes)),) if self.erasing is not None else ())
 
     def _record_step(self, imgs, labels, prepared):
         """One eager step with every library call and stream ordering recorded; returns (loss, Plan | None)."""
@@ -2245,7 +2285,7 @@ class TrainEngine(_ParamStore):
     # forward (under accumulation: before the group's first micro-step, so one poisoned micro-batch drops the whole group).  After a skipped step the model,
     # the optimizer state and the average are what they were before it: the run continues as if the batch had never been drawn.  Nothing is read back: the
     # host cannot know, so its counters (steps, ema_updates, the runner's iter, hence learning-rate and EMA warm-up schedules) count ATTEMPTED steps, as a
-    # scheduler does under torch's GradScaler; a skipped step still draws its dropout mask and blending table.  A skipped very first step is harmless: the
+    # scheduler does under torch's GradScaler; a skipped step still draws its dropout mask, blending and erasing tables.  A skipped very first step is harmless: the
     # momentum buffer is still zero and momentum * 0 + d is first_step's d (signs of zero may differ).  Under a process group the norm is taken after the
     # all-reduce, so every rank takes the same decision and rolls back its own statistics: no collective is added.  guard_state() is the one call that
     # synchronises.  Not covered: an external torch optimizer (attach_grads) and update_ema() behind one.  An engine that never enables the guard allocates
@@ -2303,7 +2343,8 @@ class TrainEngine(_ParamStore):
     # The head leaves the step's (B, classes) scores in the persistent `scores` buffer; with the option on, ONE mvf_metrics_update (no confusion matrix: 16
     # int64 words of state) reads it and the step's integer labels after forward + backward, on the launch stream, outside any launch plan: plans, plan keys
     # and recorded signatures are what they were, and a replayed step is counted exactly like an eager one.  Steps without hard labels -- blending, or a
-    # floating-point label matrix -- are not counted (mmaction2 omits the figures there too); label smoothing over integer labels is.  Under accumulation
+    # floating-point label matrix -- are not counted (mmaction2 omits the figures there too); label smoothing over integer labels is, and so are erased
+    # steps (their labels are hard).  Under accumulation
     # every micro-step counts its own rows.  train_accuracy() is the one call that synchronises.  An engine that never enables it allocates and launches
     # exactly what it did without it.
     _train_acc = None
@@ -2430,7 +2471,7 @@ class TrainEngine(_ParamStore):
     # Calibration = k forward-only training-mode batches; every statistics kernel computes (1 - m) r + m x, so with the by-value momentum argument of every
     # calibrated _BN at 1.0 the running buffers hold exactly the batch mean / unbiased batch variance after a forward, and ONE launch over a segment table
     # (csrc/precise_bn.hip) adds all ~140 buffers into an fp64 shadow array; one more launch at the end writes (float)(sum / k).  No backward, no optimizer, no
-    # average update, no blending table, no dropout draw (the torch generator is left where it was); the forwards run eagerly: launch plans are neither
+    # average update, no blending or erasing table, no dropout draw (the torch generator is left where it was); the forwards run eagerly: launch plans are neither
     # recorded nor touched, and their frozen momentum words stay valid because _BN.momentum is back at its value afterwards.  Under a process group every rank
     # calibrates its own statistics, as every rank keeps its own today.
     def _all_bns(self):
@@ -2485,7 +2526,7 @@ class TrainEngine(_ParamStore):
             bad = [key for key, (first, k, _) in zip(tab.keys, tab.slices) if not bool(torch.isfinite(tab.shadow[first:first + k]).all())]
             raise RuntimeError("precise_bn: non-finite running statistics on entry (%s); nothing was changed" % ", ".join(bad[:4]))
         nbt = self._nbt_flat.clone()
-        state = [(b, b.momentum) for b in bns], self.blending, self.dropout
+        state = [(b, b.momentum) for b in bns], self.blending, self.dropout, self.erasing
         tab.acc.zero_()
         used, done, swapped = 0, False, False
         if self._guard is not None:
@@ -2497,7 +2538,7 @@ class TrainEngine(_ParamStore):
                 swapped = True
             for b in bns:
                 b.momentum = 1.0
-            self.blending, self.dropout = None, 0.0
+            self.blending, self.dropout, self.erasing = None, 0.0, None
             for imgs, labels in itertools.islice(batches, num_iters):
                 self.forward(imgs, labels)
                 with on():
@@ -2516,7 +2557,7 @@ class TrainEngine(_ParamStore):
         finally:
             for b, m in state[0]:
                 b.momentum = m
-            self.blending, self.dropout = state[1], state[2]
+            self.blending, self.dropout, self.erasing = state[1], state[2], state[3]
             side = getattr(self, "_side", None)
             if side is not None:
                 torch.cuda.current_stream().wait_stream(side)      # the forwards' data-gradient weight packs read the parameters there
