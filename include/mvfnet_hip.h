@@ -550,6 +550,53 @@ int mvf_head_train_fwd_soft(const void* feat, int clips, int t, int hw, int c, c
  * 16-byte units, a plane beyond int -- all before any launch. */
 int mvf_stem_erase(void* xp, int planes, int hp, int wp, int pad, const int* boxes, int max_boxes, const float* fill, const unsigned int* key, int dtype,
                    void* stream);
+/* RandAugment (timm's `rand-m7-n4-mstd0.5-inc1` of the fine-tuning recipes) on the uploaded uint8 frames, IN FRONT of the frame kernels: RandAugment is
+ * defined on 8-bit images (bit masks, histograms, truncating blends), so it runs on the bytes and not on the normalised stem operand.
+ *   frames_hwc (n, hs, ws, 3) uint8, the dense packed batch of mvf_frames_prep_u8; n % t == 0, frames [c t, (c + 1) t) are clip c and share its ops.
+ *   order      the stored channel order, 0 = BGR, 1 = RGB (as mvf_frames_yuv420_gather_resample_u8): only the grey weights depend on it.
+ *   sizes      DEVICE int32 (n, 2) rows (hs_i, ws_i), or NULL = (hs, ws).  Every op works on the frame's own hs_i x ws_i image (its centre, its width, its
+ *              histogram); bytes of the hs x ws extent outside that image are copied unchanged.  The kernel clamps hs_i / ws_i to [0, hs] / [0, ws].
+ *   table      DEVICE int32 (n / t, layers, 16), 1 <= layers <= 8.  Word 0 = kind; words 1..12 = the op's arguments; word 13 = the fill colour of kind 11,
+ *              three bytes in STORED order (byte c = bits 8 c .. 8 c + 7); words 14..15 = 0.  Contents are not checked here (mvfnet_amd.randaug.check_randaug_table).
+ *   out, tmp   two buffers of n * hs * ws * 3 bytes; the layers ping-pong between them and the result is ALWAYS in out; frames_hwc is never written.
+ *   stats_layers  bit k set = layer k gets its statistics pass (some clip's kind there is 5, 6 or 8).  With the bit clear such an op still touches only the
+ *              workspace and its frame; its pixels are then unspecified.
+ *   workspace  at least n * MVF_RANDAUG_WS_PER_FRAME bytes, MVF_RANDAUG_WS_PER_FRAME = 3 * 256 + 16: per frame the three 256-byte lookup tables of kinds 5 / 6
+ *              and one int32 (the grey mean of kind 8) in the 16 bytes behind them.
+ * At most two launches per layer: the statistics pass (only where the bit is set; one workgroup per frame, LDS histograms and integer sums only, so the
+ * result does not depend on the order of the adds; a frame whose op needs no statistics loads nothing) and the apply pass (a workgroup works on ONE frame, the
+ * op is a uniform branch; a thread owns an aligned dword of the batch, so loads of the pointwise ops and all stores are dword wide although neither
+ * ws_i * 3 nor a frame's base is a multiple of 4; only a dword shared with the neighbouring frame is stored by bytes).  No float atomics; bit-identical
+ * from run to run.
+ * Kinds and their arithmetic (p = a byte of the image, per channel unless stated; this is the specification, and what was compared with Pillow):
+ *    0 identity      p
+ *    1 invert        255 - p
+ *    2 posterize     p & w1                           (the host gives w1 = ~(2^(8 - bits) - 1) & 255; bits = 0 -> 0, a black frame)
+ *    3 solarize      p < w1 ? p : 255 - p             (w1 = thresh in 0 .. 256)
+ *    4 solarize-add  p < w1 ? min(255, p + w2) : p
+ *    5 autocontrast  per channel lo / hi = min / max of the frame; hi <= lo: identity; else in fp64 without FMA scale = 255.0 / (hi - lo), off = -lo * scale,
+ *                    lut[i] = clamp((int)(i * scale + off), 0, 255)
+ *    6 equalize      per channel, h = the histogram: at most one non-empty bin: identity; step = (sum(h) - last non-empty bin) / 255 (integer); step == 0:
+ *                    identity; else acc = step / 2 and for i = 0 .. 255: lut[i] = min(255, acc / step), acc += h[i]
+ *    7 brightness    blend(0, f, p)                   (f = the fp32 whose bits are w1, kinds 7 .. 10)
+ *    8 contrast      blend(m, f, p), m = (2 S + N) / (2 N) in integers, S = the sum of the frame's grey image, N = hs_i * ws_i
+ *    9 color         blend(grey, f, p), grey = (R * 19595 + G * 38470 + B * 7471 + 0x8000) >> 16 of the pixel
+ *   10 sharpness     blend(s, f, p); interior pixels: s = (2 acc + 13) / 26 in integers, acc = the 3 x 3 sum with centre weight 5; the one-pixel border has
+ *                    s = p; frames with hs_i < 3 or ws_i < 3 are copied whole
+ *   11 affine        the inverse map with six fp64 coefficients a .. f (words 1..12, low word first), see below
+ * blend(d, f, p), fp32 with every operation rounded on its own: v = d + f * (p - d); 0 <= f <= 1: (uint8)v, truncated; else v clamped to [0, 255], then truncated.
+ * Affine, output pixel (x, y), fp64 without FMA contraction: xin = (a * (x + .5) + b * (y + .5)) + c, yin likewise with d, e, f.  Unless 0 <= xin < ws_i and
+ * 0 <= yin < hs_i the pixel takes the fill colour.  Otherwise .5 is subtracted from both, x0 = floor(xin), dx = xin - x0, the taps are x0 and x0 + 1 clamped to
+ * the frame, the rows y0 (clamped) and y0 + 1 -- the first row again when y0 + 1 is outside the frame --, each lerp is p + (q - p) * d, and the result is
+ * truncated to uint8.  Pillow steps the source coordinate incrementally along a row; this direct evaluation equals it bit for bit on the fixtures of
+ * tests/golden/randaug_cases.npz -- measured there, not guaranteed for every matrix.
+ * Not built: bicubic interpolation, YUV / addressed input, AutoAugment / AugMix policies.
+ * MVF_EINVAL (before any launch, nothing enqueued): a NULL pointer (sizes may be NULL), n / hs / ws / t < 1, n % t != 0, order not 0 / 1, layers outside [1, 8],
+ * bits of stats_layers at or above `layers`, out == tmp or either == frames_hwc, a buffer or table that is not 4-byte aligned, a workspace smaller than the
+ * formula above; MVF_ESHAPE: a frame of 2^31 bytes or more, a batch of more than 2^31 workgroups. */
+#define MVF_RANDAUG_WS_PER_FRAME (3 * 256 + 16)
+int mvf_frames_randaug_u8(const unsigned char* frames_hwc, int n, int hs, int ws, int t, int order, const int* sizes, const int* table, int layers,
+                          unsigned stats_layers, unsigned char* out, unsigned char* tmp, void* workspace, long long workspace_bytes, void* stream);
 /* conv weight gradient dw_oihw (cout, cin_real, kh, kw_real) fp32; d describes the FORWARD conv (x dims, ho/wo = dz dims).
  * kw_packed*cin_packed == d->kw*d->cin; they differ from (kw_real, cin_real) only for the stem view (8x4 vs 7x3).
  * fp32 accumulation over the pixels in a fixed order (per-split partial tiles, then a split-lane reduce): deterministic, no atomics.  fp32

@@ -243,6 +243,8 @@ def _load():
     lib.mvf_stem_blend.argtypes = [vp, i32, i32, i32, i32, i32, vp, fp, vp, i32, vp]
     lib.mvf_stem_erase.restype = i32
     lib.mvf_stem_erase.argtypes = [vp, i32, i32, i32, i32, vp, i32, fp, vp, i32, vp]
+    lib.mvf_frames_randaug_u8.restype = i32
+    lib.mvf_frames_randaug_u8.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, i32, C.c_uint, vp, vp, vp, C.c_longlong, vp]
     lib.mvf_soft_targets.restype = i32
     lib.mvf_soft_targets.argtypes = [ll, vp, fp, i32, i32, f32, fp, vp]
     lib.mvf_ce_loss_soft.restype = i32

@@ -64,6 +64,10 @@ class Recognizer2D(nn.Module):
         from ..erasing import build_erasing
         erase_cfg = train_cfg.get("erasing") if hasattr(train_cfg, "get") else getattr(train_cfg, "erasing", None)
         self.erasing = build_erasing(erase_cfg)
+        # train_cfg=dict(randaug=dict(type='RandAugment', config='rand-m7-n4-mstd0.5-inc1')): RandAugment on the uploaded uint8 frames, likewise
+        from ..randaug import build_randaug
+        randaug_cfg = train_cfg.get("randaug") if hasattr(train_cfg, "get") else getattr(train_cfg, "randaug", None)
+        self.randaug = build_randaug(randaug_cfg)
         self.module_cfg = dict(module_cfg) if module_cfg else module_cfg
         self.in_channels = 3
         if self.module_cfg:
@@ -142,11 +146,12 @@ class Recognizer2D(nn.Module):
         return self
 
     def _set_soft_options(self, eng, training):
-        """The ONE place train_cfg['blending'], train_cfg['erasing'] and the head's label_smooth_eps reach the engine: only while the model trains.  Called
-        when the engine is created, whenever the mode changes (train() / eval()) and by forward_train.  engine.blending / engine.erasing /
+        """The ONE place train_cfg['blending'], train_cfg['erasing'], train_cfg['randaug'] and the head's label_smooth_eps reach the engine: only while the model trains.  Called
+        when the engine is created, whenever the mode changes (train() / eval()) and by forward_train.  engine.blending / engine.erasing / engine.randaug /
         engine.label_smooth_eps are plain attributes: whoever drives engine.train_step directly may also set them by hand, until the next of these calls."""
         eng.blending = self.blending if training else None
         eng.erasing = self.erasing if training else None
+        eng.randaug = self.randaug if training else None
         eng.label_smooth_eps = float(getattr(self.cls_head, "label_smooth_eps", 0.0)) if training else 0.0
 
     def forward_train(self, imgs, labels, **kwargs):

@@ -1809,6 +1809,11 @@ class TrainEngine(_ParamStore):
         # the blend.  Part of the plan key; with None the step issues exactly the launches it issued without it.
         self.erasing = None
         self._erase_table = None
+        # RandAugment (randaug.py: an object with draw(batch, t, sizes, order) -> (table, mask); None = off): a per-clip transform of the uploaded uint8
+        # frames, in front of input_pipeline.to_stem -- so before resize / crop / flip / ColorJitter / Normalize, and before erasing and blending.  The uint8
+        # path never runs from a launch plan: no plan key.  With None the step allocates and launches exactly what it did without it.
+        self.randaug = None
+        self._randaug_table = None
 
     def _pack_all(self, kind):
         """All forward (kind 0) or data-gradient (kind 1) weight packs in ONE launch (mvf_pack_conv_weights_batched); the job
@@ -1843,6 +1848,8 @@ class TrainEngine(_ParamStore):
         [B] int64 (GPU), or soft labels [B, num_classes] floating point -> loss tensor (1,), keeps activations."""
         if not imgs.is_cuda or imgs.dtype not in (torch.float32, torch.uint8):
             raise RuntimeError("TrainEngine.forward: float32 (or uint8 frames) GPU input required")
+        if self.randaug is not None:
+            self._randaug_refusals(imgs)
         if self._ema_swapped:
             self._ema_live("a training forward")
         self._main = torch.cuda.current_stream()
@@ -1882,6 +1889,9 @@ class TrainEngine(_ParamStore):
             if getattr(self.erasing, "max_boxes", None) not in (None, boxes.shape[1]):     # (the plan key carries the width the object names)
                 raise ValueError("TrainEngine: the erasing table holds %d boxes per frame, its object names max_boxes=%r" % (boxes.shape[1], self.erasing.max_boxes))
             self._erase_table = self._upload_erase_table(boxes, fill, key)
+        self._randaug_table = None
+        if self.randaug is not None:
+            self._randaug_table = self._draw_randaug(imgs)
         mask = None
         if self.dropout > 0.0:
             nt, cc = imgs.shape[0] * imgs.shape[1], self.fc_w.shape[1]
@@ -1948,6 +1958,56 @@ class TrainEngine(_ParamStore):
                                                                     np.ascontiguousarray(fill, dtype=np.float32)])
         return boxes_d, fill_d, key_d, int(boxes.shape[1])
 
+    def _randaug_refusals(self, imgs):
+        """RandAugment works on packed uint8 frames: anything else is refused before the step's first launch."""
+        from .preprocess import AddressedFramePipeline, Yuv420FramePipeline
+        if imgs.dtype != torch.uint8:
+            raise ValueError("TrainEngine: randaug augments uint8 frames (engine.input_pipeline = preprocess.FramePipeline(...)); float images are "
+                             "normalised already -- augment them before Normalize, or set engine.randaug = None")
+        pipe = self.input_pipeline
+        if isinstance(pipe, (Yuv420FramePipeline, AddressedFramePipeline)):
+            raise ValueError("TrainEngine: randaug takes packed (B, T, Hs, Ws, 3) frames; %s input (decoder-native planes) is out of scope" % type(pipe).__name__)
+        if pipe is not None and (imgs.dim() != 5 or imgs.shape[-1] != 3):
+            raise ValueError("TrainEngine: randaug takes (B, T, Hs, Ws, 3) uint8 frames, got %s" % (tuple(imgs.shape),))
+
+    def _draw_randaug(self, imgs):
+        """The step's RandAugment table, drawn and validated on the host and uploaded as the other step tables are; the frame sizes are columns 0..1 of the
+        window table for the resampling pipelines, the tensor's own (hs, ws) otherwise.  -> (table, sizes | None, layers, statistics mask, order)."""
+        import numpy as np
+        from .preprocess import ResamplingFramePipeline, JITTER_COLS, RESAMPLE_COLS
+        from .randaug import check_randaug_table, stats_mask
+        self._randaug_refusals(imgs)
+        self._input_hw(imgs)                                 # (uint8 frames without a pipeline: its RuntimeError)
+        pipe = self.input_pipeline
+        b, t, hs, ws = (int(v) for v in imgs.shape[:4])
+        order = 0 if pipe.to_rgb else 1                      # to_rgb swaps on the way to the stem: the stored order is BGR
+        sizes_d, sizes_h = None, (hs, ws)
+        if isinstance(pipe, ResamplingFramePipeline):
+            rows = pipe._as_table(self.input_window)
+            if rows.shape[1] not in (RESAMPLE_COLS, JITTER_COLS) or rows.shape[0] != b * t:
+                raise ValueError("TrainEngine: randaug needs one 11- / 23-column row per frame (%d frames), got a table %s" % (b * t, tuple(rows.shape)))
+            sizes_d = rows[:, :2].contiguous()
+            sizes_h = sizes_d.cpu().numpy()               # (a readback per step: Rotate / Translate are drawn for the frame's own size)
+            if (sizes_h < 1).any() or (sizes_h[:, 0] > hs).any() or (sizes_h[:, 1] > ws).any():
+                raise ValueError("TrainEngine: a frame size of the window table lies outside the %dx%d frames" % (hs, ws))
+        table, _ = self.randaug.draw(b, t, sizes_h, order)
+        check_randaug_table(table, b)
+        table = np.ascontiguousarray(table, dtype=np.int32)
+        (table_d,) = self._upload_table("randaug_table", [table])
+        return table_d, sizes_d, int(table.shape[1]), stats_mask(table), order
+
+    def _randaug_frames(self, imgs):
+        """The augmented frames, in a persistent buffer shaped like `imgs` (which is not written)."""
+        from .randaug import WS_PER_FRAME
+        table_d, sizes_d, layers, mask, order = self._randaug_table
+        f = imgs.reshape((-1,) + tuple(imgs.shape[-3:])).contiguous()
+        n, hs, ws = (int(v) for v in f.shape[:3])
+        out, tmp = self.buf("randaug_out", tuple(f.shape), torch.uint8), self.buf("randaug_tmp", tuple(f.shape), torch.uint8)
+        wsb = self.buf("randaug_ws", (n * WS_PER_FRAME,), torch.uint8)
+        check(lib.mvf_frames_randaug_u8(_p(f), n, hs, ws, int(imgs.shape[1]), order, _p(sizes_d), _p(table_d), layers, mask, _p(out), _p(tmp), _p(wsb),
+                                        wsb.numel(), _st()), "frames_randaug")
+        return out.view(imgs.shape)
+
     def _soft_labels(self, imgs, labels):
         """The caller hands the (B, num_classes) soft-label matrix itself (floating point) instead of integer labels."""
         return labels.is_floating_point() and labels.dim() == 2 and tuple(labels.shape) == (imgs.shape[0], self.num_classes)
@@ -1988,6 +2048,8 @@ class TrainEngine(_ParamStore):
         hp, wp = h + 6, (w + 6 + 2 + 1) // 2 * 2
         xp = self.buf("xp", (nt, hp, wp, 4))
         if u8:
+            if self.randaug is not None:
+                imgs = self._randaug_frames(imgs)          # RandAugment, then erasing, then blending
             self.input_pipeline.to_stem(imgs, self.input_window, 3, wp, self.tdtype, out=xp)
         else:
             check(lib.mvf_stem_prep(_p(x), nt, 3, h, w, 3, wp, _p(xp), self.dt, _st()), "stem_prep")
@@ -2232,6 +2294,8 @@ class TrainEngine(_ParamStore):
         """forward + backward of one step, replayed from a launch plan where one exists.  exchange=True is train_step.  exchange=False is a micro-step of
         accumulate_step: without a process group the flag changes no launch, so it shares train_step's plans (same key, same recordings); WITH one, a plan
         recorded by train_step carries the tail bucket's collective, which a micro-step must not issue -- those micro-steps run eagerly, never from a plan."""
+        if self.randaug is not None:
+            self._randaug_refusals(imgs)
         if self._ema_swapped:
             self._ema_live("a training step")
         if self._guard is not None:
@@ -2526,7 +2590,7 @@ class TrainEngine(_ParamStore):
             bad = [key for key, (first, k, _) in zip(tab.keys, tab.slices) if not bool(torch.isfinite(tab.shadow[first:first + k]).all())]
             raise RuntimeError("precise_bn: non-finite running statistics on entry (%s); nothing was changed" % ", ".join(bad[:4]))
         nbt = self._nbt_flat.clone()
-        state = [(b, b.momentum) for b in bns], self.blending, self.dropout, self.erasing
+        state = [(b, b.momentum) for b in bns], self.blending, self.dropout, self.erasing, self.randaug
         tab.acc.zero_()
         used, done, swapped = 0, False, False
         if self._guard is not None:
@@ -2538,7 +2602,7 @@ class TrainEngine(_ParamStore):
                 swapped = True
             for b in bns:
                 b.momentum = 1.0
-            self.blending, self.dropout, self.erasing = None, 0.0, None
+            self.blending, self.dropout, self.erasing, self.randaug = None, 0.0, None, None
             for imgs, labels in itertools.islice(batches, num_iters):
                 self.forward(imgs, labels)
                 with on():
@@ -2557,7 +2621,7 @@ class TrainEngine(_ParamStore):
         finally:
             for b, m in state[0]:
                 b.momentum = m
-            self.blending, self.dropout, self.erasing = state[1], state[2], state[3]
+            self.blending, self.dropout, self.erasing, self.randaug = state[1], state[2], state[3], state[4]
             side = getattr(self, "_side", None)
             if side is not None:
                 torch.cuda.current_stream().wait_stream(side)      # the forwards' data-gradient weight packs read the parameters there
