@@ -852,6 +852,43 @@ enum { MVF_METRICS_ROWS = 0, MVF_METRICS_BAD_LABEL = 1, MVF_METRICS_NAN_ROWS = 2
 size_t mvf_metrics_state_words(int classes, int with_confusion);
 int mvf_metrics_update(const float* scores, int rows, int classes, const long long* labels, const int* ks, int nk, long long* state, int with_confusion,
                        int* rank_out, int* pred_out, void* stream);
+/* Per-parameter training statistics and the diagnosis of a skipped step (csrc/layer_stats.hip): where a NaN came from and whether every layer is learning,
+ * from figures that stay on the device until the host asks.
+ *
+ * mvf_flat_segment_stats: per SEGMENT of a flat fp32 array x of n elements -- or of the element-wise difference x - y when y is given -- four figures.
+ * Segment k covers [first[k], first[k + 1]), the last one runs up to n; `first` is a DEVICE array of nseg int64 with first[0] == 0, strictly ascending and
+ * below n, validated ONCE by the caller when it builds it (as the table of mvf_bn_stats_snapshot): it is not read back per call.  With
+ * d_i = (double)x[i], or (double)x[i] - (double)y[i]:
+ *   sumsq   the sum of d_i * d_i over the finite d_i            absmax  the largest |d_i| over the finite d_i (0 if there are none)
+ *   n_nan   the number of d_i that are NaN                      n_inf   the number that are +inf or -inf   (inf - inf is a NaN: d_i is classified, not x and y)
+ * Arithmetic: fp64 throughout.  The square of an fp32 value is exact in fp64, and so is the difference of two fp32 values unless their exponents lie more
+ * than 29 binades apart (then it is rounded once, and its square once more); what differs from a serial fp64 sum is the ORDER of at most n_k non-negative
+ * additions, so sumsq agrees with any fp64 restatement within a relative (n_k + 4) * 2^-52; absmax and the counts are exact.  1e20 does not overflow and
+ * 1e-30 does not vanish.  No floating-point atomics; two launches whose grids depend on n and nseg alone (fixed 4096-element chunks, one workgroup each,
+ * write one partial per (chunk c, segment s) intersection to workspace slot c + s; one wavefront per segment adds its slots in a fixed order): bit-identical
+ * from run to run.  x, y need 4-byte alignment only and segment boundaries may fall anywhere (16-byte loads are used where the addresses allow).
+ * guard_or_null: NULL = always; else the four ints of mvf_sgd_step_guarded: every workgroup of both launches reads guard[0], and when it is 0 NOT ONE byte of
+ * out, *step_out or the workspace is stored (the rule of mvf_bn_stats_restore); when it is non-zero the figures are written and, with step_out given,
+ * *step_out = guard[3] (the index of the step they belong to).  step_out without a guard is MVF_EINVAL.
+ * ws: mvf_flat_stats_workspace_bytes(n, nseg) bytes (0 for arguments the call would refuse), 8-byte aligned, owned by the caller; it needs no initialisation.
+ * Checked before any launch, nothing launched otherwise.  MVF_EINVAL: NULL x / first / out; n <= 0; nseg <= 0 or nseg > n; a misaligned operand (first, out,
+ * step_out and ws 8 bytes, x, y and guard 4 bytes); out or ws overlapping x / y or one another; guard overlapping out / step_out / ws.  MVF_EWS: a NULL or
+ * short workspace.
+ *
+ * mvf_bn_stats_nonfinite: counts[k] = the number of non-finite 32-bit words (exponent all ones) in segment k of a running-statistics table, the table
+ * mvf_bn_stats_snapshot takes.  ONE launch, one wavefront per segment with a strided loop, integer sums.  guard_or_null as above: guard[0] == 0 stores
+ * nothing.  Like snapshot / restore it does not read the table back: checked are the by-value arguments (nseg > 0, n > 0, nseg <= n), non-NULL seg / counts
+ * and alignment (seg and counts 8 bytes, guard 4), and that counts, the table and guard do not overlap -- MVF_EINVAL otherwise, nothing launched. */
+typedef struct mvf_flat_stats {
+    double sumsq;
+    double absmax;
+    long long n_nan;
+    long long n_inf;
+} mvf_flat_stats_t;
+size_t mvf_flat_stats_workspace_bytes(long n, int nseg);
+int mvf_flat_segment_stats(const float* x, const float* y_or_null, long n, const long long* first, int nseg, mvf_flat_stats_t* out, const int* guard_or_null,
+                           long long* step_out_or_null, void* ws, size_t ws_bytes, void* stream);
+int mvf_bn_stats_nonfinite(const mvf_stat_segment_t* seg, int nseg, long n, long long* counts, const int* guard_or_null, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * [r6] Launch-table replay.  One training step (the reference's batch_processor + DistOptimizerHook.after_train_iter, codes/core/train.py:45-60,

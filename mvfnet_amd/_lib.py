@@ -305,6 +305,12 @@ def _load():
     lib.mvf_metrics_state_words.argtypes = [i32, i32]
     lib.mvf_metrics_update.restype = i32
     lib.mvf_metrics_update.argtypes = [fp, i32, i32, ll, vp, i32, ll, i32, vp, vp, vp]
+    lib.mvf_flat_stats_workspace_bytes.restype = sz
+    lib.mvf_flat_stats_workspace_bytes.argtypes = [i64, i32]
+    lib.mvf_flat_segment_stats.restype = i32
+    lib.mvf_flat_segment_stats.argtypes = [fp, fp, i64, vp, i32, vp, vp, vp, vp, sz, vp]
+    lib.mvf_bn_stats_nonfinite.restype = i32
+    lib.mvf_bn_stats_nonfinite.argtypes = [vp, i32, i64, vp, vp, vp]
     lib.mvf_plan_run.restype = i32
     lib.mvf_plan_run.argtypes = [C.POINTER(PlanOp), i32, C.POINTER(C.c_ulonglong), C.POINTER(C.c_float), C.POINTER(C.c_int)]
     # Callers pass device pointers as plain Python ints (train_engine._p): without declared argtypes ctypes would truncate them to c_int silently.  Every

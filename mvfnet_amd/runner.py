@@ -26,6 +26,7 @@ import torch.distributed as dist
 from .checkpoint import load_checkpoint, save_checkpoint
 from .dist import get_dist_info, init_dist  # noqa: F401  (re-exported: train_recognizer.py imports init_dist from the core package)
 from .ema import check_ema, check_precise_bn
+from .diagnostics import check_layer_stats, skip_note, summary as _layer_summary
 from .guard import check_nonfinite_guard
 from .metrics import check_train_accuracy
 
@@ -407,8 +408,15 @@ class Runner(object):
 
     def __init__(self, model, work_dir=None, lr=0.015, momentum=0.9, weight_decay=1e-4, max_norm=40.0, lr_steps=(90, 130),
                  warmup_iters=25070, warmup_ratio=0.01, ckpt_interval=10, log_interval=20, logger=print, optimizer=None, dtype=None,
-                 warmup="linear", lr_gamma=0.1, accumulate=1, ema=None, precise_bn=None, nonfinite_guard=None, lr_policy=None, train_accuracy=None):
-        """train_accuracy = dict(k=(1, 5)) (an empty dict gives the default): the engine counts the top-k hits of every step's score matrix on the device
+                 warmup="linear", lr_gamma=0.1, accumulate=1, ema=None, precise_bn=None, nonfinite_guard=None, lr_policy=None, train_accuracy=None,
+                 layer_stats=None):
+        """layer_stats = dict(interval=None, on_skip=True, top=1) (an empty dict gives the defaults; diagnostics.check_layer_stats): per-parameter statistics taken on
+        the device (TrainEngine.enable_layer_stats).  Every `interval` optimizer steps (None: the log interval) the step in front of the log point is measured;
+        at the log point, where the loop synchronises anyway, the logging rank reads the table, appends dict(epoch, iter, step, grad_scale, params) to
+        `layer_stats_history` and adds to the END of the log line the `top` smallest and largest update_ratio among trained parameters and the `top` largest
+        grad_norm, each with its name.  on_skip=True (needs nonfinite_guard) records every skipped step on the device: ` skipped N` is followed by
+        ` (last: iter I, <kind> at <where>)` and the FloatingPointError text ends with the same diagnosis (TrainEngine.last_skip).
+        train_accuracy = dict(k=(1, 5)) (an empty dict gives the default): the engine counts the top-k hits of every step's score matrix on the device
         (TrainEngine.enable_train_accuracy: one small launch per forward, outside the launch plans) and the log line gains ` top1 %.4f top5 %.4f` -- the
         accuracy over the steps since the previous log line -- after grad_norm, read where the loop synchronises anyway.  Steps under blending or with soft
         labels are not counted; a window without counted rows logs nan.  Under a process group each rank counts its own share and rank 0 logs its own.
@@ -435,6 +443,8 @@ class Runner(object):
         self.precise_bn = check_precise_bn(precise_bn)
         self.nonfinite_guard = check_nonfinite_guard(nonfinite_guard)
         self.train_accuracy = check_train_accuracy(train_accuracy)
+        self.layer_stats = check_layer_stats(layer_stats, guard_on=self.nonfinite_guard is not None)
+        self.layer_stats_history = []
         if self.precise_bn is not None and self.precise_bn["weights"] != "live" and self.ema is None:
             raise ValueError("precise_bn: weights=%r needs averaged weights; set ema (ema_config) as well" % self.precise_bn["weights"])
         self.train_loader = None
@@ -461,6 +471,8 @@ class Runner(object):
             self.engine.enable_step_guard()
         if self.train_accuracy is not None:
             self.engine.enable_train_accuracy(**self.train_accuracy)
+        if self.layer_stats is not None:
+            self.engine.enable_layer_stats(on_skip=self.layer_stats["on_skip"])
         if self.precise_bn is not None:
             from .evaluation import PreciseBNHook
             self.register_hook(PreciseBNHook(None, **self.precise_bn))
@@ -488,12 +500,39 @@ class Runner(object):
         if self.nonfinite_guard is None:
             return ""
         st = self.engine.guard_state()
+        last = ""
+        if self.layer_stats is not None and self.layer_stats["on_skip"]:
+            rec = self.engine.last_skip()            # (the record's step is the guard's count; the runner's iter runs ahead of it by a constant)
+            last = skip_note(rec, None if rec is None else self.iter - (st["steps"] - rec["step"]))
         if st["consecutive"] >= self.nonfinite_guard["max_consecutive"]:
             raise FloatingPointError(
                 "non-finite gradient norm in %d consecutive optimizer steps (max_consecutive=%d), seen between iter %d and iter %d of epoch %d; every one was "
-                "skipped on the device: parameters, optimizer state, averaged weights and BatchNorm statistics are those of the last good step"
-                % (st["consecutive"], self.nonfinite_guard["max_consecutive"], self.iter - st["consecutive"] + 1, self.iter, self.epoch + 1))
-        return " skipped %d" % st["skipped"]
+                "skipped on the device: parameters, optimizer state, averaged weights and BatchNorm statistics are those of the last good step%s"
+                % (st["consecutive"], self.nonfinite_guard["max_consecutive"], self.iter - st["consecutive"] + 1, self.iter, self.epoch + 1, last))
+        return " skipped %d%s" % (st["skipped"], last)
+
+    def _layer_interval(self):
+        if self.layer_stats is None:
+            return 0
+        return self.layer_stats["interval"] or self.log_interval or 0
+
+    def _arm_layer_stats(self):
+        """In front of an optimizer step: measure it when the step lands on a statistics point."""
+        iv = self._layer_interval()
+        if iv and (self.iter + 1) % iv == 0:
+            self.engine.measure_layer_stats()
+
+    def _layer_note(self, rank):
+        """Behind an optimizer step (iter counted): at a statistics point the logging rank reads the measured step's table (a synchronising read), files the
+        full rows in layer_stats_history and returns the log line's suffix; '' elsewhere and with the option off."""
+        iv = self._layer_interval()
+        if not iv or self.iter % iv != 0 or rank != 0:
+            return ""
+        fig = self.engine.layer_stats()
+        if fig is None:
+            return ""
+        self.layer_stats_history.append(dict(epoch=self.epoch + 1, iter=self.iter, **fig))
+        return _layer_summary(fig["params"], self.layer_stats["top"])
 
     def _accuracy_note(self):
         """' top1 %.4f top5 %.4f' for the log line: the engine's window since the previous line (a synchronising 128-byte read, made on the logging rank only,
@@ -505,13 +544,15 @@ class Runner(object):
 
     def _apply_accumulated(self, rank):
         lr = self.current_lr()
+        self._arm_layer_stats()
         self.engine.apply_accumulated(lr=lr)
         self.iter += 1
+        layers = self._layer_note(rank)
         if self.log_interval and self.iter % self.log_interval == 0:
             note = self._check_guard()               # on every rank: all of them take the same decisions, so all of them stop together
             if rank == 0:
-                self.log("Epoch [%d] iter %d lr %.5f loss_cls %.4f grad_norm %.3f%s%s" % (
-                    self.epoch + 1, self.iter, lr, float(self.engine.accumulated_loss), float(self.engine.norm_out[0]), self._accuracy_note(), note))
+                self.log("Epoch [%d] iter %d lr %.5f loss_cls %.4f grad_norm %.3f%s%s%s" % (
+                    self.epoch + 1, self.iter, lr, float(self.engine.accumulated_loss), float(self.engine.norm_out[0]), self._accuracy_note(), note, layers))
 
     def _train_epoch_accumulated(self, loader, rank):
         """One micro-step per loader batch; the optimizer runs after every k-th batch and after the epoch's last one (a shorter trailing group is applied
@@ -535,13 +576,15 @@ class Runner(object):
             loader = ()
         for data in loader:
             lr = self.current_lr()
+            self._arm_layer_stats()
             loss = self.engine.train_step(data["img_group"], data["label"], lr=lr)
             self.iter += 1
+            layers = self._layer_note(rank)
             if self.log_interval and self.iter % self.log_interval == 0:
                 note = self._check_guard()           # on every rank: all of them take the same decisions, so all of them stop together
                 if rank == 0:
-                    self.log("Epoch [%d] iter %d lr %.5f loss_cls %.4f grad_norm %.3f%s%s" % (
-                        self.epoch + 1, self.iter, lr, float(loss), float(self.engine.norm_out[0]), self._accuracy_note(), note))
+                    self.log("Epoch [%d] iter %d lr %.5f loss_cls %.4f grad_norm %.3f%s%s%s" % (
+                        self.epoch + 1, self.iter, lr, float(loss), float(self.engine.norm_out[0]), self._accuracy_note(), note, layers))
         self._check_guard()                          # always at epoch end, before a checkpoint is written
         self.epoch += 1
         if rank == 0 and self.work_dir and self.ckpt_interval and self.epoch % self.ckpt_interval == 0:
@@ -629,6 +672,8 @@ def train_network(model, dataset, cfg, distributed=False, validate=False, logger
     cfg.precise_bn = dict(num_iters=..., interval=..., weights=...) recomputes the BatchNorm running statistics at epoch end (Runner(precise_bn=...)).
     cfg.nonfinite_guard = dict(max_consecutive=100) skips optimizer steps with a non-finite gradient norm on the device (Runner(nonfinite_guard=...)).
     cfg.train_accuracy = dict(k=(1, 5)) adds the training top-k accuracy, counted on the device, to the log line (Runner(train_accuracy=...)).
+    cfg.layer_stats = dict(interval=None, on_skip=True, top=1) adds per-parameter gradient / weight / update figures at the log points and the diagnosis of
+    every skipped step (Runner(layer_stats=...)).
     cfg.evaluation = dict(on_device=True) makes the validation hook of `validate` count its hits on the device (runner.device_test) instead of gathering rows.
     cfg.optimizer_config.accumulate = k (an integer >= 1, default 1) makes one optimizer step of k loader batches
     (gradient accumulation, Runner(accumulate=k)).  `dataset`: a torch Dataset of dict(img_group, label) items, a ready loader, or an
@@ -640,6 +685,7 @@ def train_network(model, dataset, cfg, distributed=False, validate=False, logger
     precise_bn = check_precise_bn(cfg.get("precise_bn"))
     nonfinite_guard = check_nonfinite_guard(cfg.get("nonfinite_guard"))
     train_accuracy = check_train_accuracy(cfg.get("train_accuracy"))
+    layer_stats = check_layer_stats(cfg.get("layer_stats"), guard_on=nonfinite_guard is not None)
     if precise_bn is not None and precise_bn["weights"] != "live" and ema is None:
         raise ValueError("precise_bn: weights=%r needs averaged weights; set ema_config as well" % precise_bn["weights"])
     lrc = cfg.get("lr_config") or {}
@@ -667,7 +713,7 @@ def train_network(model, dataset, cfg, distributed=False, validate=False, logger
                     warmup_iters=_cfg_get(lrc, "warmup_iters", 0), warmup_ratio=_cfg_get(lrc, "warmup_ratio", 0.1),
                     lr_gamma=_cfg_get(lrc, "gamma", 0.1), ckpt_interval=_cfg_get(ck, "interval", 0) or 0,
                     log_interval=_cfg_get(lg, "interval", 0) or 0, logger=log, optimizer=optimizer, accumulate=accumulate, ema=ema, precise_bn=precise_bn,
-                    nonfinite_guard=nonfinite_guard, lr_policy=lr_policy, train_accuracy=train_accuracy)
+                    nonfinite_guard=nonfinite_guard, lr_policy=lr_policy, train_accuracy=train_accuracy, layer_stats=layer_stats)
     if clip and _cfg_get(clip, "norm_type", 2) != 2:
         raise NotImplementedError("grad_clip norm_type %r: the fused clip is the L2 norm" % _cfg_get(clip, "norm_type"))
     if validate:

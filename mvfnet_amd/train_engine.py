@@ -1346,10 +1346,64 @@ class _ParamStore(object):
         return self._apply_optimizer(self.flat_grads, 1.0 / world, lr)
 
     def _apply_optimizer(self, grads, grad_scale, lr=None):
-        """What every optimizer path goes through (apply_sgd, step, train_step, apply_accumulated): the SGD sequence below, or mvf_adamw_step when selected."""
+        """What every optimizer path goes through (apply_sgd, step, train_step, apply_accumulated): the SGD sequence below, or mvf_adamw_step when selected.
+        The per-parameter statistics (TrainEngine.enable_layer_stats) hook in here, around the update and outside the launch plans."""
+        ls = self._lstats
+        if ls is not None:
+            ls["grads"], ls["scale"] = grads, float(grad_scale)      # (what _guard_restore's scan and the measured step read)
+            measured = self._layer_stats_before(grads)
         if self._adam is not None:
-            return self._apply_adamw(grads, grad_scale, lr)
-        return self._apply_sgd(grads, grad_scale, lr)
+            out = self._apply_adamw(grads, grad_scale, lr)
+        else:
+            out = self._apply_sgd(grads, grad_scale, lr)
+        if ls is not None:
+            ls["grads"] = None
+            if measured and out is not None:
+                self._layer_stats_after()
+        return out
+
+    _lstats = None     # per-parameter statistics (TrainEngine.enable_layer_stats): None = off, _apply_optimizer and _guard_restore launch what they always did
+
+    def _flat_stats(self, x, y, out, guard=None, step_out=None):
+        ls = self._lstats
+        check(lib.mvf_flat_segment_stats(_p(x), _p(y), x.numel(), _p(ls["first"]), ls["nseg"], _p(out), _p(guard), _p(step_out), _p(ls["ws"]), ls["ws"].numel(),
+                                         _st()), "flat segment stats")
+
+    def _layer_stats_before(self, grads):
+        """A measured step, in front of the update: the gradient's and the parameters' figures, and the copy the update is measured against."""
+        ls = self._lstats
+        if not ls["armed"] or not self.rehomed:
+            return False
+        ls["armed"] = False
+        if ls["out"] is None:                    # allocated on first use, beside the others: no recorded plan holds their addresses
+            ls["out"] = torch.zeros(3, ls["nseg"], 4, dtype=torch.int64, device=self.device)
+            ls["copy"] = torch.empty_like(self.flat_params)
+        ls["pending"] = None
+        self._flat_stats(grads, None, ls["out"][0])
+        self._flat_stats(self.flat_params, None, ls["out"][1])
+        ls["copy"].copy_(self.flat_params)
+        return True
+
+    def _layer_stats_after(self):
+        """... and behind it: the norm of the update actually applied, whichever optimizer ran (0 on a step the guard skipped)."""
+        ls = self._lstats
+        self._flat_stats(self.flat_params, ls["copy"], ls["out"][2])
+        ls["pending"] = (self.steps, ls["scale"])
+
+    def _layer_stats_on_skip(self, tab):
+        """Behind a guarded optimizer step, BEFORE the statistics go back: the gradient's figures with the step index, and the non-finite count of every
+        running statistic, both predicated on the guard's flag -- two launches that store nothing on a good step."""
+        ls = self._lstats
+        ls["seen"] += 1
+        self._flat_stats(ls["grads"], None, ls["skip_out"], guard=self._guard["buf"], step_out=ls["skip_step"])
+        if not ls["bn_from"] or ls["bn_from"][-1][1] is not tab:
+            ls["bn_from"].append((ls["seen"], tab))          # which table the record of step k belongs to: the last entry that starts at or before k
+        if tab is None:                                      # (every BatchNorm frozen: no statistic moves)
+            return
+        ent = ls["bn"].get(id(tab))
+        if ent is None:
+            ent = ls["bn"][id(tab)] = (tab, torch.zeros(tab.nseg, dtype=torch.int64, device=self.device))
+        check(lib.mvf_bn_stats_nonfinite(_p(tab.dev), tab.nseg, tab.n, _p(ent[1]), _p(self._guard["buf"]), _st()), "bn stats nonfinite")
 
     def _apply_sgd(self, grads, grad_scale, lr=None):
         """The optimizer's launch sequence on `grads` (a flat fp32 tensor laid out like flat_grads: flat_grads itself, or the accumulator of
@@ -1402,6 +1456,8 @@ class _ParamStore(object):
         """Behind a guarded optimizer step: the conditional restore of the BatchNorm statistics snapshot taken before the step's first forward."""
         g = self._guard
         snap, g["snap"] = g["snap"], None
+        if self._lstats is not None and self._lstats["on_skip"]:
+            self._layer_stats_on_skip(snap[0] if snap is not None else None)      # the NaN statistics are evidence: scanned before they are put back
         if snap is not None:
             tab, flat_stats = snap
             check(lib.mvf_bn_stats_restore(_p(tab.dev), tab.nseg, tab.n, _p(flat_stats), _p(self._nbt_flat), self._nbt_flat.numel(), _p(g["nbt"]), _p(g["buf"]),
@@ -2402,6 +2458,110 @@ class TrainEngine(_ParamStore):
         check(lib.mvf_bn_stats_snapshot(_p(tab.dev), tab.nseg, tab.n, _p(flat), _p(self._nbt_flat), self._nbt_flat.numel(), _p(g["nbt"]),
                                         C.c_void_p(torch.cuda.current_stream().cuda_stream)), "bn stats snapshot")
         g["snap"] = ent
+
+    # ---- per-parameter statistics and the diagnosis of a skipped step (csrc/layer_stats.hip, diagnostics.py) -------------------------------------------------
+    # Two questions a fine-tune asks: is every layer learning, and where did the NaN of a skipped step come from.  The evidence is on the device at the
+    # moment of the optimizer step -- the gradient in flat_grads / flat_acc, the NaN batch statistics in the BatchNorm buffers -- and gone one launch later,
+    # so it is reduced there: mvf_flat_segment_stats gives sum of squares, largest magnitude and NaN / inf counts per parameter (fp64, two launches over the
+    # whole flat range, bit-identical from run to run), mvf_bn_stats_nonfinite counts the non-finite running statistics.  All hooks sit in _apply_optimizer /
+    # _guard_restore, outside the launch plans: plans, plan keys and recorded signatures are what they were.
+    #   measure_layer_stats() arms the NEXT optimizer step: before the update the figures of the gradient (the buffer the optimizer reads: flat_grads, or the
+    #     accumulator -- under a process group after the all-reduce, so every rank holds the same figures) and of flat_params, and a copy of flat_params;
+    #     after it the figures of flat_params - copy: the update actually applied, whichever optimizer ran, 0 on a skipped step.
+    #   on_skip (needs the step guard): every guarded step is followed by the gradient's figures and the statistics' counts PREDICATED on the guard's flag
+    #     -- on a good step two launches (three kernels) that read 4 bytes per workgroup and store nothing; on a skipped one the record of that step, which
+    #     stays until the next skipped step overwrites it.
+    # layer_stats() and last_skip() are the calls that synchronise.  An engine that never calls enable_layer_stats allocates and launches exactly what it
+    # did without it.
+    def _param_table(self):
+        """The parameter layout of the flat buffers: names, flat offsets, `trained` flags (built on every call: requires_grad may change between steps)."""
+        names, first, trained = [], [], []
+        off = self.trainable_offset()
+        for name, p in self.model.named_parameters():
+            v = self._grad_view[id(p)]
+            names.append(name)
+            first.append(v.storage_offset())
+            trained.append(bool(p.requires_grad) and v.storage_offset() >= off)
+        return names, first, trained
+
+    def enable_layer_stats(self, on_skip=True):
+        """Build the parameter table (one segment per parameter of model.named_parameters() over the whole flat range; the padding zeros between parameters
+        join the preceding segment) and its workspace.  on_skip=True also records every step the non-finite guard skips (last_skip()); it needs
+        enable_step_guard() first.  Calling it again keeps the table and the record."""
+        if not self.rehomed:
+            raise RuntimeError("enable_layer_stats: this store does not own its parameters")
+        if on_skip and self._guard is None:
+            raise RuntimeError("enable_layer_stats(on_skip=True) records the steps the non-finite guard skips; call enable_step_guard() first "
+                               "(Runner(nonfinite_guard=...)), or pass on_skip=False")
+        ls = self._lstats
+        if ls is None:
+            names, first, _ = self._param_table()
+            n = self.flat_params.numel()
+            if len(names) != len(list(self.model.parameters())):
+                raise RuntimeError("enable_layer_stats: the model shares parameters between modules; the flat layout has one segment per name")
+            if not names or first[0] != 0 or any(a >= b for a, b in zip(first, first[1:])) or first[-1] >= n:      # the ONE validation of the table
+                raise RuntimeError("enable_layer_stats: the flat parameter layout is not ascending from 0")
+            ls = dict(names=names, nseg=len(names), first=torch.tensor(first, dtype=torch.int64).to(self.device), armed=False, out=None, copy=None, pending=None,
+                      grads=None, scale=1.0, on_skip=False,
+                      ws=torch.empty(lib.mvf_flat_stats_workspace_bytes(n, len(names)), dtype=torch.uint8, device=self.device))
+            self._lstats = ls
+        if on_skip and (not ls["on_skip"] or ls.get("guard_buf") is not self._guard["buf"]):
+            ls.update(skip_out=torch.zeros(ls["nseg"], 4, dtype=torch.int64, device=self.device), skip_step=torch.zeros(1, dtype=torch.int64, device=self.device),
+                      bn={}, bn_from=[], guard_buf=self._guard["buf"], seen=int(self._guard["buf"][3].item()))      # (the guard's step count so far: read once, here)
+        ls["on_skip"] = bool(on_skip)
+
+    def disable_layer_stats(self):
+        self._lstats = None
+
+    def _lstats_on(self, who):
+        if self._lstats is None:
+            raise RuntimeError("%s: the per-parameter statistics are off; call enable_layer_stats() (Runner(layer_stats=...), cfg.layer_stats) first" % who)
+        return self._lstats
+
+    def measure_layer_stats(self):
+        """Arm the NEXT optimizer step (step, train_step, apply_accumulated; SGD and Adam forms): four launches in front of the update, two behind it, one
+        copy of flat_params.  Nothing is read back; layer_stats() reads the result."""
+        self._lstats_on("measure_layer_stats")["armed"] = True
+
+    def layer_stats(self):
+        """dict(step, grad_scale, params): the figures of the last measured step, or None if none has completed.  step is the engine's count of optimizer
+        steps (`steps`) after it; params maps every name of model.named_parameters(), in that order, to dict(grad_norm, grad_absmax -- both scaled by the
+        step's grad_scale: what the clip sees --, weight_norm, update_norm, update_ratio = update_norm / weight_norm, grad_nan, grad_inf, weight_nonfinite,
+        update_nonfinite, trained).  trained is False for a frozen prefix and for requires_grad False.  A ~20 KB read that waits for the device: the one
+        synchronising call of the measured step."""
+        from . import diagnostics
+        ls = self._lstats_on("layer_stats")
+        if ls["pending"] is None:
+            return None
+        step, scale = ls["pending"]
+        rec = ls["out"].cpu().numpy()
+        _, _, trained = self._param_table()
+        return dict(step=step, grad_scale=scale, params=diagnostics.rows(ls["names"], trained, rec[0], rec[1], rec[2], scale))
+
+    def last_skip(self):
+        """None if no step has been skipped since on_skip was enabled; else dict(step, kind, where, detail) of the LAST skipped step (diagnostics.diagnose):
+        step is the guard's count of optimizer steps (guard_state()['steps']) at that step, kind one of 'forward' / 'backward' / 'loss' / 'norm_overflow',
+        where a BatchNorm module's or a parameter's name.  The record survives later good steps.  The BatchNorm table is _all_bns() without the frozen ones:
+        stem first, then per block the MVF module's BatchNorm, bn1, the downsample branch's, bn2, bn3 -- the forward's DATAFLOW order (every BatchNorm's input
+        depends only on BatchNorms in front of it; the downsample branch reads the block input), which is why the first non-finite entry is the culprit.
+        Frozen / norm_eval BatchNorms move no statistic and are not in the table: localisation is coarser there (diagnostics.diagnose).  Reads that wait for
+        the device."""
+        from . import diagnostics
+        ls = self._lstats_on("last_skip")
+        if not ls["on_skip"]:
+            raise RuntimeError("last_skip: enable_layer_stats(on_skip=True) first")
+        step = int(ls["skip_step"].item())
+        if step == 0:
+            return None
+        tab = None
+        for start, t in ls["bn_from"]:
+            if start <= step:
+                tab = t
+        bn_names, bn_counts = ([], [])
+        if tab is not None:
+            bn_names, bn_counts = tab.keys, ls["bn"][id(tab)][1].cpu().numpy()
+        _, _, trained = self._param_table()
+        return diagnostics.diagnose(step, bn_names, bn_counts, ls["names"], trained, ls["skip_out"].cpu().numpy())
 
     # ---- training accuracy: top-k hits of every step's score matrix, counted on the device ----------------------------------------------------------------
     # The head leaves the step's (B, classes) scores in the persistent `scores` buffer; with the option on, ONE mvf_metrics_update (no confusion matrix: 16
