@@ -529,6 +529,27 @@ int mvf_ce_loss_soft(const float* scores, const float* targets, int clips, int c
 int mvf_head_train_fwd_soft(const void* feat, int clips, int t, int hw, int c, const float* fc_w, const float* fc_b, int classes,
                             const float* targets, const float* drop_mask /* (clips*t, c) pre-scaled keep mask or NULL */,
                             float* pooled, float* scores, float* dscores, float* loss_part, float* loss, int dtype, void* stream);
+/* Knowledge distillation (Hinton's loss) behind mvf_head_train_fwd / mvf_head_train_fwd_soft, which left the cross-entropy's dscores (clips, classes),
+ * loss_part (clips) and loss (1) in device memory; scores = the student's (clips, classes), teacher_scores = the teacher's, all fp32.  Per clip i, with
+ * s = scores[i], z = teacher_scores[i], T = temperature, a = alpha, p = softmax(z / T), q = softmax(s / T):
+ *   kd_i          = sum_k p_k * ((z_k / T - s_k / T) - (lse(z / T) - lse(s / T)))        -- KL(p || q); exactly 0 when z and s hold the same bits, and for
+ *                                                                                           one class
+ *   loss_part[i] <- (1 - a) * loss_part[i] + a * T * T * kd_i
+ *   dscores[i][k] <- (1 - a) * dscores[i][k] + a * T * (q_k - p_k) / clips
+ *   loss[0]      <- the mean of the new loss_part, clips in a fixed order
+ *   terms[0]      = the mean of the INCOMING loss_part (the cross-entropy term), terms[1] = the mean of T * T * kd_i; terms may be NULL, the other outputs
+ *                   are then the same bits
+ * i.e. (1 - a) * CE + a * T^2 * kl_div(log_softmax(s / T), softmax(z / T), 'batchmean') and its gradient with respect to the scores.
+ * Precision: all per-row arithmetic runs in fp64 -- inputs are widened, exp / log are taken in double, 1 - a is formed in double from the fp32 a, sums have
+ * a fixed order (wavefront shuffle tree, wave partials in wave order, clips ascending) -- and every output is rounded to fp32 once.  No atomics, no
+ * workspace: bit-identical from run to run.  temperature and alpha travel as float (a launch plan's call record carries no double).
+ * MVF_EINVAL, checked before any launch (nothing is enqueued, no output is touched): a NULL scores / teacher_scores / dscores / loss_part / loss; clips < 1 or
+ * classes < 1; temperature not finite or <= 0; alpha not finite or outside (0, 1].
+ * A NaN or inf in a row of teacher_scores (or scores) makes that row's loss_part and dscores, loss[0] and terms[1] NaN: the non-finite step guard then
+ * skips the step.  scores / teacher_scores must not overlap the outputs. */
+int mvf_distill_loss(const float* scores, const float* teacher_scores, int clips, int classes, float temperature, float alpha,
+                     float* dscores /* in/out */, float* loss_part /* in/out */, float* loss /* out */, float* terms /* out, 2 floats, or NULL */,
+                     void* stream);
 /* RandomErasing (timm's, as PySlowFast and mmaction2 use it) on the stem operand, IN PLACE.  xp = (planes, hp, wp, 4) in `dtype` as mvf_stem_prep lays it
  * out, 16-byte aligned; no plane reads another plane.  One table per step, three DEVICE arrays:
  *   boxes int32  (planes, max_boxes, 5): y0, x0, y1, x1, mode -- a half-open box in image pixels (before the pad), 0 <= y0 <= y1 <= H, 0 <= x0 <= x1 <= W;

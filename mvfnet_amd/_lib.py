@@ -251,6 +251,8 @@ def _load():
     lib.mvf_ce_loss_soft.argtypes = [fp, fp, i32, i32, fp, fp, fp, vp]
     lib.mvf_head_train_fwd_soft.restype = i32
     lib.mvf_head_train_fwd_soft.argtypes = [vp, i32, i32, i32, i32, fp, fp, i32, fp, fp, fp, fp, fp, fp, fp, i32, vp]
+    lib.mvf_distill_loss.restype = i32
+    lib.mvf_distill_loss.argtypes = [fp, fp, i32, i32, f32, f32, fp, fp, fp, fp, vp]
     lib.mvf_head_train_bwd.restype = i32
     lib.mvf_head_train_bwd.argtypes = [fp, fp, fp, fp, i32, i32, i32, i32, i32, fp, fp, fp, vp, i32, vp]
     lib.mvf_conv2d_wgrad_workspace_bytes.restype = sz

@@ -294,17 +294,40 @@ class BackboneEngine(object):
                 raise RuntimeError("uint8 frames need engine.input_pipeline = preprocess.FramePipeline(...)")
             nt = self.n_images(x_nchw, window)
             h, w = self.input_pipeline.crop_hw
-            hp, wp = h + 2 * pad, (w + 2 * pad + 2 + 1) // 2 * 2
+            wp = self.stem_operand_shape(nt, h, w)[2]
             xp = self.input_pipeline.to_stem(x_nchw, window, pad, wp, self.dtype)
         else:
             nt, cin, h, w = x_nchw.shape
-            hp, wp = h + 2 * pad, (w + 2 * pad + 2 + 1) // 2 * 2
-            xp = torch.empty(nt, hp, wp, 4, dtype=self.dtype, device=x_nchw.device)
+            wp = self.stem_operand_shape(nt, h, w)[2]
+            xp = torch.empty(self.stem_operand_shape(nt, h, w), dtype=self.dtype, device=x_nchw.device)
             check(lib.mvf_stem_prep(_p(x_nchw), nt, cin, h, w, pad, wp, _p(xp), _DT[self.dtype], _stream()), "mvf_stem_prep")
+        return self._from_stem(xp, nt, h, w, stages, out)
+
+    def stem_operand_shape(self, nt, h, w):
+        """(nt, h + 2 * pad, wp, 4): the padded NHWC4 operand mvf_stem_prep and the frame kernels make of nt images of h x w pixels."""
+        pad = self.stem.stem_pad
+        return nt, h + 2 * pad, (w + 2 * pad + 2 + 1) // 2 * 2, 4
+
+    def forward_stem(self, xp, nt, h, w, out=None):
+        """The stem conv, the max-pool and the blocks on a GIVEN stem operand (what mvf_stem_prep, the uint8 / YUV / addressed frame kernels, mvf_stem_erase
+        and mvf_stem_blend produce): xp (nt, h + 2 * pad, wp, 4) in the engine's dtype -> features (nt, hf, wf, 2048).  One chain on the current stream;
+        the bits of forward() on the images that operand was made of.  A training engine hands its own operand to a second model here (distill.py)."""
+        if not torch.is_tensor(xp) or not xp.is_cuda:
+            raise RuntimeError("forward_stem: the stem operand must be a GPU tensor")
+        if xp.dtype != self.dtype:
+            raise TypeError("forward_stem: the stem operand is %s, this engine was built for %s" % (xp.dtype, self.dtype))
+        want = self.stem_operand_shape(nt, h, w)
+        if tuple(xp.shape) != want or not xp.is_contiguous():
+            raise ValueError("forward_stem: a contiguous stem operand %s is expected for %d images of %d x %d, got %s" % (want, nt, h, w, tuple(xp.shape)))
+        return self._from_stem(xp, nt, h, w, None, out)
+
+    def _from_stem(self, xp, nt, h, w, stages=None, out=None):
+        pad = self.stem.stem_pad
+        hp, wp = xp.shape[1], xp.shape[2]
         ho, wo = (h + 2 * pad - self.stem.kh) // 2 + 1, (w + 2 * pad - 7) // 2 + 1
         y, _, _ = self.stem.run(xp, nt, hp, wp, 4, ho=ho, wo=wo, stride=2, pad=0)
         h2, w2 = (ho + 2 - 3) // 2 + 1, (wo + 2 - 3) // 2 + 1
-        p = torch.empty(nt, h2, w2, self.stem.cout, dtype=self.dtype, device=x_nchw.device)
+        p = torch.empty(nt, h2, w2, self.stem.cout, dtype=self.dtype, device=xp.device)
         check(lib.mvf_maxpool3x3s2_nhwc(_p(y), nt, ho, wo, self.stem.cout, _p(p), _DT[self.dtype], _stream()), "mvf_maxpool3x3s2_nhwc")
         if stages is not None:
             stages["maxpool"] = p
@@ -336,21 +359,25 @@ class HeadEngine(object):
     def b(self):
         return self.fc.bias.detach().to(device=self.device, dtype=torch.float32).contiguous() if self.fc.bias is not None else None
 
-    def scores(self, feat, num_seg):
-        return self._pool_fc(feat, num_seg)[1]
+    def scores(self, feat, num_seg, out=None):
+        """(clips, classes) fp32 scores; out: a contiguous fp32 buffer of that shape to write them into (a train engine's persistent one)."""
+        return self._pool_fc(feat, num_seg, out)[1]
 
     def features(self, feat, num_seg):
         """TSNClsHead(extract_feat=True) (tsn_clshead.py:88-98, :110-112): the consensus of the pooled features, (clips, in_channels) fp32
         -- the mean over the clip's num_seg * h * w positions, which is the buffer mvf_head_pool_fc pools into before its FC."""
         return self._pool_fc(feat, num_seg)[0]
 
-    def _pool_fc(self, feat, num_seg):
+    def _pool_fc(self, feat, num_seg, out=None):
         nt, h, w, c = feat.shape
         if c != self.c or nt % num_seg:
             raise ValueError("head: features %s do not match in_channels=%d / num_seg=%d" % (tuple(feat.shape), self.c, num_seg))
         clips = nt // num_seg
         pooled = torch.empty(clips, c, dtype=torch.float32, device=feat.device)
-        out = torch.empty(clips, self.classes, dtype=torch.float32, device=feat.device)
+        if out is None:
+            out = torch.empty(clips, self.classes, dtype=torch.float32, device=feat.device)
+        elif tuple(out.shape) != (clips, self.classes) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != feat.device:
+            raise ValueError("head: the score buffer %s %s does not match (%d, %d) float32" % (tuple(out.shape), out.dtype, clips, self.classes))
         wgt, bias = self.w, self.b            # kept alive until the launch is queued
         check(lib.mvf_head_pool_fc(_p(feat), clips, num_seg, h * w, c, _p(wgt), _p(bias), self.classes, _p(pooled), _p(out),
                                    _DT[feat.dtype], _stream()), "mvf_head_pool_fc")

@@ -69,6 +69,13 @@ class Recognizer2D(nn.Module):
         randaug_cfg = train_cfg.get("randaug") if hasattr(train_cfg, "get") else getattr(train_cfg, "randaug", None)
         self.randaug = build_randaug(randaug_cfg)
         self.module_cfg = dict(module_cfg) if module_cfg else module_cfg
+        # train_cfg=dict(distill=dict(type='KnowledgeDistillation', teacher=..., temperature=4.0, alpha=0.5)): the teacher scores the step's stem operand and
+        # the loss becomes (1 - alpha) * CE + alpha * T^2 * KL on the device, likewise.  A plain object, not a module: the teacher is no submodule of this model
+        from ..distill import build_distill
+        distill_cfg = train_cfg.get("distill") if hasattr(train_cfg, "get") else getattr(train_cfg, "distill", None)
+        self.distill = build_distill(distill_cfg)
+        if self.distill is not None and hasattr(self.distill, "check_student"):
+            self.distill.check_student(self, device=False)
         self.in_channels = 3
         if self.module_cfg:
             # reference recognizer2d.py:45-59: weights are initialised/loaded BEFORE the MVF wrappers exist
@@ -146,12 +153,13 @@ class Recognizer2D(nn.Module):
         return self
 
     def _set_soft_options(self, eng, training):
-        """The ONE place train_cfg['blending'], train_cfg['erasing'], train_cfg['randaug'] and the head's label_smooth_eps reach the engine: only while the model trains.  Called
-        when the engine is created, whenever the mode changes (train() / eval()) and by forward_train.  engine.blending / engine.erasing / engine.randaug /
+        """The ONE place train_cfg['blending'], train_cfg['erasing'], train_cfg['randaug'], train_cfg['distill'] and the head's label_smooth_eps reach the engine: only while the model trains.  Called
+        when the engine is created, whenever the mode changes (train() / eval()) and by forward_train.  engine.blending / engine.erasing / engine.randaug / engine.distill /
         engine.label_smooth_eps are plain attributes: whoever drives engine.train_step directly may also set them by hand, until the next of these calls."""
         eng.blending = self.blending if training else None
         eng.erasing = self.erasing if training else None
         eng.randaug = self.randaug if training else None
+        eng.distill = self.distill if training else None       # train_cfg['distill'] (distill.py): the same rule
         eng.label_smooth_eps = float(getattr(self.cls_head, "label_smooth_eps", 0.0)) if training else 0.0
 
     def forward_train(self, imgs, labels, **kwargs):

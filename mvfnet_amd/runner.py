@@ -420,6 +420,8 @@ class Runner(object):
         (TrainEngine.enable_train_accuracy: one small launch per forward, outside the launch plans) and the log line gains ` top1 %.4f top5 %.4f` -- the
         accuracy over the steps since the previous log line -- after grad_norm, read where the loop synchronises anyway.  Steps under blending or with soft
         labels are not counted; a window without counted rows logs nan.  Under a process group each rank counts its own share and rank 0 logs its own.
+        A model built with train_cfg=dict(distill=...) (distill.py) needs no option here: while its engine has `distill` set, loss_cls is the combined loss and
+        the log line gains ` loss_ce %.4f loss_kd %.4f` -- the last step's two terms (TrainEngine.distill_terms) -- behind the accuracy fields.
         lr_policy = None (the step schedule of lr_steps / lr_gamma), dict(policy='cosine', min_lr= | min_lr_ratio=, by_epoch=True) or dict(policy='poly',
         power=1.0, min_lr=0.0, by_epoch=True): mmcv's CosineAnnealing / Poly updater hooks (cosine_lr / poly_lr) with the same warm-up on top; max_epochs and
         max_iters (optimizer steps) are learned in run().
@@ -542,6 +544,14 @@ class Runner(object):
         fig = self.engine.train_accuracy()
         return "".join(" top%d %.4f" % (kk, fig["top%d" % kk]) for kk in self.train_accuracy["k"])
 
+    def _distill_note(self):
+        """' loss_ce %.4f loss_kd %.4f' for the log line while the engine distils (engine.distill set: train_cfg['distill']): the two terms loss_cls combines,
+        of the last step (an 8-byte synchronising read, on the logging rank only, where the line's loss and norm are read anyway); '' otherwise."""
+        if getattr(self.engine, "distill", None) is None:
+            return ""
+        fig = self.engine.distill_terms()
+        return " loss_ce %.4f loss_kd %.4f" % (fig["loss_ce"], fig["loss_kd"])
+
     def _apply_accumulated(self, rank):
         lr = self.current_lr()
         self._arm_layer_stats()
@@ -552,7 +562,7 @@ class Runner(object):
             note = self._check_guard()               # on every rank: all of them take the same decisions, so all of them stop together
             if rank == 0:
                 self.log("Epoch [%d] iter %d lr %.5f loss_cls %.4f grad_norm %.3f%s%s%s" % (
-                    self.epoch + 1, self.iter, lr, float(self.engine.accumulated_loss), float(self.engine.norm_out[0]), self._accuracy_note(), note, layers))
+                    self.epoch + 1, self.iter, lr, float(self.engine.accumulated_loss), float(self.engine.norm_out[0]), self._accuracy_note() + self._distill_note(), note, layers))
 
     def _train_epoch_accumulated(self, loader, rank):
         """One micro-step per loader batch; the optimizer runs after every k-th batch and after the epoch's last one (a shorter trailing group is applied
@@ -584,7 +594,7 @@ class Runner(object):
                 note = self._check_guard()           # on every rank: all of them take the same decisions, so all of them stop together
                 if rank == 0:
                     self.log("Epoch [%d] iter %d lr %.5f loss_cls %.4f grad_norm %.3f%s%s%s" % (
-                        self.epoch + 1, self.iter, lr, float(loss), float(self.engine.norm_out[0]), self._accuracy_note(), note, layers))
+                        self.epoch + 1, self.iter, lr, float(loss), float(self.engine.norm_out[0]), self._accuracy_note() + self._distill_note(), note, layers))
         self._check_guard()                          # always at epoch end, before a checkpoint is written
         self.epoch += 1
         if rank == 0 and self.work_dir and self.ckpt_interval and self.epoch % self.ckpt_interval == 0:

@@ -1870,6 +1870,11 @@ class TrainEngine(_ParamStore):
         # path never runs from a launch plan: no plan key.  With None the step allocates and launches exactly what it did without it.
         self.randaug = None
         self._randaug_table = None
+        # Knowledge distillation (distill.py: an object with teacher_scores(xp, b, t, h, w, out=), temperature and alpha, and optionally check_step(model, dtype); None = off): the teacher's
+        # eval-mode launch chain on the finished stem operand, and one mvf_distill_loss behind the head.  An instance attribute: no plan-key switch.  Steps with
+        # it run eagerly (_plan_key); with None the step allocates and launches exactly what it did without it.
+        self.distill = None
+        self._distill_terms = None
 
     def _pack_all(self, kind):
         """All forward (kind 0) or data-gradient (kind 1) weight packs in ONE launch (mvf_pack_conv_weights_batched); the job
@@ -1906,6 +1911,8 @@ class TrainEngine(_ParamStore):
             raise RuntimeError("TrainEngine.forward: float32 (or uint8 frames) GPU input required")
         if self.randaug is not None:
             self._randaug_refusals(imgs)
+        if self.distill is not None:
+            self._distill_refusals()
         if self._ema_swapped:
             self._ema_live("a training forward")
         self._main = torch.cuda.current_stream()
@@ -2026,6 +2033,13 @@ class TrainEngine(_ParamStore):
         if pipe is not None and (imgs.dim() != 5 or imgs.shape[-1] != 3):
             raise ValueError("TrainEngine: randaug takes (B, T, Hs, Ws, 3) uint8 frames, got %s" % (tuple(imgs.shape),))
 
+    def _distill_refusals(self):
+        """A teacher that cannot teach this model (the model itself, another device, class count or n_segment) or a request for a teacher in another
+        storage dtype is refused before the step's first launch (distill.KnowledgeDistillation.check_step; an object without it checks for itself)."""
+        chk = getattr(self.distill, "check_step", None)
+        if chk is not None:
+            chk(self.model, self.tdtype)
+
     def _draw_randaug(self, imgs):
         """The step's RandAugment table, drawn and validated on the host and uploaded as the other step tables are; the frame sizes are columns 0..1 of the
         window table for the resampling pipelines, the tensor's own (hs, ws) otherwise.  -> (table, sizes | None, layers, statistics mask, order)."""
@@ -2119,6 +2133,12 @@ class TrainEngine(_ParamStore):
             xb = self.buf("xp_blend", (nt, hp, wp, 4))
             check(lib.mvf_stem_blend(_p(xp), b, t, hp, wp, 3, _p(rows_d), _p(wts_d), _p(xb), self.dt, _st()), "stem_blend")
             xp = xb
+        teacher_scores = None
+        if self.distill is not None:
+            # the operand is complete (erased, blended): the teacher's whole chain runs here, on the launch stream, in front of the student's stem -- one
+            # model after the other, so the two share the conv kernel's stream-K scratch of this stream as consecutive convs of one model do
+            teacher_scores = self.buf("teacher_scores", (b, self.num_classes), torch.float32)
+            self.distill.teacher_scores(xp, b, t, h, w, out=teacher_scores)
         ho, wo = (h + 6 - 7) // 2 + 1, (w + 6 - 7) // 2 + 1
         z0, _, _ = self.stem.forward(xp, nt, hp, wp, ho=ho, wo=wo, bn=self.stem_bn)
         h2, w2 = (ho - 1) // 2 + 1, (wo - 1) // 2 + 1
@@ -2158,10 +2178,24 @@ class TrainEngine(_ParamStore):
         else:
             check(lib.mvf_head_train_fwd(_p(xcur), b, t, hc * wc, cc, _p(self.fc_w), _p(self.fc_b), self.num_classes, _p(lab), _p(mask), _p(pooled),
                                          _p(scores), _p(dscores), _p(loss_part), _p(loss), self.dt, _st()), "head fwd")
+        if teacher_scores is not None:
+            # the head left the cross-entropy's dscores / loss_part / loss: they become the combined loss's in place, whatever kind of labels made them
+            terms = self._distill_terms = self.buf("distill_terms", (2,), f32)
+            check(lib.mvf_distill_loss(_p(scores), _p(teacher_scores), b, self.num_classes, C.c_float(self.distill.temperature), C.c_float(self.distill.alpha),
+                                       _p(dscores), _p(loss_part), _p(loss), _p(terms), _st()), "distill loss")
+            self.saved.update(teacher_scores=teacher_scores)
         self.saved.update(pooled=pooled, dscores=dscores, mask=mask, hw=hc * wc, c=cc, feat_shape=xcur.shape, scores=scores)
         if self._nbt_touched:
             self._count_batches()
         return loss
+
+    def distill_terms(self):
+        """dict(loss_ce, loss_kd) of the last distilled step (under accumulation: of its last micro-step): the mean cross-entropy and the mean T^2 * KL that
+        mvf_distill_loss combined into the step's loss.  An 8-byte read that waits for the device: the only synchronising call of the option."""
+        if self._distill_terms is None:
+            raise RuntimeError("distill_terms: no step has run with engine.distill set (train_cfg['distill'], distill.KnowledgeDistillation)")
+        ce, kd = self._distill_terms.tolist()
+        return dict(loss_ce=ce, loss_kd=kd)
 
     def _count_batches(self):
         """num_batches_tracked += 1 of every BatchNorm in training mode: one launch (see _BN._count)."""
@@ -2306,6 +2340,8 @@ class TrainEngine(_ParamStore):
             return None                  # frozen statistics are folded per step by torch calls (_BN.use_running_stats)
         if self.erasing is not None and getattr(self.erasing, "max_boxes", None) is None:
             return None                  # an erasing object that does not name its table width (max_boxes) may change it from step to step
+        if self.distill is not None:
+            return None                  # the teacher's calls go through engine.py, which a plan does not record; back at None the recorded plans are replayed
         sw = self.__dict__.get("_switch_names")
         if sw is None:
             sw = self._switch_names = sorted(k for c_ in type(self).__mro__ for k, v in vars(c_).items()
@@ -2352,6 +2388,8 @@ class TrainEngine(_ParamStore):
         recorded by train_step carries the tail bucket's collective, which a micro-step must not issue -- those micro-steps run eagerly, never from a plan."""
         if self.randaug is not None:
             self._randaug_refusals(imgs)
+        if self.distill is not None:
+            self._distill_refusals()
         if self._ema_swapped:
             self._ema_live("a training step")
         if self._guard is not None:
@@ -2750,7 +2788,7 @@ class TrainEngine(_ParamStore):
             bad = [key for key, (first, k, _) in zip(tab.keys, tab.slices) if not bool(torch.isfinite(tab.shadow[first:first + k]).all())]
             raise RuntimeError("precise_bn: non-finite running statistics on entry (%s); nothing was changed" % ", ".join(bad[:4]))
         nbt = self._nbt_flat.clone()
-        state = [(b, b.momentum) for b in bns], self.blending, self.dropout, self.erasing, self.randaug
+        state = [(b, b.momentum) for b in bns], self.blending, self.dropout, self.erasing, self.randaug, self.distill
         tab.acc.zero_()
         used, done, swapped = 0, False, False
         if self._guard is not None:
@@ -2763,6 +2801,7 @@ class TrainEngine(_ParamStore):
             for b in bns:
                 b.momentum = 1.0
             self.blending, self.dropout, self.erasing, self.randaug = None, 0.0, None, None
+            self.distill = None                  # no teacher forward, no mvf_distill_loss: the calibration needs the student's batch statistics alone
             for imgs, labels in itertools.islice(batches, num_iters):
                 self.forward(imgs, labels)
                 with on():
@@ -2781,7 +2820,7 @@ class TrainEngine(_ParamStore):
         finally:
             for b, m in state[0]:
                 b.momentum = m
-            self.blending, self.dropout, self.erasing, self.randaug = state[1], state[2], state[3], state[4]
+            self.blending, self.dropout, self.erasing, self.randaug, self.distill = state[1], state[2], state[3], state[4], state[5]
             side = getattr(self, "_side", None)
             if side is not None:
                 torch.cuda.current_stream().wait_stream(side)      # the forwards' data-gradient weight packs read the parameters there
