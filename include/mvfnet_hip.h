@@ -683,7 +683,9 @@ int mvf_pack_conv_weight_dgrad(const float* w_oihw, int cout, int cin, int kh, i
                                void* stream);
 /* MVF training primitives, channels-last (the engine composes MVF fwd/bwd from these + the BN calls above) */
 /* out[..., :cs] = f(stencil(x[..., :cs])) [+ addend[..., :cs] (pitch addend_c; NULL = none), gated per channel by
- * addend_sign_bits ([pixels][addend_c/4] bytes as written by mvf_bn_apply_bits; NULL = ungated)]; flip = transposed stencil */
+ * addend_sign_bits ([pixels][addend_c/4] bytes as written by mvf_bn_apply_bits; NULL = ungated)]; flip = transposed stencil.
+ * Channels >= cs of a wider `out` are left as they are -- EXCEPT when x and out have the same pitch (x_c == out_c > cs): the call then also copies channels
+ * [cs, x_c) of every pixel from x to out (the pass-through channels of the MVF module, a second launch), for every entry point of this family. */
 int mvf_nhwc_stencil(const mvf_desc_t* d, const void* x, int x_c, void* out, int out_c, const float* w_t,
                      const float* w_h, const float* w_w, const float* scale, const float* shift, int flip,
                      const void* addend, int addend_c, const unsigned char* addend_sign_bits, void* stream);
@@ -710,6 +712,49 @@ int mvf_nhwc_stencil_stats(const mvf_desc_t* d, const void* x, int x_c, void* ou
 size_t mvf_nhwc_tapgrad_workspace_bytes(const mvf_desc_t* d);
 int mvf_nhwc_tapgrad(const mvf_desc_t* d, const void* x, int x_c, const void* dy, int dy_c, float* dw_t, float* dw_h,
                      float* dw_w, void* ws, size_t ws_bytes, void* stream);
+/* Which kernel the calling thread's LAST mvf_nhwc_stencil* / mvf_nhwc_tapgrad call launched: the MVF primitives' counterpart of
+ * mvf_conv2d_wgrad_last_launch (host-side, thread-local, plain stores next to the launches; no device work).  A call refused before its first launch
+ * leaves launches = 0 and kernel = NONE; the plan queries (mvf_nhwc_stencil_stats_rows, mvf_nhwc_stencil_tile_plan) leave the record alone. */
+enum {
+    MVF_STENCIL_KERNEL_NONE = 0,
+    MVF_STENCIL_KERNEL_WALK1 = 1,    /* mvf_nhwc_apply<T, 1>: one channel per thread, serial walk over t (cs or a pitch % 4 != 0, misaligned operands) */
+    MVF_STENCIL_KERNEL_WALK4 = 2,    /* mvf_nhwc_apply<T, 4>: four channels per thread, serial walk (policy stencil_chunked=0, taps not 16-byte aligned) */
+    MVF_STENCIL_KERNEL_CHUNKED = 3,  /* mvf_nhwc_apply_chunked<T, 4 | 8>: all loads of a chunk of frames in flight at once                             */
+    MVF_STENCIL_KERNEL_LDS = 4       /* mvf_nhwc_apply_lds<T, CW>: bf16, a (band of rows, CW channels, all frames) tile in LDS                         */
+};
+enum {
+    MVF_STENCIL_FLIP = 1, MVF_STENCIL_HSWISH = 2, MVF_STENCIL_ADDEND = 4, MVF_STENCIL_ADDEND_BITS = 8, MVF_STENCIL_OUT_GATE = 16,
+    MVF_STENCIL_STATS = 32,          /* partial sums were written (the statistics of mvf_nhwc_stencil_stats or the column sums of _gate_colsums)       */
+    MVF_STENCIL_TAIL_COPY = 64       /* x_c == out_c > cs: channels >= cs were copied from x to out by a second launch                                */
+};
+typedef struct {
+    int32_t kernel;                  /* MVF_STENCIL_KERNEL_*                                                                          */
+    int32_t dtype;                   /* MVF_F32 | MVF_BF16                                                                            */
+    int32_t frames_per_chunk;        /* CHUNKED: 4 (fp32) | 8 (bf16); the walk and the LDS kernel: 0                                  */
+    int32_t rows_per_band, chan_per_wg;   /* LDS: the tile (as mvf_nhwc_stencil_tile_plan); else 0                                    */
+    int32_t bands;                   /* workgroups per clip along the pixels                                                          */
+    int32_t pixels_per_wg;           /* pixels of one frame a workgroup owns (LDS: rows_per_band * w); it owns them in all T frames   */
+    int32_t grid_x, grid_y;          /* clips * bands, channel slabs                                                                  */
+    int32_t partial_rows;            /* rows of stats_part / sums_part per channel (= grid_x); 0 without MVF_STENCIL_STATS            */
+    int32_t flags;                   /* MVF_STENCIL_* bits                                                                            */
+    int32_t launches;                /* 1, or 2 with the tail copy                                                                    */
+} mvf_stencil_launch_info_t;
+int mvf_nhwc_stencil_last_launch(mvf_stencil_launch_info_t* out);
+enum {
+    MVF_TAPGRAD_KERNEL_NONE = 0,
+    MVF_TAPGRAD_KERNEL_ROWS = 1,     /* mvf_nhwc_tapgrad_rows_kernel: contiguous ranges of the (n, t, h, w) rows                      */
+    MVF_TAPGRAD_KERNEL_BANDS = 2     /* mvf_nhwc_tapgrad_kernel: (clip, band of pixels) workgroups walking t (policy tapgrad_rows=0)  */
+};
+typedef struct {
+    int32_t kernel;                  /* MVF_TAPGRAD_KERNEL_*                                                                          */
+    int32_t dtype;
+    int32_t nblk;                    /* partial rows [nblk][cs][7] the finalize kernel sums (= grid x)                                */
+    int32_t rows_per_blk;            /* ROWS: rows per block; BANDS: pixels of one frame per block (it owns them in all T frames)     */
+    int32_t cgp;                     /* threads along the 4-channel groups per block                                                  */
+    int32_t grid_y;                  /* channel slabs                                                                                 */
+    int32_t launches;                /* the partial sums and their finalize: 2                                                        */
+} mvf_tapgrad_launch_info_t;
+int mvf_nhwc_tapgrad_last_launch(mvf_tapgrad_launch_info_t* out);
 /* clip_grad_norm_(max_norm) on grad_scale*grads, then torch.optim.SGD(nesterov) on flat fp32 buffers.
  * norm_out[0] = total norm, norm_out[1] = clip coefficient. */
 size_t mvf_sgd_workspace_bytes(long n);

@@ -55,6 +55,26 @@ WGRAD_FAMILIES = {0: "none", 1: "f32_reg", 2: "f32_dma", 3: "x3", 4: "bf16_widen
                   10: "c3x3_c64", 11: "stem"}
 
 
+class StencilLaunchInfo(C.Structure):
+    """mvf_stencil_launch_info_t: which kernel the calling thread's last mvf_nhwc_stencil* call launched (host-side record)."""
+    _fields_ = [("kernel", C.c_int32), ("dtype", C.c_int32), ("frames_per_chunk", C.c_int32), ("rows_per_band", C.c_int32), ("chan_per_wg", C.c_int32),
+                ("bands", C.c_int32), ("pixels_per_wg", C.c_int32), ("grid_x", C.c_int32), ("grid_y", C.c_int32), ("partial_rows", C.c_int32),
+                ("flags", C.c_int32), ("launches", C.c_int32)]
+
+
+STENCIL_KERNELS = {0: "none", 1: "walk1", 2: "walk4", 3: "chunked", 4: "lds"}
+STENCIL_FLIP, STENCIL_HSWISH, STENCIL_ADDEND, STENCIL_ADDEND_BITS, STENCIL_OUT_GATE, STENCIL_STATS, STENCIL_TAIL_COPY = 1, 2, 4, 8, 16, 32, 64
+
+
+class TapgradLaunchInfo(C.Structure):
+    """mvf_tapgrad_launch_info_t: which kernel the calling thread's last mvf_nhwc_tapgrad call launched (host-side record)."""
+    _fields_ = [("kernel", C.c_int32), ("dtype", C.c_int32), ("nblk", C.c_int32), ("rows_per_blk", C.c_int32), ("cgp", C.c_int32), ("grid_y", C.c_int32),
+                ("launches", C.c_int32)]
+
+
+TAPGRAD_KERNELS = {0: "none", 1: "rows", 2: "bands"}
+
+
 class PackJob(C.Structure):
     _fields_ = [("w", C.c_void_p), ("out", C.c_void_p), ("cout", C.c_int32), ("cin", C.c_int32), ("kh", C.c_int32), ("kw", C.c_int32),
                 ("kw_pad", C.c_int32), ("cin_pad", C.c_int32), ("kind", C.c_int32), ("first_block", C.c_int32)]
@@ -271,6 +291,10 @@ def _load():
     lib.mvf_nhwc_tapgrad_workspace_bytes.argtypes = [dp]
     lib.mvf_nhwc_tapgrad.restype = i32
     lib.mvf_nhwc_tapgrad.argtypes = [dp, vp, i32, vp, i32, fp, fp, fp, vp, sz, vp]
+    lib.mvf_nhwc_stencil_last_launch.restype = i32
+    lib.mvf_nhwc_stencil_last_launch.argtypes = [C.POINTER(StencilLaunchInfo)]
+    lib.mvf_nhwc_tapgrad_last_launch.restype = i32
+    lib.mvf_nhwc_tapgrad_last_launch.argtypes = [C.POINTER(TapgradLaunchInfo)]
     lib.mvf_sgd_workspace_bytes.restype = sz
     lib.mvf_sgd_workspace_bytes.argtypes = [i64]
     lib.mvf_sgd_nesterov_step.restype = i32

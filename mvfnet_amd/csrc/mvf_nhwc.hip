@@ -21,6 +21,11 @@ namespace {
 
 constexpr int kThreads = 256;
 
+// Host-side records of the calling thread's last stencil / tap-gradient call (mvf_nhwc_stencil_last_launch, mvf_nhwc_tapgrad_last_launch): plain host stores
+// next to the launches, nothing on the device.
+thread_local mvf_stencil_launch_info_t t_last_stencil = {};
+thread_local mvf_tapgrad_launch_info_t t_last_tapgrad = {};
+
 struct NhwcArgs {
     const void* x;
     void* out;
@@ -557,6 +562,7 @@ __global__ void copy_tail_nhwc(const ET* src, ET* dst, long npix, int c, int cs)
 struct NhwcFlip { int flip; const void* add; int add_c; const unsigned char* add_mask; const unsigned char* out_gate; float* stats_part; const float* stats_shift; int rows_only; };
 int mvf_nhwc_fwd_infer_impl2(const mvf_desc_t* d, const void* x, void* out, int out_c, const float* wt, const float* wh,
                              const float* ww, const float* scale, const float* shift, NhwcFlip fl, hipStream_t st) {
+    if (!fl.rows_only) t_last_stencil = mvf_stencil_launch_info_t{};      // (a plan query leaves the record alone)
     // In-place hazard: a workgroup re-reads neighbour pixels that another workgroup may already have overwritten.
     MVF_REQUIRE(x != out, MVF_EINVAL,
                 "mvf_fwd_infer(NHWC): in-place is not supported in this layout (neighbour pixels are re-read from "
@@ -613,7 +619,23 @@ int mvf_nhwc_fwd_infer_impl2(const mvf_desc_t* d, const void* x, void* out, int 
     // [r3] all of a chunk's loads in flight at once instead of the serial walk over t (policy stencil_chunked=0: the walk)
     static const int chunked_env = mvf_policy_int("stencil_chunked", 1);
     const bool chunked = chunked_env != 0 && vec && ((uintptr_t)wt | (uintptr_t)(wh ? wh : wt) | (uintptr_t)(ww ? ww : wt)) % 16 == 0;
-    MVF_REQUIRE(!fl.stats_part || chunked, MVF_EUNSUPPORTED, "nhwc_stencil_stats: needs the chunked 4-channel kernel (cs, pitches %% 4 == 0, 16-byte aligned taps, policy stencil_chunked != 0)");
+    MVF_REQUIRE(!fl.stats_part || chunked || use_lds, MVF_EUNSUPPORTED, "nhwc_stencil_stats: needs the chunked 4-channel kernel (cs, pitches %% 4 == 0, 16-byte aligned taps, policy stencil_chunked != 0) or the tiled one");
+    mvf_stencil_launch_info_t rec = {};
+    rec.dtype = d->dtype;
+    rec.flags = (fl.flip ? MVF_STENCIL_FLIP : 0) | (scale ? MVF_STENCIL_HSWISH : 0) | (fl.add ? MVF_STENCIL_ADDEND : 0) | (fl.add_mask ? MVF_STENCIL_ADDEND_BITS : 0) |
+                (fl.out_gate ? MVF_STENCIL_OUT_GATE : 0) | (fl.stats_part ? MVF_STENCIL_STATS : 0);
+    if (use_lds) {
+        rec.kernel = MVF_STENCIL_KERNEL_LDS;
+        rec.rows_per_band = lp.rb; rec.chan_per_wg = lp.cw; rec.bands = lp.bands; rec.pixels_per_wg = lp.rb * d->w;
+        rec.grid_x = a.n_clips * lp.bands; rec.grid_y = d->cs / lp.cw;
+    } else {
+        rec.kernel = chunked ? MVF_STENCIL_KERNEL_CHUNKED : (vec ? MVF_STENCIL_KERNEL_WALK4 : MVF_STENCIL_KERNEL_WALK1);
+        rec.frames_per_chunk = chunked ? (d->dtype == MVF_F32 ? 4 : 8) : 0;
+        rec.bands = a.bands; rec.pixels_per_wg = a.pixw; rec.grid_x = (int)grid.x; rec.grid_y = (int)grid.y;
+    }
+    rec.partial_rows = fl.stats_part ? rec.grid_x : 0;
+    rec.launches = 1;
+    t_last_stencil = rec;
     if (use_lds) {
         // launched above
     } else if (d->dtype == MVF_F32) {
@@ -634,6 +656,8 @@ int mvf_nhwc_fwd_infer_impl2(const mvf_desc_t* d, const void* x, void* out, int 
         else
             hipLaunchKernelGGL(copy_tail_nhwc<bf16_t>, dim3(blocks), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)out, npix, d->c, d->cs);
         MVF_LAUNCH_CHECK();
+        t_last_stencil.flags |= MVF_STENCIL_TAIL_COPY;
+        t_last_stencil.launches = 2;
     }
     return MVF_OK;
 }
@@ -959,6 +983,7 @@ extern "C" {
 int mvf_nhwc_stencil(const mvf_desc_t* d, const void* x, int x_c, void* out, int out_c, const float* w_t, const float* w_h,
                      const float* w_w, const float* scale, const float* shift, int flip, const void* addend, int addend_c,
                      const unsigned char* addend_sign_bits, void* stream) {
+    t_last_stencil = mvf_stencil_launch_info_t{};
     MVF_REQUIRE(d && x && out && w_t && x != out && x_c >= d->cs && out_c >= d->cs, MVF_EINVAL, "nhwc_stencil: bad argument");
     MVF_REQUIRE(!addend || addend_c >= d->cs, MVF_EINVAL, "nhwc_stencil: addend pitch < cs");
     MVF_REQUIRE(!addend_sign_bits || (addend && addend_c % 4 == 0), MVF_EINVAL, "nhwc_stencil: gate bits need an addend with pitch % 4 == 0");
@@ -974,6 +999,7 @@ int mvf_nhwc_stencil(const mvf_desc_t* d, const void* x, int x_c, void* out, int
 int mvf_nhwc_stencil_gate(const mvf_desc_t* d, const void* x, int x_c, void* out, int out_c, const float* w_t, const float* w_h,
                           const float* w_w, const float* scale, const float* shift, int flip, const void* addend, int addend_c,
                           const unsigned char* addend_sign_bits, const unsigned char* out_gate_bits, void* stream) {
+    t_last_stencil = mvf_stencil_launch_info_t{};
     MVF_REQUIRE(d && x && out && w_t && x != out && x_c >= d->cs && out_c >= d->cs && out_gate_bits, MVF_EINVAL, "nhwc_stencil_gate: bad argument");
     MVF_REQUIRE(!addend || addend_c >= d->cs, MVF_EINVAL, "nhwc_stencil_gate: addend pitch < cs");
     MVF_REQUIRE(!addend_sign_bits || (addend && addend_c % 4 == 0), MVF_EINVAL, "nhwc_stencil_gate: gate bits need an addend with pitch % 4 == 0");
@@ -989,6 +1015,7 @@ int mvf_nhwc_stencil_gate(const mvf_desc_t* d, const void* x, int x_c, void* out
 int mvf_nhwc_stencil_gate_colsums(const mvf_desc_t* d, const void* x, int x_c, void* out, int out_c, const float* w_t, const float* w_h,
                                   const float* w_w, int flip, const void* addend, int addend_c, const unsigned char* addend_sign_bits,
                                   const unsigned char* out_gate_bits, float* sums_part, void* stream) {
+    t_last_stencil = mvf_stencil_launch_info_t{};
     MVF_REQUIRE(d && x && out && w_t && x != out && x_c >= d->cs && out_c >= d->cs && out_gate_bits && sums_part, MVF_EINVAL, "nhwc_stencil_gate_colsums: bad argument");
     MVF_REQUIRE(!addend || addend_c >= d->cs, MVF_EINVAL, "nhwc_stencil_gate_colsums: addend pitch < cs");
     MVF_REQUIRE(!addend_sign_bits || (addend && addend_c % 4 == 0), MVF_EINVAL, "nhwc_stencil_gate_colsums: gate bits need an addend with pitch % 4 == 0");
@@ -1024,6 +1051,7 @@ int mvf_nhwc_stencil_stats_rows(const mvf_desc_t* d, int x_c, int out_c) {
 }
 int mvf_nhwc_stencil_stats(const mvf_desc_t* d, const void* x, int x_c, void* out, int out_c, const float* w_t, const float* w_h,
                            const float* w_w, float* stats_part, const float* stats_shift, void* stream) {
+    t_last_stencil = mvf_stencil_launch_info_t{};
     MVF_REQUIRE(d && x && out && w_t && x != out && x_c >= d->cs && out_c >= d->cs && stats_part, MVF_EINVAL, "nhwc_stencil_stats: bad argument");
     mvf_desc_t dd = *d;
     dd.c = x_c;
@@ -1042,6 +1070,7 @@ size_t mvf_nhwc_tapgrad_workspace_bytes(const mvf_desc_t* d) {
 // dw_t/dw_h/dw_w [cs][3] = tap gradients of the three views given dy (pitch dy_c) and the forward input x (pitch x_c)
 int mvf_nhwc_tapgrad(const mvf_desc_t* d, const void* x, int x_c, const void* dy, int dy_c, float* dw_t, float* dw_h, float* dw_w,
                      void* ws, size_t ws_bytes, void* stream) {
+    t_last_tapgrad = mvf_tapgrad_launch_info_t{};
     MVF_REQUIRE(d && x && dy && dw_t && d->cs % 4 == 0 && x_c % 4 == 0 && dy_c % 4 == 0, MVF_EINVAL, "nhwc_tapgrad: bad argument (cs %% 4?)");
     MVF_REQUIRE(ws && ws_bytes >= mvf_nhwc_tapgrad_workspace_bytes(d), MVF_EWS, "nhwc_tapgrad: workspace too small");
     const int n_clips = d->nt / d->n_segment;
@@ -1056,8 +1085,10 @@ int mvf_nhwc_tapgrad(const mvf_desc_t* d, const void* x, int x_c, const void* dy
         else
             hipLaunchKernelGGL(mvf_nhwc_tapgrad_rows_kernel<bf16_t>, grid, dim3(kThreads), 0, st, (const bf16_t*)x, x_c, (const bf16_t*)dy, dy_c, rows, d->h, d->w,
                                d->n_segment, d->cs, q.cgp, q.rows_per_blk, (float*)ws);
+        t_last_tapgrad = mvf_tapgrad_launch_info_t{MVF_TAPGRAD_KERNEL_ROWS, d->dtype, q.nblk, q.rows_per_blk, q.cgp, q.gy, 1};
         MVF_LAUNCH_CHECK();
         hipLaunchKernelGGL(mvf_tapgrad_finalize_rows_kernel, dim3((d->cs * 7 + 15) / 16), dim3(256), 0, st, (const float*)ws, q.nblk, d->cs, d->mode, dw_t, dw_h, dw_w);
+        t_last_tapgrad.launches = 2;
         MVF_LAUNCH_CHECK();
         return MVF_OK;
     }
@@ -1067,9 +1098,23 @@ int mvf_nhwc_tapgrad(const mvf_desc_t* d, const void* x, int x_c, const void* dy
         hipLaunchKernelGGL(mvf_nhwc_tapgrad_kernel<float>, grid, dim3(kThreads), 0, st, (const float*)x, x_c, (const float*)dy, dy_c, d->nt, d->h, d->w, d->n_segment, d->cs, p.cgp, p.pixw, p.bands, (float*)ws);
     else
         hipLaunchKernelGGL(mvf_nhwc_tapgrad_kernel<bf16_t>, grid, dim3(kThreads), 0, st, (const bf16_t*)x, x_c, (const bf16_t*)dy, dy_c, d->nt, d->h, d->w, d->n_segment, d->cs, p.cgp, p.pixw, p.bands, (float*)ws);
+    t_last_tapgrad = mvf_tapgrad_launch_info_t{MVF_TAPGRAD_KERNEL_BANDS, d->dtype, n_clips * p.bands, p.pixw, p.cgp, p.gy, 1};
     MVF_LAUNCH_CHECK();
     hipLaunchKernelGGL(mvf_tapgrad_finalize_kernel, dim3((d->cs + 63) / 64), dim3(64), 0, st, (const float*)ws, n_clips * p.bands, d->cs, d->mode, dw_t, dw_h, dw_w);
+    t_last_tapgrad.launches = 2;
     MVF_LAUNCH_CHECK();
+    return MVF_OK;
+}
+
+int mvf_nhwc_stencil_last_launch(mvf_stencil_launch_info_t* out) {
+    MVF_REQUIRE(out, MVF_EINVAL, "nhwc_stencil_last_launch: NULL argument");
+    *out = t_last_stencil;
+    return MVF_OK;
+}
+
+int mvf_nhwc_tapgrad_last_launch(mvf_tapgrad_launch_info_t* out) {
+    MVF_REQUIRE(out, MVF_EINVAL, "nhwc_tapgrad_last_launch: NULL argument");
+    *out = t_last_tapgrad;
     return MVF_OK;
 }
 

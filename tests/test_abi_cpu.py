@@ -140,3 +140,58 @@ def test_refused_weight_gradient_calls_leave_an_empty_launch_record():
         assert lib.mvf_conv2d_wgrad_last_launch(C.byref(info)) == 0
         assert (info.family, info.launches, info.nsplit) == (0, 0, 0)
     assert lib.mvf_conv2d_wgrad_last_launch(None) == -1
+
+
+def test_refused_stencil_calls_leave_an_empty_launch_record():
+    """mvf_nhwc_stencil_last_launch is a host-side record: a stencil call refused before its first launch -- checked here from host addresses that are never
+    read -- leaves launches = 0 and kernel NONE, on each entry point of the family; a plan query does not touch the record."""
+    import ctypes as C
+    from mvfnet_amd import _lib
+    lib = _lib.lib
+    host = (C.c_float * 64)()
+    a = C.cast(host, C.c_void_p)
+    b = C.c_void_p(a.value + 64)
+    info = _lib.StencilLaunchInfo()
+    assert C.sizeof(info) == 12 * 4 and len(_lib.STENCIL_KERNELS) == 5
+    d = _lib.MvfDesc(8, 16, 4, 4, 4, 8, 7, _lib.MVF_NHWC, _lib.MVF_BF16)
+    d3 = _lib.MvfDesc(8, 6, 4, 4, 4, 3, 7, _lib.MVF_NHWC, _lib.MVF_F32)
+    EINVAL, EUNSUPPORTED = -1, -5
+    for rc_want, call in ((EINVAL, lambda: lib.mvf_nhwc_stencil(C.byref(d), a, 16, a, 16, a, a, a, None, None, 0, None, 0, None, None)),           # x == out
+                          (EINVAL, lambda: lib.mvf_nhwc_stencil(C.byref(d), a, 16, b, 8, a, a, a, None, None, 0, a, 4, None, None)),              # addend pitch < cs
+                          (EINVAL, lambda: lib.mvf_nhwc_stencil(C.byref(d), a, 16, b, 8, a, a, a, None, None, 1, None, 0, a, None)),              # bits without an addend
+                          (EINVAL, lambda: lib.mvf_nhwc_stencil_gate(C.byref(d), a, 16, b, 8, a, a, a, None, None, 1, None, 0, None, None, None)),  # no gate bits
+                          (EUNSUPPORTED, lambda: lib.mvf_nhwc_stencil_gate(C.byref(d3), a, 6, b, 6, a, a, a, None, None, 0, None, 0, None, a, None)),  # gate on cs = 3
+                          (EINVAL, lambda: lib.mvf_nhwc_stencil_gate_colsums(C.byref(d), a, 16, b, 8, a, a, a, 1, None, 0, None, a, None, None)),   # no sums_part
+                          (EINVAL, lambda: lib.mvf_nhwc_stencil_stats(C.byref(d), a, 4, b, 8, a, a, a, a, None, None)),                           # x pitch < cs
+                          (EUNSUPPORTED, lambda: lib.mvf_nhwc_stencil_stats(C.byref(d3), a, 6, b, 6, a, a, a, a, None, None))):                   # statistics on cs = 3
+        info.kernel, info.launches, info.grid_x = 99, 99, 99
+        assert call() == rc_want, lib.mvf_last_error()
+        assert lib.mvf_nhwc_stencil_last_launch(C.byref(info)) == 0
+        assert (info.kernel, info.launches, info.grid_x, info.flags) == (0, 0, 0, 0)
+    assert lib.mvf_nhwc_stencil_stats_rows(C.byref(d), 16, 8) > 0
+    assert lib.mvf_nhwc_stencil_last_launch(C.byref(info)) == 0 and (info.kernel, info.launches) == (0, 0)
+    assert lib.mvf_nhwc_stencil_last_launch(None) == -1
+
+
+def test_refused_tap_gradient_calls_leave_an_empty_launch_record():
+    """mvf_nhwc_tapgrad_last_launch: the same for the tap gradients -- a workspace one byte short (MVF_EWS), a NULL workspace, cs % 4 != 0."""
+    import ctypes as C
+    from mvfnet_amd import _lib
+    lib = _lib.lib
+    host = (C.c_float * 64)()
+    a = C.cast(host, C.c_void_p)
+    info = _lib.TapgradLaunchInfo()
+    assert C.sizeof(info) == 7 * 4 and len(_lib.TAPGRAD_KERNELS) == 3
+    d = _lib.MvfDesc(8, 16, 4, 4, 4, 8, 7, _lib.MVF_NHWC, _lib.MVF_F32)
+    d6 = _lib.MvfDesc(8, 16, 4, 4, 4, 6, 7, _lib.MVF_NHWC, _lib.MVF_F32)
+    nb = lib.mvf_nhwc_tapgrad_workspace_bytes(C.byref(d))
+    assert nb > 0 and nb % 256 == 0 and lib.mvf_nhwc_tapgrad_workspace_bytes(C.byref(d6)) == 0
+    for rc_want, call in ((-3, lambda: lib.mvf_nhwc_tapgrad(C.byref(d), a, 16, a, 8, a, a, a, a, nb - 1, None)),
+                          (-3, lambda: lib.mvf_nhwc_tapgrad(C.byref(d), a, 16, a, 8, a, a, a, None, nb, None)),
+                          (-1, lambda: lib.mvf_nhwc_tapgrad(C.byref(d6), a, 16, a, 8, a, a, a, a, nb, None)),
+                          (-1, lambda: lib.mvf_nhwc_tapgrad(C.byref(d), a, 18, a, 8, a, a, a, a, nb, None))):
+        info.kernel, info.launches, info.nblk = 99, 99, 99
+        assert call() == rc_want, lib.mvf_last_error()
+        assert lib.mvf_nhwc_tapgrad_last_launch(C.byref(info)) == 0
+        assert (info.kernel, info.launches, info.nblk) == (0, 0, 0)
+    assert lib.mvf_nhwc_tapgrad_last_launch(None) == -1
