@@ -340,6 +340,10 @@ int mvf_head_pool_fc(const void* feat, int clips, int t, int hw, int c, const fl
                      int classes, float* pooled_ws, float* scores, int dtype, void* stream);
 /* average_clip (codes/models/recognizers/base.py:43-74): kind 0 = None (copy), 1 = 'score', 2 = 'prob'. */
 int mvf_average_clip(const float* scores, int clips, int classes, int kind, float* out, void* stream);
+/* average_clips = 'sigmoid' (multi-label heads): out[k] = the mean over the clips, in ascending order, of sigmoid(scores[cl][k]); fp64 arithmetic that
+ * cannot overflow for either sign of the score, rounded to fp32 once; a NaN score gives a NaN.  scores (clips, classes) -> out (1, classes), any
+ * classes >= 1.  MVF_EINVAL before any launch: NULL scores / out, clips < 1 or classes < 1. */
+int mvf_average_clip_sigmoid(const float* scores, int clips, int classes, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Training step (fp32 this round).  Mirrors, in order: Bottleneck.forward with batch-statistics BatchNorm2d
@@ -529,6 +533,34 @@ int mvf_ce_loss_soft(const float* scores, const float* targets, int clips, int c
 int mvf_head_train_fwd_soft(const void* feat, int clips, int t, int hw, int c, const float* fc_w, const float* fc_b, int classes,
                             const float* targets, const float* drop_mask /* (clips*t, c) pre-scaled keep mask or NULL */,
                             float* pooled, float* scores, float* dscores, float* loss_part, float* loss, int dtype, void* stream);
+/* Binary cross-entropy with logits (csrc/bce.hip): the sigmoid head of multi-label recognition and of BCE training against Mixup / CutMix targets.
+ * scores, targets (clips, classes) fp32; pos_weight (classes) fp32 or NULL (= all ones); target_threshold NaN = off.  Per element, with s the score,
+ * t the target and w = pos_weight[k]:
+ *   t   <- (t > target_threshold) ? 1 : 0                          -- only with the threshold on (timm's bce_target_thresh)
+ *   lw   = 1 + (w - 1) * t
+ *   l    = (1 - t) * s + lw * (max(-s, 0) + log1p(exp(-|s|)))
+ *   dl/ds = (1 - t) - lw * sigmoid(-s),   sigmoid(-s) = e / (1 + e) for s >= 0 and 1 / (1 + e) for s < 0, e = exp(-|s|) <= 1
+ * i.e. torch.nn.functional.binary_cross_entropy_with_logits(s, t, pos_weight=w) and its gradient.  With D = classes (sum_classes = 0, torch's 'mean',
+ * mmaction2's BCELossWithLogits) or D = 1 (sum_classes = 1, timm's option):
+ *   loss_part[i]  = sum_k l_ik / D
+ *   loss[0]       = the mean of loss_part, clips in ascending order
+ *   dscores[i][k] = (dl/ds)_ik / (clips * D), or dscores == NULL: the same loss_part and loss bits, no gradient
+ * -- the contract of mvf_ce_loss_soft, which mvf_head_train_bwd and mvf_distill_loss build on.
+ * Precision: all per-row arithmetic runs in fp64 from widened fp32 inputs (exp / log1p in double), sums have a fixed order (wavefront shuffle tree, wave
+ * partials in wave order, clips ascending) and every output is rounded to fp32 once.  No atomics, no workspace: bit-identical from run to run.  Any
+ * classes >= 1.  target_threshold travels as float (a launch plan's call record carries no double).
+ * MVF_EINVAL, checked before any launch (nothing is enqueued, no output is touched): a NULL scores / targets / loss_part / loss; clips < 1 or classes < 1;
+ * an infinite target_threshold; sum_classes outside {0, 1}.
+ * A NaN score or a non-finite pos_weight entry makes that clip's loss_part and loss[0] NaN (a NaN score's dscores element too): the non-finite step guard
+ * then skips the step. */
+int mvf_bce_loss(const float* scores, const float* targets, int clips, int classes, const float* pos_weight /* (classes) or NULL */,
+                 float target_threshold /* NaN = off */, int sum_classes, float* dscores /* or NULL */, float* loss_part, float* loss, void* stream);
+/* mvf_head_train_fwd_soft with the loss of mvf_bce_loss in place of the soft-target cross-entropy: the same pool and fc launches (pooled and scores hold
+ * the same bits), then the two loss launches.  The checks of both, before any launch; dscores is required. */
+int mvf_head_train_fwd_bce(const void* feat, int clips, int t, int hw, int c, const float* fc_w, const float* fc_b, int classes,
+                           const float* targets, const float* drop_mask /* (clips*t, c) pre-scaled keep mask or NULL */,
+                           const float* pos_weight /* (classes) or NULL */, float target_threshold /* NaN = off */, int sum_classes,
+                           float* pooled, float* scores, float* dscores, float* loss_part, float* loss, int dtype, void* stream);
 /* Knowledge distillation (Hinton's loss) behind mvf_head_train_fwd / mvf_head_train_fwd_soft, which left the cross-entropy's dscores (clips, classes),
  * loss_part (clips) and loss (1) in device memory; scores = the student's (clips, classes), teacher_scores = the teacher's, all fp32.  Per clip i, with
  * s = scores[i], z = teacher_scores[i], T = temperature, a = alpha, p = softmax(z / T), q = softmax(s / T):
@@ -918,6 +950,40 @@ enum { MVF_METRICS_ROWS = 0, MVF_METRICS_BAD_LABEL = 1, MVF_METRICS_NAN_ROWS = 2
 size_t mvf_metrics_state_words(int classes, int with_confusion);
 int mvf_metrics_update(const float* scores, int rows, int classes, const long long* labels, const int* ks, int nk, long long* state, int with_confusion,
                        int* rank_out, int* pred_out, void* stream);
+/* Multi-label evaluation (csrc/multilabel_metrics.hip): per-class average precision of everything recorded in a pass, without a sort and without a
+ * readback.  Definition -- the step-wise AP of scikit-learn's average_precision_score, what mmaction2 reports as mean_average_precision -- for class c
+ * with positives P_c:
+ *   AP_c = (1 / |P_c|) * sum_{i in P_c} TP_i / N_i,     N_i = #{j : s_jc >= s_ic},     TP_i = #{j in P_c : s_jc >= s_ic}
+ * Summed over a group of tied scores the terms are dTP * TP / N at that threshold, so ties need no special case and nothing depends on the order of the
+ * rows.  +inf and -inf are ordinary values.  mAP = the mean of AP_c over the classes with at least one positive (the caller's division).
+ *
+ * The record, owned by the caller, in device memory:
+ *   rec_scores fp32  (classes, capacity)   class-major: a class's column is contiguous
+ *   rec_labels uint8 (classes, capacity)   0 / 1
+ *   state      int64 (MVF_MULTILABEL_STATE_WORDS), 8-byte aligned, zero at the start of a pass:
+ *     word 0  slots used: the write offset, in device memory, so that appending synchronises nothing        (MVF_MULTILABEL_SLOTS)
+ *     word 1  rows that held a NaN score                                                                     (MVF_MULTILABEL_NAN_ROWS)
+ *     word 2  rows that did not fit (overflow): counted, not stored                                          (MVF_MULTILABEL_OVERFLOW)
+ *     word 3  rows seen                                                                                      (MVF_MULTILABEL_SEEN)
+ *     words 4..7 reserved (zero)
+ *   so the rows that take part are word 3 - word 2 - word 1, and SUM-merging words 1..3 merges ranks.
+ * mvf_multilabel_record: appends scores (rows, classes) fp32 and labels (rows, classes) uint8 (non-zero = positive) at slot word 0 + row.  A row holding a
+ * NaN score is stored as NaN scores without a label: a comparison with a NaN is false and the row is no positive, so it is left out of every class (and
+ * counted in word 1) while slots and rows stay in step.  For the same reason a NaN-filled, label-free slot is padding: records whose unused slots are
+ * filled that way merge by concatenation along `capacity` with word 0 = the total capacity.  Two launches (the store; one thread that advances the words);
+ * rows == 0 is MVF_OK without a launch.
+ * mvf_multilabel_ap: two launches over slots [0, word 0), read on the device.  (1) a workgroup per 256 rows of a class walks the class's column in 256-entry
+ * LDS tiles and writes the integer pair tp[c][i] = TP_i, nn[c][i] = N_i for each positive i, 0 / 0 for the other rows (a workgroup without a positive
+ * returns at once: sum_c |P_c| * n comparisons, to workgroup granularity); (2) one wavefront per class sums TP_i / N_i in fp64 -- lane l takes rows l, l + 64, ..
+ * in ascending order, a shuffle tree adds the lane sums -- into ap[c] (NaN for a class without a positive) and positives[c] = |P_c|.  tp, nn int32 and
+ * (classes, capacity); ap fp64 (classes); positives int64 (classes).  Integer counts in launch 1, no atomics in either: bit-identical from run to run.
+ * Checked before any launch: a NULL or misaligned operand (state, ap, positives 8 bytes; fp32 / int32 arrays 4) is MVF_EINVAL; classes < 1 (ap: > 65535),
+ * rows < 0, capacity outside [1, 2^31 - 1], or a record beyond the grid / 2^63 bytes is MVF_ESHAPE. */
+enum { MVF_MULTILABEL_SLOTS = 0, MVF_MULTILABEL_NAN_ROWS = 1, MVF_MULTILABEL_OVERFLOW = 2, MVF_MULTILABEL_SEEN = 3, MVF_MULTILABEL_STATE_WORDS = 8 };
+int mvf_multilabel_record(const float* scores, const unsigned char* labels, int rows, int classes, float* rec_scores, unsigned char* rec_labels, long capacity,
+                          long long* state, void* stream);
+int mvf_multilabel_ap(const float* rec_scores, const unsigned char* rec_labels, long capacity, int classes, const long long* state, int* tp, int* nn, double* ap,
+                      long long* positives, void* stream);
 /* Per-parameter training statistics and the diagnosis of a skipped step (csrc/layer_stats.hip): where a NaN came from and whether every layer is learning,
  * from figures that stay on the device until the host asks.
  *

@@ -17,6 +17,7 @@ MVF_NCHW, MVF_NHWC = 0, 1
 VIEW_T, VIEW_H, VIEW_W = 1, 2, 4
 MODE_BITS = {"T": 1, "TH": 3, "THW": 7}
 METRICS_ROWS, METRICS_BAD_LABEL, METRICS_NAN_ROWS, METRICS_HITS, METRICS_MAX_K, METRICS_CONFUSION = 0, 1, 2, 8, 8, 16      # state words of mvf_metrics_update
+MULTILABEL_SLOTS, MULTILABEL_NAN_ROWS, MULTILABEL_OVERFLOW, MULTILABEL_SEEN, MULTILABEL_STATE_WORDS = 0, 1, 2, 3, 8      # state words of mvf_multilabel_record
 ERRNAMES = {-1: "MVF_EINVAL", -2: "MVF_ESHAPE", -3: "MVF_EWS", -4: "MVF_EHIP", -5: "MVF_EUNSUPPORTED"}
 
 
@@ -273,6 +274,16 @@ def _load():
     lib.mvf_head_train_fwd_soft.argtypes = [vp, i32, i32, i32, i32, fp, fp, i32, fp, fp, fp, fp, fp, fp, fp, i32, vp]
     lib.mvf_distill_loss.restype = i32
     lib.mvf_distill_loss.argtypes = [fp, fp, i32, i32, f32, f32, fp, fp, fp, fp, vp]
+    lib.mvf_bce_loss.restype = i32
+    lib.mvf_bce_loss.argtypes = [fp, fp, i32, i32, fp, f32, i32, fp, fp, fp, vp]
+    lib.mvf_head_train_fwd_bce.restype = i32
+    lib.mvf_head_train_fwd_bce.argtypes = [vp, i32, i32, i32, i32, fp, fp, i32, fp, fp, fp, f32, i32, fp, fp, fp, fp, fp, i32, vp]
+    lib.mvf_average_clip_sigmoid.restype = i32
+    lib.mvf_average_clip_sigmoid.argtypes = [fp, i32, i32, fp, vp]
+    lib.mvf_multilabel_record.restype = i32
+    lib.mvf_multilabel_record.argtypes = [fp, vp, i32, i32, fp, vp, C.c_long, ll, vp]
+    lib.mvf_multilabel_ap.restype = i32
+    lib.mvf_multilabel_ap.argtypes = [fp, vp, C.c_long, i32, ll, vp, vp, vp, ll, vp]
     lib.mvf_head_train_bwd.restype = i32
     lib.mvf_head_train_bwd.argtypes = [fp, fp, fp, fp, i32, i32, i32, i32, i32, fp, fp, fp, vp, i32, vp]
     lib.mvf_conv2d_wgrad_workspace_bytes.restype = sz

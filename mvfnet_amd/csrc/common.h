@@ -228,6 +228,11 @@ int wgrad_stem_launch(const WgradStemArgs& a, hipStream_t st);
 int stem_direct_launch(const StemDirectArgs& a, hipStream_t st);
 int conv3x3_c64_launch(const Conv3x3C64Args& a, hipStream_t st);
 int pw_sums_launch(const PwSumsArgs& a, hipStream_t st);
+// binary cross-entropy with logits (bce.hip): the argument checks and the two loss launches mvf_bce_loss and mvf_head_train_fwd_bce share
+int bce_check(const char* who, const float* scores, const float* targets, int clips, int classes, float threshold, int sum_classes, const float* loss_part,
+              const float* loss);
+int bce_launch(const float* scores, const float* targets, int clips, int classes, const float* pos_weight, float threshold, int sum_classes, float* dscores,
+               float* loss_part, float* loss, hipStream_t st);
 }
 
 #ifdef __HIPCC__

@@ -151,6 +151,20 @@ __global__ void average_clip_kernel(const float* scores, int clips, int classes,
     for (int k = tid; k < classes; k += blockDim.x) out[k] = out[k] / (float)clips;
 }
 
+// average_clips = 'sigmoid': out[k] = mean over the clips of sigmoid(s[cl][k]).  One thread per class, clips in ascending order, fp64 (exp(-|s|) <= 1 for
+// either sign, so nothing overflows), rounded to fp32 once.
+__global__ void average_clip_sigmoid_kernel(const float* __restrict__ scores, int clips, int classes, float* __restrict__ out) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= classes) return;
+    double acc = 0.0;
+    for (int cl = 0; cl < clips; ++cl) {
+        const double s = (double)scores[(long)cl * classes + k];
+        const double e = exp(-fabs(s));
+        acc += s != s ? s : (s >= 0.0 ? 1.0 / (1.0 + e) : e / (1.0 + e));
+    }
+    out[k] = (float)(acc / (double)clips);
+}
+
 inline int grid_for(long total, int per_block = 256, int cap = 256 * 32) {
     return (int)std::min<long>((total + per_block - 1) / per_block, cap);
 }
@@ -208,6 +222,13 @@ int mvf_average_clip(const float* scores, int clips, int classes, int kind, floa
         return MVF_OK;
     }
     hipLaunchKernelGGL(average_clip_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, scores, clips, classes, kind, out);
+    MVF_LAUNCH_CHECK();
+    return MVF_OK;
+}
+
+int mvf_average_clip_sigmoid(const float* scores, int clips, int classes, float* out, void* stream) {
+    MVF_REQUIRE(scores && out && clips > 0 && classes > 0, MVF_EINVAL, "average_clip_sigmoid: bad argument (clips=%d classes=%d)", clips, classes);
+    hipLaunchKernelGGL(average_clip_sigmoid_kernel, dim3((classes + 255) / 256), dim3(256), 0, (hipStream_t)stream, scores, clips, classes, out);
     MVF_LAUNCH_CHECK();
     return MVF_OK;
 }

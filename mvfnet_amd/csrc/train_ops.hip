@@ -2193,6 +2193,29 @@ int mvf_head_train_fwd_soft(const void* feat, int clips, int t, int hw, int c, c
     return MVF_OK;
 }
 
+// mvf_head_train_fwd_soft with the binary cross-entropy of mvf_bce_loss (bce.hip) in place of the soft-target cross-entropy: the same frame_pool_kernel and
+// head_fc_seg_kernel launches, so pooled and scores hold the same bits.  Every argument is checked before the first launch.
+int mvf_head_train_fwd_bce(const void* feat, int clips, int t, int hw, int c, const float* fc_w, const float* fc_b, int classes,
+                           const float* targets, const float* drop_mask, const float* pos_weight, float target_threshold, int sum_classes,
+                           float* pooled, float* scores, float* dscores, float* loss_part, float* loss, int dtype, void* stream) {
+    MVF_REQUIRE(clips > 0 && t > 0 && hw > 0 && c > 0 && classes > 0, MVF_EINVAL, "head_train_fwd_bce: bad argument (clips=%d t=%d hw=%d c=%d classes=%d)",
+                clips, t, hw, c, classes);
+    MVF_REQUIRE(dtype == MVF_F32 || dtype == MVF_BF16, MVF_EINVAL, "head_train_fwd_bce: dtype %d", dtype);
+    MVF_REQUIRE((size_t)c * sizeof(float) <= 160 * 1024, MVF_EUNSUPPORTED, "head_train_fwd_bce: c=%d does not fit the LDS feature buffer", c);
+    MVF_REQUIRE((long)clips * t <= 65535, MVF_ESHAPE, "head_train_fwd_bce: %d x %d frames exceed the grid", clips, t);
+    MVF_REQUIRE(feat && fc_w && pooled && dscores, MVF_EINVAL, "head_train_fwd_bce: NULL argument");
+    const int rc = mvf_internal::bce_check("head_train_fwd_bce", scores, targets, clips, classes, target_threshold, sum_classes, loss_part, loss);
+    if (rc != MVF_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    dim3 g((c + 255) / 256, clips * t);
+    if (dtype == MVF_F32) hipLaunchKernelGGL(frame_pool_kernel<float>, g, dim3(256), 0, st, (const float*)feat, hw, c, drop_mask, pooled);
+    else hipLaunchKernelGGL(frame_pool_kernel<bf16_t>, g, dim3(256), 0, st, (const bf16_t*)feat, hw, c, drop_mask, pooled);
+    MVF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(head_fc_seg_kernel, dim3(clips, kHeadSplit), dim3(256), (size_t)c * sizeof(float), st, pooled, fc_w, fc_b, clips, t, c, classes, scores);
+    MVF_LAUNCH_CHECK();
+    return mvf_internal::bce_launch(scores, targets, clips, classes, pos_weight, target_threshold, sum_classes, dscores, loss_part, loss, st);
+}
+
 int mvf_ce_loss_soft(const float* scores, const float* targets, int clips, int classes, float* dscores, float* loss_part, float* loss, void* stream) {
     MVF_REQUIRE(clips > 0 && classes > 0, MVF_EINVAL, "ce_loss_soft: bad argument (clips=%d classes=%d)", clips, classes);
     MVF_REQUIRE(scores && targets && loss_part && loss, MVF_EINVAL, "ce_loss_soft: NULL argument");

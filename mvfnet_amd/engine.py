@@ -384,8 +384,13 @@ class HeadEngine(object):
         return pooled, out
 
     def average(self, scores, average_clips):
+        if average_clips == "sigmoid":            # multi-label heads: the mean over the clips of sigmoid(score); an entry point of its own
+            clips, classes = scores.shape
+            out = torch.empty(1, classes, dtype=torch.float32, device=scores.device)
+            check(lib.mvf_average_clip_sigmoid(_p(scores), clips, classes, _p(out), _stream()), "mvf_average_clip_sigmoid")
+            return out
         if average_clips not in self.KINDS:
-            raise ValueError("%s is not supported. Currently supported ones are ['score', 'prob', None]" % (average_clips,))
+            raise ValueError("%s is not supported. Currently supported ones are ['score', 'prob', 'sigmoid', None]" % (average_clips,))
         kind = self.KINDS[average_clips]
         if kind == 0:
             return scores

@@ -78,6 +78,37 @@ def get_weighted_score(score_list, coeff_list):
     return list(np.tensordot(np.array(coeff_list), scores, axes=(0, 0)))
 
 
+def average_precision(scores, labels):
+    """Per-class step-wise average precision of a (videos, classes) score matrix against (videos, classes) multi-hot labels (non-zero = positive):
+    AP_c = (1 / |P_c|) * sum_{i in P_c} TP_i / N_i with N_i = #{j : s_jc >= s_ic} and TP_i = #{j in P_c : s_jc >= s_ic} -- scikit-learn's
+    average_precision_score, what mmaction2 reports; summed over a tie group the terms are dTP * TP / N at that threshold, so ties need no special case.
+    Rows holding a NaN score are left out of every class.  Returns (ap float64 (classes,), NaN where a class has no positive; positives int64 (classes,)).
+    The definition csrc/multilabel_metrics.hip computes on the device (metrics.DeviceMultiLabelMetrics); here one sort per class."""
+    s = np.asarray(scores, dtype=np.float64)
+    y = np.asarray(labels) != 0
+    if s.ndim != 2 or y.shape != s.shape:
+        raise ValueError("average_precision: scores %s and labels %s must be two (videos, classes) matrices" % (s.shape, y.shape))
+    keep = ~np.isnan(s).any(axis=1)
+    s, y = s[keep], y[keep]
+    n, classes = s.shape
+    ap, positives = np.full(classes, np.nan), y.sum(axis=0).astype(np.int64)
+    for c in range(classes):
+        if positives[c] == 0:
+            continue
+        order = np.argsort(s[:, c], kind="stable")
+        sc, yc = s[order, c], y[order, c]
+        first = np.searchsorted(sc, sc[yc], side="left")          # rows [first, n) score >= the positive's
+        below = np.concatenate(([0], np.cumsum(yc)))               # positives among the first k sorted rows
+        ap[c] = np.sum((positives[c] - below[first]) / (n - first)) / positives[c]
+    return ap, positives
+
+
+def mean_average_precision(scores, labels):
+    """The mean of average_precision over the classes with at least one positive (mmaction2's mean_average_precision); nan when no class has one."""
+    ap, positives = average_precision(scores, labels)
+    return float(np.mean(ap[positives > 0])) if (positives > 0).any() else float("nan")
+
+
 WEIGHTS = ("live", "ema", "both")
 
 
@@ -162,6 +193,61 @@ class EvalTopKAccuracyHook(object):
         out["epoch"] = runner.epoch
         self.history.append(out)
         return out
+
+
+class EvalMeanAPHook(EvalTopKAccuracyHook):
+    """EvalTopKAccuracyHook for multi-label data: after every `interval`-th training epoch, score the validation set and log 'mAP' (mean_average_precision;
+    'ema mAP' for the averaged weights).  labels: the (videos, classes) multi-hot matrix.  on_device = True: the pass is runner.device_test into a
+    metrics.DeviceMultiLabelMetrics -- no score row leaves the device, the ranks' records are merged by all_gather() and ONE read ends the pass; it needs one
+    score row per video (test_cfg.average_clips 'sigmoid', 'prob' or 'score')."""
+
+    def __init__(self, loader, labels, interval=1, weights="live", on_device=False):
+        if weights not in WEIGHTS:
+            raise ValueError("weights must be one of %s, got %r" % (", ".join(map(repr, WEIGHTS)), weights))
+        lab = np.asarray(labels)
+        if lab.ndim != 2:
+            raise ValueError("EvalMeanAPHook: labels must be a (videos, classes) multi-hot matrix, got shape %s" % (lab.shape,))
+        self.loader, self.labels, self.interval, self.weights = loader, (lab != 0).astype(np.uint8), interval, weights
+        self.on_device = bool(on_device)
+        self._metrics, self._share = None, None
+        self.history = []
+
+    def _score(self, runner, prefix):
+        if self.on_device:
+            return self._score_on_device(runner, prefix)
+        from .runner import multi_gpu_test
+        was_training = runner.model.training
+        results = multi_gpu_test(runner.model, self.loader, size=len(self.labels))
+        runner.model.train(was_training)
+        if results is None:                          # not rank 0
+            return None
+        rows = np.stack([np.asarray(r).squeeze() for r in results])
+        return {"%smAP" % prefix: mean_average_precision(rows, self.labels[:len(rows)])}
+
+    def _score_on_device(self, runner, prefix):
+        from .dist import get_dist_info
+        from .metrics import DeviceMultiLabelMetrics
+        from .runner import device_test
+        model = runner.model.module if hasattr(runner.model, "module") else runner.model
+        test_cfg = getattr(model, "test_cfg", None)
+        if test_cfg is None or test_cfg.get("average_clips") is None:
+            raise ValueError("evaluation hook with on_device=True: test_cfg.average_clips=None leaves several score rows per video; the device record "
+                             "takes one row per video (average_clips='sigmoid', 'prob' or 'score'), or use the host path (on_device=False)")
+        rank, world = self._share if self._share is not None else get_dist_info()
+        if self._metrics is None:
+            self._metrics = DeviceMultiLabelMetrics(self.labels.shape[1], capacity=max(1, (len(self.labels) + world - 1) // world))
+        if self._metrics.capacity != max(1, (len(self.labels) + world - 1) // world):      # a merged record from the last pass: start from a rank's own size
+            self._metrics = DeviceMultiLabelMetrics(self.labels.shape[1], capacity=max(1, (len(self.labels) + world - 1) // world))
+        self._metrics.reset()
+        was_training = runner.model.training
+        device_test(runner.model, self.loader, self.labels, self._metrics, rank=rank, world=world)
+        runner.model.train(was_training)
+        if world > 1:
+            self._metrics.all_gather()
+        fig = self._metrics.compute()                # every rank holds the figures; rank 0 reports them
+        if get_dist_info()[0] != 0:
+            return None
+        return {"%smAP" % prefix: float(fig["mAP"])}
 
 
 class PreciseBNHook(object):

@@ -20,12 +20,54 @@ import torch.nn as nn
 from ..builder import HEADS
 
 
+LOSS_TYPES = ("CrossEntropyLoss", "BCELossWithLogits")
+BCE_KEYS = ("type", "pos_weight", "target_threshold", "sum_classes")
+
+
+def check_loss_cls(cfg, num_classes):
+    """loss_cls of the head: None / dict(type='CrossEntropyLoss') -> None (softmax cross-entropy, the default), or
+    dict(type='BCELossWithLogits', pos_weight=None | sequence of num_classes numbers, target_threshold=None | finite float, sum_classes=False) -> a dict
+    with the three settings (pos_weight a tuple of floats or None).  Any other type raises NotImplementedError; an unknown key or a bad value ValueError."""
+    if cfg is None:
+        return None
+    if not hasattr(cfg, "keys") or "type" not in cfg.keys():
+        raise ValueError("TSNClsHead: loss_cls must be None or a dict with a 'type', got %r" % (cfg,))
+    kind = cfg["type"]
+    if kind not in LOSS_TYPES:
+        raise NotImplementedError("TSNClsHead: loss_cls type %r is not built (built: %s)" % (kind, ", ".join(LOSS_TYPES)))
+    if kind == "CrossEntropyLoss":
+        extra = sorted(k for k in cfg.keys() if k != "type")
+        if extra:
+            raise ValueError("TSNClsHead: loss_cls CrossEntropyLoss takes no options here, got %s" % ", ".join(map(repr, extra)))
+        return None
+    unknown = sorted(k for k in cfg.keys() if k not in BCE_KEYS)
+    if unknown:
+        raise ValueError("TSNClsHead: loss_cls BCELossWithLogits: unknown key %s (known: %s)" % (", ".join(map(repr, unknown)), ", ".join(BCE_KEYS)))
+    pw, thr, sc = cfg.get("pos_weight"), cfg.get("target_threshold"), cfg.get("sum_classes", False)
+    if pw is not None:
+        try:
+            pw = tuple(float(v) for v in pw)
+        except (TypeError, ValueError):
+            raise ValueError("TSNClsHead: loss_cls pos_weight must be None or a sequence of %d numbers, got %r" % (num_classes, cfg.get("pos_weight")))
+        if len(pw) != num_classes:
+            raise ValueError("TSNClsHead: loss_cls pos_weight holds %d entries for num_classes=%d" % (len(pw), num_classes))
+    if thr is not None:
+        if isinstance(thr, bool) or not isinstance(thr, numbers.Real) or thr != thr or thr in (float("inf"), float("-inf")):
+            raise ValueError("TSNClsHead: loss_cls target_threshold must be None or a finite number, got %r" % (thr,))
+        thr = float(thr)
+    if not isinstance(sc, bool):
+        raise ValueError("TSNClsHead: loss_cls sum_classes must be a bool, got %r" % (sc,))
+    return dict(pos_weight=pw, target_threshold=thr, sum_classes=sc)
+
+
 @HEADS.register_module
 class TSNClsHead(nn.Module):
     def __init__(self, spatial_type="avg", spatial_size=7, consensus_cfg=dict(type="avg", dim=1), with_avg_pool=False,
                  temporal_feature_size=1, spatial_feature_size=1, dropout_ratio=0.8, in_channels=1024, num_classes=101,
-                 init_std=0.001, fcn_testing=False, extract_feat=False, label_smooth_eps=0.0):
+                 init_std=0.001, fcn_testing=False, extract_feat=False, label_smooth_eps=0.0, loss_cls=None):
         super().__init__()
+        self.loss_cls = check_loss_cls(loss_cls, num_classes)
+        self._pos_weight_dev = None
         if isinstance(label_smooth_eps, bool) or not isinstance(label_smooth_eps, numbers.Real) or not 0.0 <= label_smooth_eps < 1.0:
             raise ValueError("TSNClsHead: label_smooth_eps must lie in [0, 1) (got %r)" % (label_smooth_eps,))
         self.label_smooth_eps = float(label_smooth_eps)
@@ -50,7 +92,21 @@ class TSNClsHead(nn.Module):
 
     def _apply(self, fn, *a, **k):
         self._engine = None
+        self._pos_weight_dev = None
         return super()._apply(fn, *a, **k)
+
+    def bce_settings(self, device):
+        """None for the default loss; else (pos_weight, target_threshold, sum_classes) as mvf_bce_loss takes them: a persistent fp32 device tensor (uploaded
+        once per device) or None, a float with NaN = off, 0 / 1."""
+        if self.loss_cls is None:
+            return None
+        pw = None
+        if self.loss_cls["pos_weight"] is not None:
+            pw, dev = self._pos_weight_dev, torch.device(device)
+            if pw is None or pw.device.type != dev.type or (dev.index is not None and pw.device.index != dev.index):
+                pw = self._pos_weight_dev = torch.tensor(self.loss_cls["pos_weight"], dtype=torch.float32, device=device)
+        thr = self.loss_cls["target_threshold"]
+        return pw, float("nan") if thr is None else thr, int(self.loss_cls["sum_classes"])
 
     def load_state_dict(self, *a, **k):
         self._engine = None
@@ -90,17 +146,38 @@ class TSNClsHead(nn.Module):
         HIP cross-entropy kernel of the train head (mvf_ce_loss); no autograd through it -- Recognizer2D.forward_train is the
         path that trains (scores, loss and their gradients in one fused head).
         labels: integers (B,) / (B, 1), or a floating-point (B, num_classes) matrix of soft labels (mvf_ce_loss_soft).  In training mode integer labels are
-        smoothed with label_smooth_eps (mvf_soft_targets) as mmaction's head does."""
+        smoothed with label_smooth_eps (mvf_soft_targets) as mmaction's head does.
+        With loss_cls = BCELossWithLogits the loss is mvf_bce_loss against a target matrix: a bool / uint8 / floating-point (B, num_classes) matrix as it
+        is (multi-hot labels), integer labels through mvf_soft_targets."""
         import ctypes as C
         from .._lib import check, lib
         if not cls_score.is_cuda:
             raise RuntimeError("TSNClsHead.loss: mvfnet_amd runs on MI355X tensors only; no CPU fallback (tests use oracle/)")
         s = cls_score.detach().to(torch.float32).contiguous()
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        bce = self.bce_settings(s.device)
+        if bce is not None and labels.dtype in (torch.bool, torch.uint8) and labels.dim() == 2 and tuple(labels.shape) == tuple(s.shape):
+            labels = labels.to(torch.float32)                # multi-hot labels
         soft = labels.is_floating_point() and labels.dim() == 2 and tuple(labels.shape) == tuple(s.shape)
         eps = self.label_smooth_eps if self.training else 0.0
         if soft and eps > 0.0:
             raise ValueError("TSNClsHead.loss: soft (B, num_classes) labels are taken as they are; label_smooth_eps needs integer labels")
+        if bce is not None:
+            # loss_cls = BCELossWithLogits: always against a target matrix -- the caller's (multi-hot or soft), or mvf_soft_targets' one-hot / smoothed one
+            P = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+            if soft:
+                tgt = labels.detach().to(device=s.device, dtype=torch.float32).contiguous()
+            else:
+                lab = labels.reshape(-1).to(device=s.device, dtype=torch.int64).contiguous()
+                if lab.numel() != s.shape[0]:
+                    raise ValueError("TSNClsHead.loss: %d labels for %d score rows" % (lab.numel(), s.shape[0]))
+                tgt = torch.empty_like(s)
+                check(lib.mvf_soft_targets(P(lab), None, None, s.shape[0], s.shape[1], C.c_float(eps), P(tgt), stream), "mvf_soft_targets")
+            part = torch.empty(s.shape[0], dtype=torch.float32, device=s.device)
+            out = torch.empty(1, dtype=torch.float32, device=s.device)
+            pw, thr, sum_classes = bce
+            check(lib.mvf_bce_loss(P(s), P(tgt), s.shape[0], s.shape[1], P(pw), C.c_float(thr), sum_classes, None, P(part), P(out), stream), "mvf_bce_loss")
+            return dict(loss_cls=out.reshape(()))
         if soft or eps > 0.0:
             P = lambda t: C.c_void_p(t.data_ptr())
             if soft:

@@ -147,7 +147,8 @@ class Plan(object):
         sig = []
         for (kind, fn, name, ints, flts, fl), o in zip(rec.ops, self.ops):
             if kind == CALL:
-                sig.append((name, fn, tuple(None if (o.word0 + j) in dyn else w for j, w in enumerate(ints)), tuple(flts)))
+                # (a NaN float argument -- mvf_head_train_fwd_bce's "threshold off" -- is named: NaN != NaN would make every recording a new one)
+                sig.append((name, fn, tuple(None if (o.word0 + j) in dyn else w for j, w in enumerate(ints)), tuple(v if v == v else "nan" for v in flts)))
             else:
                 sig.append((name, ints[1] if kind == RECORD else ints[0]))          # the stream; the events are each recording's own
         self.signature = (tuple(sig), tuple(self.cuts))

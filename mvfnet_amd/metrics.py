@@ -151,3 +151,119 @@ class DeviceMetrics(object):
         if not self.record:
             raise RuntimeError("DeviceMetrics.records: built with record=0")
         return self._rank[:self.recorded], self._pred[:self.recorded]
+
+
+def figures_from_ap(ap, positives, state, strict=True):
+    """The dict DeviceMultiLabelMetrics.compute() returns, from host copies of the kernel's outputs and the record's state words."""
+    ap, positives = np.asarray(ap, dtype=np.float64).reshape(-1), np.asarray(positives, dtype=np.int64).reshape(-1)
+    state = np.asarray(state, dtype=np.int64).reshape(-1)
+    nan_rows, overflow, seen = (int(state[i]) for i in (_lib.MULTILABEL_NAN_ROWS, _lib.MULTILABEL_OVERFLOW, _lib.MULTILABEL_SEEN))
+    if strict and overflow:
+        raise RuntimeError("device multi-label metrics: %d of %d rows did not fit the record; build it with a larger capacity" % (overflow, seen))
+    have = positives > 0
+    return dict(mAP=float(np.mean(ap[have])) if have.any() else float("nan"), ap=ap, positives=positives, classes_with_positives=int(have.sum()),
+                rows=seen - overflow - nan_rows, nan_rows=nan_rows, overflow=overflow)
+
+
+class DeviceMultiLabelMetrics(object):
+    """Mean average precision of everything passed to update() since the last reset(), for multi-label data (several actions per video: Charades,
+    Multi-Moments in Time, HVU), recorded and computed on the device (csrc/multilabel_metrics.hip).
+
+        m = DeviceMultiLabelMetrics(157, capacity=1863)
+        for scores, labels in ...:          # (rows, 157) fp32 and (rows, 157) uint8 / bool multi-hot, both on the device
+            m.update(scores, labels)        # two launches on the current stream, no readback: the write offset lives in device memory
+        m.all_gather()                      # under a process group: every rank then holds every rank's rows
+        m.compute()                         # the one synchronising call: dict(mAP, ap, positives, classes_with_positives, rows, nan_rows, overflow)
+
+    AP is the step-wise average precision of scikit-learn's average_precision_score (evaluation.mean_average_precision is the same definition in numpy);
+    mAP is its mean over the classes with at least one positive.  `capacity` = the rows the record can hold (per rank): rows beyond it are counted and
+    compute() raises.  A row holding a NaN score is left out of every class and counted in nan_rows (it still takes a slot).  Unused slots hold NaN scores
+    and no label, which a comparison never counts: that is what lets all_gather() merge the ranks' records by plain concatenation."""
+
+    def __init__(self, num_classes, capacity, device=None):
+        for name, v in (("num_classes", num_classes), ("capacity", capacity)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+                raise ValueError("%s must be an integer >= 1, got %r" % (name, v))
+        if num_classes > 65535 or capacity > 2 ** 31 - 1:
+            raise ValueError("num_classes=%d / capacity=%d: at most 65535 classes and 2^31 - 1 rows" % (num_classes, capacity))
+        self.num_classes, self.capacity = int(num_classes), int(capacity)
+        self.device = torch.device(device if device is not None else "cuda")
+        self.rec_scores = torch.full((self.num_classes, self.capacity), float("nan"), dtype=torch.float32, device=self.device)
+        self.rec_labels = torch.zeros((self.num_classes, self.capacity), dtype=torch.uint8, device=self.device)
+        self.state = torch.zeros(_lib.MULTILABEL_STATE_WORDS, dtype=torch.int64, device=self.device)
+        self._pairs = None                    # (tp, nn) of the last compute(): int32 (num_classes, capacity) device arrays
+
+    def update(self, scores, labels):
+        """scores (rows, num_classes) fp32 contiguous, labels (rows, num_classes) uint8 or bool (non-zero = positive) contiguous, both on this object's
+        device.  Asynchronous on the current stream."""
+        if not (torch.is_tensor(scores) and torch.is_tensor(labels) and scores.is_cuda and labels.is_cuda):
+            raise RuntimeError("DeviceMultiLabelMetrics.update: device tensors required (the host path is evaluation.mean_average_precision); no CPU fallback")
+        if scores.device != self.state.device or labels.device != self.state.device:
+            raise RuntimeError("DeviceMultiLabelMetrics.update: scores on %s, labels on %s, record on %s" % (scores.device, labels.device, self.state.device))
+        if scores.dtype != torch.float32 or scores.dim() != 2 or scores.shape[1] != self.num_classes or not scores.is_contiguous():
+            raise ValueError("DeviceMultiLabelMetrics.update: scores must be a contiguous float32 (rows, %d) tensor, got %s %s"
+                             % (self.num_classes, scores.dtype, tuple(scores.shape)))
+        if labels.dtype not in (torch.uint8, torch.bool) or tuple(labels.shape) != tuple(scores.shape) or not labels.is_contiguous():
+            raise ValueError("DeviceMultiLabelMetrics.update: labels must be a contiguous uint8 / bool %s tensor, got %s %s"
+                             % (tuple(scores.shape), labels.dtype, tuple(labels.shape)))
+        _lib.check(_lib.lib.mvf_multilabel_record(scores.data_ptr(), labels.data_ptr(), scores.shape[0], self.num_classes, self.rec_scores.data_ptr(),
+                                                  self.rec_labels.data_ptr(), self.capacity, self.state.data_ptr(),
+                                                  torch.cuda.current_stream(self.state.device).cuda_stream), "multilabel_record")
+
+    def reset(self):
+        self.rec_scores.fill_(float("nan"))
+        self.rec_labels.zero_()
+        self.state.zero_()
+        self._pairs = None
+
+    def merge(self, records):
+        """Replace this object's record by the concatenation of `records`, a list of (rec_scores, rec_labels, state) triples of equal class count on this
+        device (what all_gather() collects; unused slots must hold NaN scores and no label, as reset() leaves them).  AP does not depend on the order of
+        the rows, so nothing is re-interleaved.  No readback."""
+        self.rec_scores = torch.cat([r[0] for r in records], dim=1).contiguous()
+        self.rec_labels = torch.cat([r[1] for r in records], dim=1).contiguous()
+        self.capacity = int(self.rec_scores.shape[1])
+        state = torch.stack([r[2] for r in records]).sum(dim=0)
+        state[_lib.MULTILABEL_SLOTS] = self.capacity          # every slot may hold a row: the padding is NaN
+        self.state = state
+        self._pairs = None
+
+    def all_gather(self):
+        """Under the default process group every rank ends up with every rank's rows (records padded to the longest capacity); nothing without one."""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+            return
+        world = dist.get_world_size()
+        cap = torch.tensor([self.capacity], dtype=torch.int64, device=self.device)
+        caps = [torch.zeros_like(cap) for _ in range(world)]
+        dist.all_gather(caps, cap)
+        longest = int(torch.stack(caps).max())                 # (a host read of one word per rank: capacities are host figures, not the pass's results)
+        sc, lb = self.rec_scores, self.rec_labels
+        if longest > self.capacity:
+            sc = torch.cat([sc, torch.full((self.num_classes, longest - self.capacity), float("nan"), dtype=torch.float32, device=self.device)], dim=1).contiguous()
+            lb = torch.cat([lb, torch.zeros((self.num_classes, longest - self.capacity), dtype=torch.uint8, device=self.device)], dim=1).contiguous()
+        scs, lbs, sts = ([torch.empty_like(t) for _ in range(world)] for t in (sc, lb, self.state))
+        dist.all_gather(scs, sc)
+        dist.all_gather(lbs, lb)
+        dist.all_gather(sts, self.state)
+        self.merge(list(zip(scs, lbs, sts)))
+
+    def compute(self, strict=True):
+        """The one synchronising call: dict(mAP, ap (num_classes,) float64 with NaN where a class has no positive, positives (num_classes,) int64,
+        classes_with_positives, rows, nan_rows, overflow).  strict=True raises RuntimeError when rows did not fit the record."""
+        tp = torch.empty((self.num_classes, self.capacity), dtype=torch.int32, device=self.device)
+        nn = torch.empty((self.num_classes, self.capacity), dtype=torch.int32, device=self.device)
+        ap = torch.empty(self.num_classes, dtype=torch.float64, device=self.device)
+        positives = torch.empty(self.num_classes, dtype=torch.int64, device=self.device)
+        _lib.check(_lib.lib.mvf_multilabel_ap(self.rec_scores.data_ptr(), self.rec_labels.data_ptr(), self.capacity, self.num_classes, self.state.data_ptr(),
+                                              tp.data_ptr(), nn.data_ptr(), ap.data_ptr(), positives.data_ptr(),
+                                              torch.cuda.current_stream(self.state.device).cuda_stream), "multilabel_ap")
+        self._pairs = (tp, nn)
+        return figures_from_ap(ap.cpu().numpy(), positives.cpu().numpy(), self.state.cpu().numpy(), strict)
+
+    def pairs(self):
+        """(tp, nn, slots): the int32 (num_classes, capacity) device arrays of TP_i and N_i the last compute() made (0 / 0 for a row that is no positive of
+        the class) and the number of slots they cover."""
+        if self._pairs is None:
+            raise RuntimeError("DeviceMultiLabelMetrics.pairs: compute() has not run since the last update of the record")
+        return self._pairs[0], self._pairs[1], int(self.state[_lib.MULTILABEL_SLOTS])

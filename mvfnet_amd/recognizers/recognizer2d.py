@@ -161,10 +161,16 @@ class Recognizer2D(nn.Module):
         eng.randaug = self.randaug if training else None
         eng.distill = self.distill if training else None       # train_cfg['distill'] (distill.py): the same rule
         eng.label_smooth_eps = float(getattr(self.cls_head, "label_smooth_eps", 0.0)) if training else 0.0
+        # the head's loss (loss_cls) is no augmentation: it holds in either mode.  None = softmax cross-entropy.
+        if getattr(self.cls_head, "loss_cls", None) is not None:
+            eng.bce = self.cls_head.bce_settings(eng.device)
+        else:
+            eng.bce = None
 
     def forward_train(self, imgs, labels, **kwargs):
         """imgs [B, T, 3, H, W], labels [B, 1] -> {'loss_cls': scalar tensor} (reference recognizer2d.py:132-149).
-        labels may also be a floating-point (B, num_classes) matrix of soft labels.  While self.training, train_cfg['erasing'] (RandomErasing),
+        labels may also be a floating-point (B, num_classes) matrix of soft labels -- or, with the head's loss_cls = BCELossWithLogits, a bool / uint8
+        (B, num_classes) matrix of multi-hot labels.  While self.training, train_cfg['erasing'] (RandomErasing),
         train_cfg['blending'] (Mixup / CutMix) and the head's label_smooth_eps are applied on the device (mvfnet_amd/erasing.py, mvfnet_amd/blending.py).
         The returned loss supports .backward(): gradients land in the parameters' .grad (copies of the engine's flat gradient
         buffer; after engine.attach_grads() the .grad tensors ARE views of it), as the reference's DistOptimizerHook expects.
@@ -191,6 +197,10 @@ class Recognizer2D(nn.Module):
         eng.trainable_offset()
         eng.input_pipeline, eng.input_window = getattr(self, "input_pipeline", None), kwargs.get("window")
         self._set_soft_options(eng, self.training)
+        if eng.bce is not None and torch.is_tensor(labels) and labels.dtype in (torch.bool, torch.uint8) and labels.dim() == 2 \
+                and tuple(labels.shape) == (imgs.shape[0], self.cls_head.num_classes):
+            # multi-hot labels: the fp32 target matrix is made HERE, in front of the engine's recorded region (a torch op inside it is dropped on replay)
+            labels = labels.to(device=imgs.device, dtype=torch.float32)
         eng.dropout = self.cls_head.dropout_ratio if (self.cls_head.dropout is not None and self.cls_head.training) else 0.0
         params = [p for p in self.parameters()]
         loss = _TrainStepFn.apply(eng, imgs, labels, *params)

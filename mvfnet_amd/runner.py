@@ -769,10 +769,23 @@ def device_test(model, loader, labels, metrics, rank=None, world=None):
     `metrics.update(score, labels[i : i + rows])` with i the item's index in the full label list -- `rank + n * world` for the n-th item of a rank that scores
     the `rank::world` share, the order collect_results assumes.  `labels` (one integer per video; a list, an array, or an int64 device tensor) are uploaded once.  Nothing inside the loop waits for the
     device; the caller ends the pass with metrics.all_reduce() / metrics.compute().  A failing launch raises from the forward as it always did.
+    With a metrics.DeviceMultiLabelMetrics, `labels` is the (videos, classes) multi-hot matrix and the rows are recorded for its mean average precision
+    (the caller ends the pass with metrics.all_gather() / metrics.compute()).
     rank / world default to the process group's.  Returns `metrics`."""
     if rank is None or world is None:
         rank, world = get_dist_info()
-    if torch.is_tensor(labels) and labels.is_cuda:       # already uploaded (int64, one per video)
+    from .metrics import DeviceMultiLabelMetrics
+    if isinstance(metrics, DeviceMultiLabelMetrics):
+        # multi-label videos: `labels` is the (videos, classes) multi-hot matrix (bool / uint8 / any numbers, non-zero = positive), uploaded once as uint8
+        if torch.is_tensor(labels) and labels.is_cuda and labels.dtype in (torch.uint8, torch.bool):
+            lab_dev = labels
+        else:
+            lab = np.asarray(labels.cpu() if torch.is_tensor(labels) else labels)
+            lab_dev = torch.from_numpy(np.ascontiguousarray((lab != 0).astype(np.uint8))).to(metrics.state.device)
+        if lab_dev.dim() != 2 or lab_dev.shape[1] != metrics.num_classes:
+            raise ValueError("device_test: a DeviceMultiLabelMetrics takes a (videos, %d) label matrix, got %s" % (metrics.num_classes, tuple(lab_dev.shape)))
+        lab_dev = lab_dev.contiguous()
+    elif torch.is_tensor(labels) and labels.is_cuda:       # already uploaded (int64, one per video)
         lab_dev = labels.reshape(-1)
     else:
         try:

@@ -1875,6 +1875,12 @@ class TrainEngine(_ParamStore):
         # it run eagerly (_plan_key); with None the step allocates and launches exactly what it did without it.
         self.distill = None
         self._distill_terms = None
+        # Binary cross-entropy head (TSNClsHead(loss_cls=dict(type='BCELossWithLogits', ...)).bce_settings: (pos_weight device tensor | None, target_threshold
+        # with NaN = off, sum_classes 0 / 1); None = the softmax cross-entropy).  With it the head ALWAYS takes the target-matrix path: integer labels go
+        # through mvf_soft_targets (one-hot, smoothed, Mixup / CutMix: timm's BCE recipe), a floating-point (B, classes) matrix is taken as it is (multi-hot
+        # labels), and mvf_head_train_fwd_bce stands where mvf_head_train_fwd_soft stood.  Part of the plan key, appended only when set: with None the key,
+        # the allocations and the launches are what they were.
+        self.bce = None
 
     def _pack_all(self, kind):
         """All forward (kind 0) or data-gradient (kind 1) weight packs in ONE launch (mvf_pack_conv_weights_batched); the job
@@ -2080,10 +2086,13 @@ class TrainEngine(_ParamStore):
 
     def _soft_labels(self, imgs, labels):
         """The caller hands the (B, num_classes) soft-label matrix itself (floating point) instead of integer labels."""
-        return labels.is_floating_point() and labels.dim() == 2 and tuple(labels.shape) == (imgs.shape[0], self.num_classes)
+        matrix = labels.dim() == 2 and tuple(labels.shape) == (imgs.shape[0], self.num_classes)
+        if self.bce is not None and matrix and labels.dtype in (torch.bool, torch.uint8):
+            return True                  # multi-hot labels under the BCE head: _step_tensors widens them to fp32, outside any recorded region
+        return labels.is_floating_point() and matrix
 
     def _uses_soft_head(self, lab):
-        return self.blending is not None or self.label_smooth_eps > 0.0 or lab.is_floating_point()
+        return self.blending is not None or self.label_smooth_eps > 0.0 or lab.is_floating_point() or self.bce is not None
 
     def set_options(self, lr=None, momentum=None, weight_decay=None, max_norm=None, dtype=None, optimizer=None, betas=None, eps=None):
         """Update the optimizer hyper-parameters of an existing engine (Recognizer2D.train_engine(**opt) on a model that already
@@ -2173,8 +2182,14 @@ class TrainEngine(_ParamStore):
                 targets = self.buf("soft_targets", (b, self.num_classes), f32)
                 check(lib.mvf_soft_targets(_p(lab), _p(rows_d), _p(wts_d), b, self.num_classes, C.c_float(self.label_smooth_eps), _p(targets), _st()),
                       "soft_targets")
-            check(lib.mvf_head_train_fwd_soft(_p(xcur), b, t, hc * wc, cc, _p(self.fc_w), _p(self.fc_b), self.num_classes, _p(targets), _p(mask), _p(pooled),
-                                              _p(scores), _p(dscores), _p(loss_part), _p(loss), self.dt, _st()), "head fwd (soft targets)")
+            if self.bce is not None:
+                pos_weight, thr, sum_classes = self.bce
+                check(lib.mvf_head_train_fwd_bce(_p(xcur), b, t, hc * wc, cc, _p(self.fc_w), _p(self.fc_b), self.num_classes, _p(targets), _p(mask),
+                                                 _p(pos_weight), C.c_float(thr), sum_classes, _p(pooled), _p(scores), _p(dscores), _p(loss_part), _p(loss),
+                                                 self.dt, _st()), "head fwd (bce)")
+            else:
+                check(lib.mvf_head_train_fwd_soft(_p(xcur), b, t, hc * wc, cc, _p(self.fc_w), _p(self.fc_b), self.num_classes, _p(targets), _p(mask), _p(pooled),
+                                                  _p(scores), _p(dscores), _p(loss_part), _p(loss), self.dt, _st()), "head fwd (soft targets)")
         else:
             check(lib.mvf_head_train_fwd(_p(xcur), b, t, hc * wc, cc, _p(self.fc_w), _p(self.fc_b), self.num_classes, _p(lab), _p(mask), _p(pooled),
                                          _p(scores), _p(dscores), _p(loss_part), _p(loss), self.dt, _st()), "head fwd")
@@ -2351,7 +2366,9 @@ class TrainEngine(_ParamStore):
                 # a plan recorded without blending / smoothing / soft labels is never replayed with them (other launches, and eps is a frozen float word)
                 self.blending is not None, float(self.label_smooth_eps), self._soft_labels(imgs, labels)) + (
                     # erasing off: the key of every existing configuration is what it was.  The table's width is a frozen integer word of the recorded call.
-                    (("erasing", int(self.erasing.max_boxes)),) if self.erasing is not None else ())
+                    (("erasing", int(self.erasing.max_boxes)),) if self.erasing is not None else ()) + (
+                    # the loss kind and its three settings (the threshold and sum_classes are frozen words of the recorded call, pos_weight a frozen address)
+                    (("bce", self.bce[0].data_ptr() if self.bce[0] is not None else 0, repr(float(self.bce[1])), int(self.bce[2])),) if self.bce is not None else ())
 
     def _record_step(self, imgs, labels, prepared):
         """One eager step with every library call and stream ordering recorded; returns (loss, Plan | None)."""
