@@ -922,6 +922,46 @@ size_t mvf_adamw_workspace_bytes(long n);
 int mvf_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long n, float grad_scale, float max_norm,
                    const mvf_adamw_hyper_t* hyper, const mvf_sgd_segment_t* segments, int nseg, float* ema, float ema_momentum, int* guard,
                    long long* applied_steps, float* norm_out, void* ws, size_t ws_bytes, void* stream);
+/* clip_grad_norm_(max_norm) on grad_scale * grads, then LAMB with the arithmetic of timm's Lamb (optim/lamb.py: bias correction on, grad_averaging on), on
+ * flat fp32 device buffers that need only 4-byte alignment -- beside mvf_adamw_step, with its conventions: caller-owned workspace
+ * (mvf_lamb_workspace_bytes(n, nseg), 8-byte aligned), every check before any launch, no atomics, grids that depend on n and nseg alone, bit-identical from
+ * run to run.  The clip in front is this library's, coef = min(1, max_norm / (norm + 1e-6)) (clip_grad_norm_; max_norm <= 0 = off); timm's own max_grad_norm
+ * divides by max(1, norm / max_grad_norm) and so differs by that 1e-6 alone.
+ * segments is REQUIRED, and ONE SEGMENT IS ONE TRUST-RATIO UNIT: the caller passes one entry per parameter tensor (segment k covers elements
+ * [first_k, first_{k+1}), sorted, first_0 = 0; lr * lr_mult, weight_decay * decay_mult; lr_mult < 0 = excluded: the gradient stays outside the norm, params,
+ * exp_avg, exp_avg_sq and ema keep their bits).
+ * Per trained element, in fp32, with coef = norm_out[1], wd_i = weight_decay * decay_mult and t the applied-step count AFTER this step:
+ *     d  = g * grad_scale * coef
+ *     m' = b1 * m + (1 - b1) * d
+ *     v' = b2 * v + (1 - b2) * d^2
+ *     u  = (m' / (1 - b1^t)) / (sqrt(v') / sqrt(1 - b2^t) + eps) + wd_i * p
+ * Per segment k, the two sums in fp64 (the square of an fp32 value is exact there), each rounded once:
+ *     wn = sqrt(sum p^2)   (p before the update)          un = sqrt(sum u^2)
+ *     adapts_k = (wd_k != 0) or always_adapt
+ *     r_k = adapts_k and wn > 0 and un > 0 ? (float)(wn / un) : 1 ;     trust_clip: r_k = min(r_k, 1)
+ *     p'  = p - (float)(lr_k * (double)r_k) * u
+ * hyper is HOST memory, read during the call; 1 - beta1, 1 - beta2, 1 / (1 - b1^t), sqrt(1 - b2^t), wd_i and lr_k * r_k are formed in double and rounded to
+ * fp32 once.  u is formed twice -- for un, and again when p' is stored -- by one function whose roundings are pinned, so no n-sized scratch is needed.
+ * ratio_out: nseg floats in DEVICE memory, 4-byte aligned: the ratio applied to each segment, 1 where the segment does not adapt, 0 where it is excluded.
+ * applied_steps, ema, guard, norm_out: as in mvf_adamw_step (ema[i] = ema_step(ema[i], p', ema_momentum), bit-identical to the plain step followed by
+ * mvf_ema_update; the lane that finishes the norm keeps the guard counters and the applied-step count).  With guard != NULL and a non-finite scaled norm every
+ * workgroup of the three LAMB launches returns before any store: params, exp_avg, exp_avg_sq, ema, ratio_out and *applied_steps keep their bits.  With the flag
+ * clear the results are bit-identical to guard == NULL.
+ * The table's CONTENT (ascending first, first_0 == 0) is the caller's contract, validated once where the table is built, as for mvf_flat_segment_stats: a table
+ * that breaks it gives meaningless figures but no access outside the operands.
+ * MVF_EINVAL, nothing launched: a NULL params / grads / exp_avg / exp_avg_sq / norm_out / ratio_out / hyper / applied_steps / segments, n <= 0, nseg outside
+ * [1, n], a misaligned operand (applied_steps, ws and segments 8 bytes, the others 4), any two operands that overlap (the four arrays, ema, guard,
+ * applied_steps, norm_out, ratio_out, ws, the segment table), a beta outside [0, 1), eps <= 0, a negative lr or weight_decay, a NaN anywhere in the struct,
+ * trust_clip or always_adapt other than 0 / 1, an ema_momentum outside [0, 1] (or NaN) when ema is given.  MVF_EWS: a NULL or short workspace.
+ * mvf_lamb_workspace_bytes is 0 for n <= 0 or nseg outside [1, n]. */
+typedef struct mvf_lamb_hyper {
+    double lr, beta1, beta2, eps, weight_decay;
+    int trust_clip, always_adapt;
+} mvf_lamb_hyper_t;
+size_t mvf_lamb_workspace_bytes(long n, int nseg);
+int mvf_lamb_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long n, float grad_scale, float max_norm,
+                  const mvf_lamb_hyper_t* hyper, const mvf_sgd_segment_t* segments, int nseg, float* ema, float ema_momentum, int* guard,
+                  long long* applied_steps, float* norm_out, float* ratio_out, void* ws, size_t ws_bytes, void* stream);
 /* Device-side accuracy: top-k hits and confusion counts of a (rows, classes) fp32 score matrix against integer labels, summed into a state array that stays
  * on the device (evaluation without one readback per video, training accuracy in the log without a readback per step).
  *

@@ -95,6 +95,12 @@ class AdamwHyper(C.Structure):
     _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double), ("decoupled", C.c_int32)]
 
 
+class LambHyper(C.Structure):
+    """mvf_lamb_hyper_t: the hyper-parameters of mvf_lamb_step, doubles in HOST memory (the library rounds 1 - beta and lr_k * r_k to fp32 once)."""
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double), ("trust_clip", C.c_int32),
+                ("always_adapt", C.c_int32)]
+
+
 class StatSegment(C.Structure):
     """mvf_stat_segment_t: one BatchNorm statistic buffer in the flat shadow layout of the precise-BN entry points (csrc/precise_bn.hip)."""
     _fields_ = [("ptr", C.c_void_p), ("first", C.c_long)]
@@ -338,6 +344,10 @@ def _load():
     lib.mvf_adamw_workspace_bytes.argtypes = [i64]
     lib.mvf_adamw_step.restype = i32
     lib.mvf_adamw_step.argtypes = [fp, fp, fp, fp, i64, f32, f32, C.POINTER(AdamwHyper), vp, i32, fp, f32, vp, vp, fp, vp, sz, vp]
+    lib.mvf_lamb_workspace_bytes.restype = sz
+    lib.mvf_lamb_workspace_bytes.argtypes = [i64, i32]
+    lib.mvf_lamb_step.restype = i32
+    lib.mvf_lamb_step.argtypes = [fp, fp, fp, fp, i64, f32, f32, C.POINTER(LambHyper), vp, i32, fp, f32, vp, vp, fp, fp, vp, sz, vp]
     lib.mvf_metrics_state_words.restype = sz
     lib.mvf_metrics_state_words.argtypes = [i32, i32]
     lib.mvf_metrics_update.restype = i32

@@ -201,3 +201,33 @@ def adamw_moments(opt_state, n_params):
     if len(steps) > 1:
         raise ValueError("optimizer state: the parameters' step counts differ (%s); the fused optimizer keeps one" % sorted(steps))
     return (steps.pop() if steps else 0), ms, vs, dict(groups[0])
+
+
+# ---- optimizer state: the fused LAMB step (train_engine._apply_lamb).  THE PROJECT'S OWN FORMAT: Adam's wire layout with the groups marked lamb=True ---------
+def lamb_state_dict(step, exp_avgs, exp_avg_sqs, lr, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, trust_clip=False, always_adapt=False, multipliers=None,
+                    initial_lr=None):
+    """adamw_state_dict's layout -- {'state': {i: {'step', 'exp_avg', 'exp_avg_sq'}}, 'param_groups': [...]}, `step` the number of APPLIED steps as a float32
+    scalar per stepped parameter, one group or one per parameter under `multipliers` -- with groups that carry lamb=True, trust_clip, always_adapt,
+    bias_correction=True and grad_averaging=True (the two timm options the fused step fixes) in place of Adam's amsgrad / decoupled_weight_decay keys.  The state
+    entries are the ones timm's Lamb keeps, but timm's own files were not available to compare with: this is the project's format, written and read here."""
+    n = len(exp_avgs)
+    state = {i: {"step": torch.tensor(float(step), dtype=torch.float32), "exp_avg": m, "exp_avg_sq": v}
+             for i, (m, v) in enumerate(zip(exp_avgs, exp_avg_sqs)) if m is not None}
+    base = lr if initial_lr is None else initial_lr
+
+    def group(ids, lr_, wd_, base_):
+        return dict(lr=lr_, initial_lr=base_, betas=(float(betas[0]), float(betas[1])), eps=float(eps), weight_decay=wd_, lamb=True, trust_clip=bool(trust_clip),
+                    always_adapt=bool(always_adapt), bias_correction=True, grad_averaging=True, params=ids)
+
+    if multipliers is None:
+        return {"state": state, "param_groups": [group(list(range(n)), lr, weight_decay, base)]}
+    return {"state": state, "param_groups": [group([i], lr * a, weight_decay * b, base * a) for i, (a, b) in enumerate(multipliers)]}
+
+
+def lamb_moments(opt_state, n_params):
+    """Inverse, as adamw_moments: (step, exp_avgs, exp_avg_sqs, first group).  A state another optimizer kind wrote -- SGD's (no moments), Adam's / AdamW's (groups
+    without lamb=True) -- is a ValueError: its moments mean nothing to this update."""
+    step, ms, vs, group = adamw_moments(opt_state, n_params)
+    if not all(g.get("lamb") for g in opt_state["param_groups"]):
+        raise ValueError("optimizer state: not written by the LAMB optimizer (a param group lacks lamb=True)")
+    return step, ms, vs, group

@@ -10,7 +10,7 @@ iters from ratio 0.01; mmcv 0.4.3 semantics).  `train_recognizer.
 What is different by design: the optimizer is not a torch.optim object stepping 161 tensors but a facade (`EngineSGD`) over the
 train engine's fused clip + SGD kernel on ONE flat parameter buffer -- same hyper-parameters, same `state_dict()` wire format
 (torch.optim.SGD's), same per-parameter `paramwise_options` -- and `EngineAdamW` over its fused Adam / AdamW step for
-`optimizer = dict(type='AdamW' | 'Adam', ...)`, with `lr_config` policies 'cosine' and 'poly' beside 'step'; `fp16 = dict(loss_scale=...)` in a config selects the engine's
+`optimizer = dict(type='AdamW' | 'Adam', ...)` and `EngineLamb` over its fused LAMB step for `optimizer = dict(type='Lamb', ...)`, with `lr_config` policies 'cosine' and 'poly' beside 'step'; `fp16 = dict(loss_scale=...)` in a config selects the engine's
 bf16 storage mode (fp32 master weights / gradients / statistics as the reference's Fp16OptimizerHook keeps them,
 codes/core/fp16/hooks.py:12-136; bf16's exponent range makes the loss scale a no-op, it is accepted and ignored).
 Host batches are staged through pinned memory and uploaded on a copy stream one batch ahead (the reference's scatter
@@ -259,18 +259,68 @@ class EngineAdamW(object):
         self.param_groups[0].update(lr=self.engine.lr, betas=self.engine.betas, eps=self.engine.eps, weight_decay=self.engine.weight_decay)
 
 
+class EngineLamb(object):
+    """What `build_optimizer` returns for type='Lamb' (timm's class name): EngineAdamW's surface (param_groups, state_dict, load_state_dict, zero_grad, step)
+    over the train engine's fused LAMB step (mvf_lamb_step on the flat buffers: exp_avg / exp_avg_sq laid out like the parameters, the step count and one
+    trust ratio per parameter tensor on the device; engine.trust_ratios() reads them).  The defaults are timm's (lr 1e-3, betas (0.9, 0.999), eps 1e-6,
+    weight_decay 0.01, trust_clip and always_adapt off); bias correction and grad_averaging are always on, so bias_correction=False / grad_averaging=False are
+    refused, and timm's max_grad_norm is the runner's grad_clip.  `step()` = all-reduce / world (when a process group is up) + global L2 clip (if `grad_clip`
+    was given) + the update, one fused launch sequence."""
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, trust_clip=False, always_adapt=False, bias_correction=True,
+                 grad_averaging=True, max_grad_norm=None, paramwise=None, dtype=None, **unknown):
+        if not grad_averaging:
+            raise NotImplementedError("Lamb grad_averaging=False is not built")
+        if not bias_correction:
+            raise NotImplementedError("Lamb bias_correction=False is not built")
+        if max_grad_norm is not None:
+            raise NotImplementedError("Lamb max_grad_norm: the clip is the runner's, optimizer_config = dict(grad_clip=dict(max_norm=...))")
+        if unknown:
+            raise TypeError("optimizer config: unexpected keys %s" % sorted(unknown))
+        model = model.module if hasattr(model, "module") else model
+        opt = dict(lr=lr, weight_decay=weight_decay, max_norm=None, optimizer="lamb", betas=betas, eps=eps, trust_clip=bool(trust_clip),
+                   always_adapt=bool(always_adapt))
+        if dtype is not None:
+            opt["dtype"] = dtype
+        self.model, self.engine = model, model.train_engine(**opt)
+        self.grad_clip = None
+        self.engine.max_norm = None
+        self.engine.set_param_options(paramwise)
+        self.param_groups = [dict(lr=lr, initial_lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, lamb=True, trust_clip=bool(trust_clip),
+                                  always_adapt=bool(always_adapt), bias_correction=True, grad_averaging=True, params=list(model.parameters()))]
+
+    zero_grad = EngineSGD.zero_grad
+
+    def step(self, lr=None):
+        g, eng = self.param_groups[0], self.engine
+        eng.weight_decay = g["weight_decay"]
+        if tuple(g["betas"]) != eng.betas or g["eps"] != eng.eps or bool(g["trust_clip"]) != eng.trust_clip or bool(g["always_adapt"]) != eng.always_adapt:
+            eng.set_optimizer("lamb", betas=g["betas"], eps=g["eps"], trust_clip=g["trust_clip"], always_adapt=g["always_adapt"])
+        return eng.step(g["lr"] if lr is None else lr)
+
+    state_dict = EngineAdamW.state_dict
+
+    def load_state_dict(self, sd):
+        eng = self.engine
+        eng.load_optimizer_state_dict(sd)
+        self.param_groups[0].update(lr=eng.lr, betas=eng.betas, eps=eng.eps, weight_decay=eng.weight_decay, trust_clip=eng.trust_clip, always_adapt=eng.always_adapt)
+
+
 def build_optimizer(model, optimizer_cfg, dtype=None):
     """reference train.py:79-156 for the optimizer the MVFNet configs use: dict(type='SGD', lr, momentum, weight_decay, nesterov
     [, paramwise_options=dict(bias_lr_mult, bias_decay_mult, norm_decay_mult)]) -> EngineSGD, and for fine-tuning configs
-    dict(type='AdamW' | 'Adam', lr, betas, eps, weight_decay[, paramwise_options]) -> EngineAdamW (amsgrad / maximize are refused)."""
+    dict(type='AdamW' | 'Adam', lr, betas, eps, weight_decay[, paramwise_options]) -> EngineAdamW (amsgrad / maximize are refused) or
+    dict(type='Lamb', lr, betas, eps, weight_decay, trust_clip, always_adapt[, paramwise_options]) -> EngineLamb (grad_averaging=False and unknown keys are
+    refused).  Type names are case-sensitive: 'Lamb' is timm's class name."""
     cfg = dict(optimizer_cfg)
     kind = cfg.pop("type", "SGD")
-    if kind not in ("SGD", "AdamW", "Adam"):
-        raise NotImplementedError("optimizer type %r: the fused HIP optimizers are SGD, AdamW and Adam" % kind)
+    if kind not in ("SGD", "AdamW", "Adam", "Lamb"):
+        raise NotImplementedError("optimizer type %r: the fused HIP optimizers are SGD, AdamW, Adam and Lamb" % kind)
     paramwise = cfg.pop("paramwise_options", None)
     target = model.module if hasattr(model, "module") else model
     if kind != "SGD" and not hasattr(target, "train_engine"):
-        raise NotImplementedError("optimizer type %r: the fused Adam step lives in a recognizer's train engine; %s has none" % (kind, type(target).__name__))
+        raise NotImplementedError("optimizer type %r: the fused %s step lives in a recognizer's train engine; %s has none"
+                                  % (kind, "LAMB" if kind == "Lamb" else "Adam", type(target).__name__))
     mult = None
     if paramwise is not None:
         if not isinstance(paramwise, dict):
@@ -278,6 +328,8 @@ def build_optimizer(model, optimizer_cfg, dtype=None):
         if ("bias_decay_mult" in paramwise or "norm_decay_mult" in paramwise) and cfg.get("weight_decay") is None:
             raise ValueError("weight_decay must be given explicitly when a decay multiplier is")        # train.py:123-125
         mult = paramwise_multipliers(target, paramwise)
+    if kind == "Lamb":
+        return EngineLamb(target, paramwise=mult, dtype=dtype, **cfg)
     if kind != "SGD":
         if kind == "Adam":
             cfg.setdefault("weight_decay", 0.0)          # (torch.optim.Adam's default; AdamW's is 1e-2)

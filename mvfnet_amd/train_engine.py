@@ -1353,7 +1353,7 @@ class _ParamStore(object):
             ls["grads"], ls["scale"] = grads, float(grad_scale)      # (what _guard_restore's scan and the measured step read)
             measured = self._layer_stats_before(grads)
         if self._adam is not None:
-            out = self._apply_adamw(grads, grad_scale, lr)
+            out = self._apply_lamb(grads, grad_scale, lr) if self._adam.get("lamb") is not None else self._apply_adamw(grads, grad_scale, lr)
         else:
             out = self._apply_sgd(grads, grad_scale, lr)
         if ls is not None:
@@ -1475,8 +1475,13 @@ class _ParamStore(object):
 
     @property
     def optimizer(self):
-        """'sgd' (default), 'adamw' (decoupled weight decay: p *= 1 - lr * wd) or 'adam' (g += wd * p).  Assignable before the engine's first step."""
-        return "sgd" if self._adam is None else ("adamw" if self._adam["decoupled"] else "adam")
+        """'sgd' (default), 'adamw' (decoupled weight decay: p *= 1 - lr * wd), 'adam' (g += wd * p) or 'lamb' (timm's Lamb: Adam's update + wd * p, scaled
+        per parameter tensor by ||w|| / ||update||).  Assignable before the engine's first step."""
+        if self._adam is None:
+            return "sgd"
+        if self._adam.get("lamb") is not None:
+            return "lamb"
+        return "adamw" if self._adam["decoupled"] else "adam"
 
     @optimizer.setter
     def optimizer(self, kind):
@@ -1484,25 +1489,30 @@ class _ParamStore(object):
 
     betas = property(lambda self: self._adam["betas"] if self._adam is not None else None)
     eps = property(lambda self: self._adam["eps"] if self._adam is not None else None)
+    trust_clip = property(lambda self: bool(self._adam["lamb"]["trust_clip"]) if self.optimizer == "lamb" else None)
+    always_adapt = property(lambda self: bool(self._adam["lamb"]["always_adapt"]) if self.optimizer == "lamb" else None)
 
-    def set_optimizer(self, kind, betas=None, eps=None):
-        """Select the optimizer; betas / eps (Adam forms only) default to what is set, else (0.9, 0.999) / 1e-8.  Changing the KIND is allowed before the first
-        step only: the moments of one optimizer mean nothing to another."""
+    def set_optimizer(self, kind, betas=None, eps=None, trust_clip=None, always_adapt=None):
+        """Select the optimizer; betas / eps (Adam forms and LAMB only) default to what is set, else (0.9, 0.999) / 1e-8 (LAMB: 1e-6, timm's value);
+        trust_clip / always_adapt (LAMB only) default to what is set, else False.  Changing the KIND is allowed before the first step only: the moments of one
+        optimizer mean nothing to another."""
         kind = str(kind).lower()
-        if kind not in ("sgd", "adamw", "adam"):
-            raise ValueError("optimizer %r: the fused HIP optimizers are 'sgd', 'adamw' and 'adam'" % (kind,))
+        if kind not in ("sgd", "adamw", "adam", "lamb"):
+            raise ValueError("optimizer %r: the fused HIP optimizers are 'sgd', 'adamw', 'adam' and 'lamb'" % (kind,))
+        if kind != "lamb" and (trust_clip is not None or always_adapt is not None):
+            raise ValueError("trust_clip / always_adapt belong to optimizer='lamb'")
         if not self.rehomed:
             raise RuntimeError("set_optimizer: this store does not own its parameters (stand-alone Bottleneck.forward)")
         if kind != self.optimizer and self.steps > 0:
             raise RuntimeError("the optimizer cannot be switched from %r to %r after the engine's first step" % (self.optimizer, kind))
         if kind == "sgd":
             if betas is not None or eps is not None:
-                raise ValueError("betas / eps belong to optimizer='adamw' | 'adam'")
+                raise ValueError("betas / eps belong to optimizer='adamw' | 'adam' | 'lamb'")
             self._adam = self.flat_var = None
             return
-        old = self._adam or {}
+        old = (self._adam or {}) if kind == self.optimizer or "lamb" not in (kind, self.optimizer) else {}      # (to or from LAMB: its eps default is its own)
         betas = tuple(float(b) for b in (betas if betas is not None else old.get("betas", (0.9, 0.999))))
-        eps = float(eps if eps is not None else old.get("eps", 1e-8))
+        eps = float(eps if eps is not None else old.get("eps", 1e-6 if kind == "lamb" else 1e-8))
         if len(betas) != 2 or not all(0.0 <= b < 1.0 for b in betas):
             raise ValueError("betas must be two numbers in [0, 1), got %r" % (betas,))
         if not eps > 0.0:
@@ -1511,9 +1521,18 @@ class _ParamStore(object):
             self.flat_var = torch.zeros_like(self.flat_params)          # new allocations beside the others: no recorded plan holds their addresses
             self._adam = dict(count=torch.zeros(1, dtype=torch.int64, device=self.device), hyper=_lib.AdamwHyper())
         self._adam.update(decoupled=int(kind == "adamw"), betas=betas, eps=eps)
+        if kind == "lamb":
+            lamb = self._adam.get("lamb") or dict(trust_clip=0, always_adapt=0, hyper=_lib.LambHyper(), tables={}, last=None)
+            if trust_clip is not None:
+                lamb["trust_clip"] = int(bool(trust_clip))
+            if always_adapt is not None:
+                lamb["always_adapt"] = int(bool(always_adapt))
+            self._adam["lamb"] = lamb
+        else:
+            self._adam.pop("lamb", None)
 
     def applied_steps(self):
-        """The device counter of APPLIED Adam / AdamW steps (skipped ones do not count).  An 8-byte read that waits for the device: checkpoint time only."""
+        """The device counter of APPLIED Adam / AdamW / LAMB steps (skipped ones do not count).  An 8-byte read that waits for the device: checkpoint time only."""
         if self._adam is None:
             raise RuntimeError("applied_steps: the optimizer is SGD")
         return int(self._adam["count"].item())
@@ -1546,6 +1565,78 @@ class _ParamStore(object):
             self._guard_restore()
         self.steps += 1
         return self.norm_out
+
+    # ---- LAMB: mvf_lamb_step in place of mvf_adamw_step -----------------------------------------------------------------------------------------------------
+    # Selected with TrainEngine(optimizer='lamb', betas=, eps=, trust_clip=, always_adapt=).  It lives in the Adam forms' slot (_adam): flat_mom / flat_var are
+    # exp_avg / exp_avg_sq, the device counter holds the applied steps, accumulation, the process-group path, the layer statistics and _guard_restore see one more
+    # optimizer behind _apply_optimizer.  What is LAMB's own: an UNMERGED per-parameter segment table (one segment = one trust-ratio unit, where _segments()
+    # merges neighbours with equal multipliers) and one float per parameter for the ratio applied last.  An engine that never selects LAMB allocates and
+    # launches exactly what it did.
+    def _lamb_segments(self, off):
+        """(device table, nseg, parameter names, device ratios) for the flat range [off, end): ONE segment per parameter, frozen parameters at lr_mult -1.
+        Cached like _seg_tables; set_param_options drops the cache.  The padding between parameters is zeros and joins the parameter in front of it: zeros
+        change neither norm, and their update is 0."""
+        tabs = self._adam["lamb"]["tables"]
+        opts = self.param_options or {}
+        key = (off, tuple(p.requires_grad for p in self.model.parameters()), tuple(sorted(opts.items())))
+        if key not in tabs:
+            segs, names, last = [], [], -1
+            for name, p in self.model.named_parameters():
+                first = self._grad_view[id(p)].storage_offset()
+                if first + p.numel() <= off:
+                    continue
+                mult = opts.get(id(p), (1.0, 1.0)) if p.requires_grad else (-1.0, 0.0)
+                start = max(first - off, 0) if segs else 0
+                if start <= last:
+                    raise RuntimeError("lamb: parameter %s does not lie behind its predecessor in the flat buffer" % name)      # (the table's contract, checked once)
+                last = start
+                segs.append(_lib.SgdSegment(start, mult[0], mult[1]))
+                names.append(name)
+            arr = (_lib.SgdSegment * len(segs))(*segs)
+            tabs[key] = (torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device), len(segs), names,
+                         torch.zeros(max(len(segs), 1), device=self.device))
+        return tabs[key]
+
+    def _apply_lamb(self, grads, grad_scale, lr=None):
+        """mvf_lamb_step on `grads` scaled by grad_scale: norm + clip + moments + per-parameter trust ratios + update (+ the averaged weights, + the guard)."""
+        off = self.trainable_offset()
+        n = self.flat_params.numel() - off
+        if n <= 0:
+            return None
+        if self._ema_swapped:
+            raise RuntimeError("apply_sgd inside averaged_weights(): the parameters are the averaged ones; leave the block before training")
+        a = self._adam
+        lamb = a["lamb"]
+        tab, nseg, names, ratios = self._lamb_segments(off)
+        ws = self.workspace(lib.mvf_lamb_workspace_bytes(n, nseg))
+        h = lamb["hyper"]
+        h.lr, h.weight_decay = float(self.lr if lr is None else lr), float(self.weight_decay or 0.0)
+        h.beta1, h.beta2, h.eps, h.trust_clip, h.always_adapt = a["betas"][0], a["betas"][1], a["eps"], lamb["trust_clip"], lamb["always_adapt"]
+        ema, ema_m = None, 0.0
+        if self.flat_ema is not None:
+            ema, ema_m = _p(self.flat_ema[off:]), _ema_momentum_at(self.ema_momentum, self.ema_warmup_steps, self.ema_updates)
+            self.ema_updates += 1
+        guard = _p(self._guard["buf"]) if self._guard is not None else None
+        check(lib.mvf_lamb_step(_p(self.flat_params[off:]), _p(grads[off:]), _p(self.flat_mom[off:]), _p(self.flat_var[off:]), n, C.c_float(grad_scale),
+                                C.c_float(self.max_norm or 0.0), C.byref(h), _p(tab), nseg, ema, C.c_float(ema_m), guard, _p(a["count"]), _p(self.norm_out),
+                                _p(ratios), _p(ws), ws.numel(), _st()), "lamb step")
+        lamb["last"] = (names, ratios)
+        if self._guard is not None:
+            self._guard_restore()
+        self.steps += 1
+        return self.norm_out
+
+    def trust_ratios(self):
+        """{parameter name: the trust ratio the last applied LAMB step used}: 1 where the parameter does not adapt (its weight decay is 0 and always_adapt is
+        off, or one of the two norms is 0), 0 where it is excluded from training.  A frozen prefix that trainable_offset() cuts off is not listed.  The one
+        read that waits for the device; a step the guard skipped leaves the figures of the step before it."""
+        if self.optimizer != "lamb":
+            raise RuntimeError("trust_ratios: the optimizer is %r" % self.optimizer)
+        last = self._adam["lamb"]["last"]
+        if last is None:
+            return {}
+        names, ratios = last
+        return dict(zip(names, ratios[:len(names)].tolist()))
 
     # ---- averaged weights: an exponential moving average of the parameters, one update per OPTIMIZER step ------------------------------------------------
     # e' = fmaf(m_t, p' - e, e) in fp32 (csrc/common.h ema_step), m_t = ema.momentum_at(momentum, warmup_steps, t).  flat_ema is laid out like flat_params; the
@@ -1727,16 +1818,23 @@ class _ParamStore(object):
             ms.append(self.flat_mom[first:first + p.numel()].view(p.shape).detach().cpu().clone() if stepped else None)
             vs.append(self.flat_var[first:first + p.numel()].view(p.shape).detach().cpu().clone() if stepped else None)
         mult = [self.param_options.get(id(p), (1.0, 1.0)) for p in params] if self.param_options else None
+        if a.get("lamb") is not None:          # Adam's wire layout, the groups marked lamb=True: the project's own format (checkpoint.lamb_state_dict)
+            from .checkpoint import lamb_state_dict
+            return lamb_state_dict(t, ms, vs, self.lr, a["betas"], a["eps"], self.weight_decay, bool(a["lamb"]["trust_clip"]), bool(a["lamb"]["always_adapt"]),
+                                   multipliers=mult, initial_lr=getattr(self, "initial_lr", None))
         return adamw_state_dict(t, ms, vs, self.lr, a["betas"], a["eps"], self.weight_decay, bool(a["decoupled"]), multipliers=mult,
                                 initial_lr=getattr(self, "initial_lr", None))
 
     def _load_adamw_state_dict(self, opt):
         """Inverse: torch.optim.AdamW's / Adam's state_dict into flat_mom / flat_var and the device counter.  With one param group its lr, betas, eps and
         weight_decay become the engine's (per-parameter groups carry multiplied values: the base values stay the engine's)."""
-        from .checkpoint import adamw_moments
+        from .checkpoint import adamw_moments, lamb_moments
         params = list(self.model.parameters())
-        t, ms, vs, group = adamw_moments(opt, len(params))
-        if "decoupled_weight_decay" in group and bool(group["decoupled_weight_decay"]) != bool(self._adam["decoupled"]):
+        is_lamb = self._adam.get("lamb") is not None
+        t, ms, vs, group = (lamb_moments if is_lamb else adamw_moments)(opt, len(params))
+        if group.get("lamb") and not is_lamb:
+            raise ValueError("optimizer state: written by LAMB, the engine's optimizer is %r" % self.optimizer)
+        if not is_lamb and "decoupled_weight_decay" in group and bool(group["decoupled_weight_decay"]) != bool(self._adam["decoupled"]):
             raise ValueError("optimizer state: written by %s, the engine's optimizer is %r" % ("AdamW" if group["decoupled_weight_decay"] else "Adam", self.optimizer))
         for p, m, v in zip(params, ms, vs):
             if m is not None and (tuple(m.shape) != tuple(p.shape) or tuple(v.shape) != tuple(p.shape)):
@@ -1753,7 +1851,8 @@ class _ParamStore(object):
             any_state = True
         self._adam["count"].fill_(int(t) if any_state else 0)
         if "betas" in group:
-            self.set_optimizer(self.optimizer, betas=group["betas"], eps=group.get("eps"))
+            more = dict(trust_clip=group.get("trust_clip"), always_adapt=group.get("always_adapt")) if is_lamb else {}
+            self.set_optimizer(self.optimizer, betas=group["betas"], eps=group.get("eps"), **more)
         if len(opt["param_groups"]) == 1:
             for k in ("lr", "weight_decay"):
                 if k in group:
@@ -1811,16 +1910,18 @@ class BlockTrainer(_ParamStore):
 class TrainEngine(_ParamStore):
     """One-GPU training step for a mvfnet_amd Recognizer2D (fp32)."""
 
-    def __init__(self, model, lr=0.015, momentum=0.9, weight_decay=1e-4, max_norm=40.0, dtype=torch.float32, optimizer="sgd", betas=None, eps=None):
+    def __init__(self, model, lr=0.015, momentum=0.9, weight_decay=1e-4, max_norm=40.0, dtype=torch.float32, optimizer="sgd", betas=None, eps=None,
+                 trust_clip=None, always_adapt=None):
         """optimizer = 'sgd' (default) | 'adamw' | 'adam' with betas = (0.9, 0.999), eps = 1e-8: the fused Adam forms (_ParamStore.set_optimizer); lr and
-        weight_decay are then theirs, momentum is unused.
+        weight_decay are then theirs, momentum is unused.  optimizer = 'lamb' with betas = (0.9, 0.999), eps = 1e-6, trust_clip = always_adapt = False: the
+        fused LAMB step (timm's Lamb), one trust ratio per parameter tensor (trust_ratios()).
         dtype = storage type of activations and packed weights (float32 | bfloat16).  With bfloat16 the accumulation,
         BatchNorm statistics, all parameter gradients, the master weights and the optimizer stay fp32 (what the
         reference's own fp16 mode keeps in fp32, codes/core/fp16/hooks.py:12-136; no loss scaling is needed for bf16)."""
         self._init_store(model, dtype)
         self.lr, self.momentum, self.weight_decay, self.max_norm = lr, momentum, weight_decay, max_norm
-        if str(optimizer).lower() != "sgd" or betas is not None or eps is not None:
-            self.set_optimizer(optimizer, betas=betas, eps=eps)
+        if str(optimizer).lower() != "sgd" or betas is not None or eps is not None or trust_clip is not None or always_adapt is not None:
+            self.set_optimizer(optimizer, betas=betas, eps=eps, trust_clip=trust_clip, always_adapt=always_adapt)
         bb = model.backbone
         self.stem, self.stem_bn = _TConv(bb.conv1, self, stem=True), _BN(bb.bn1, self, "bn1")
         self.blocks = [_TBlock(blk, self) for name in bb.res_layers for blk in getattr(bb, name)]
@@ -2094,7 +2195,8 @@ class TrainEngine(_ParamStore):
     def _uses_soft_head(self, lab):
         return self.blending is not None or self.label_smooth_eps > 0.0 or lab.is_floating_point() or self.bce is not None
 
-    def set_options(self, lr=None, momentum=None, weight_decay=None, max_norm=None, dtype=None, optimizer=None, betas=None, eps=None):
+    def set_options(self, lr=None, momentum=None, weight_decay=None, max_norm=None, dtype=None, optimizer=None, betas=None, eps=None, trust_clip=None,
+                    always_adapt=None):
         """Update the optimizer hyper-parameters of an existing engine (Recognizer2D.train_engine(**opt) on a model that already
         has one); the storage dtype is fixed at construction."""
         if dtype is not None and dtype != self.tdtype:
@@ -2102,8 +2204,8 @@ class TrainEngine(_ParamStore):
         for k, v in (("lr", lr), ("momentum", momentum), ("weight_decay", weight_decay), ("max_norm", max_norm)):
             if v is not None:
                 setattr(self, k, v)
-        if optimizer is not None or betas is not None or eps is not None:
-            self.set_optimizer(optimizer if optimizer is not None else self.optimizer, betas=betas, eps=eps)
+        if optimizer is not None or betas is not None or eps is not None or trust_clip is not None or always_adapt is not None:
+            self.set_optimizer(optimizer if optimizer is not None else self.optimizer, betas=betas, eps=eps, trust_clip=trust_clip, always_adapt=always_adapt)
 
     def _forward(self, imgs, labels, stages=None, prepared=None):
         b, t = imgs.shape[0], imgs.shape[1]
