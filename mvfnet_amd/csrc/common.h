@@ -75,7 +75,7 @@ __device__ __forceinline__ void st4(bf16_t* p, float4 v) {
     *reinterpret_cast<uint2*>(p) = r;
 }
 
-// One update of the averaged weights (ema.hip and the _ema optimizer kernels of train_ops.hip): e + m (p - e) with the product and the sum in one
+// One update of the averaged weights (ema.hip and the EMA forms of the optimizer kernels in optim.hip): e + m (p - e) with the product and the sum in one
 // rounding.  e == p is an exact fixed point, and the fp32 rounding of 1 - m never enters.  At m = 1 (the first step of a warm-up: the mean of one iterate
 // is that iterate) the result is p itself: fl(fl(p - e) + e) can miss p by an ulp where p - e falls into a higher binade than p.
 __device__ __forceinline__ float ema_step(float e, float p, float m) { return m >= 1.0f ? p : fmaf(m, p - e, e); }

@@ -2,7 +2,7 @@
 //
 // The training recipes for small sets (UCF101, HMDB51, Something-Something: 96-clip steps, blended inputs, a few thousand optimizer steps) are evaluated on
 // an average of the weights, not on the last iterate.  The fused optimizer kernels keep that average where the new parameter value is already in a register
-// (train_ops.hip: sgd_nesterov_kernel<true> / sgd_segments_kernel<true>).  mvf_ema_update is the same arithmetic after an optimizer that is not ours (the
+// (optim.hip: the EMA instantiations of sgd_kernel / adamw_kernel, lamb_apply_kernel).  mvf_ema_update is the same arithmetic after an optimizer that is not ours (the
 // attach_grads path) and the twin those kernels are tested against; mvf_ema_swap exchanges the averaged copy with the live parameters in place for
 // evaluation (TrainEngine.averaged_weights): the model's parameters are views of the flat buffer, so the pointers cannot be swapped, and a third
 // parameter-sized buffer is not wanted.

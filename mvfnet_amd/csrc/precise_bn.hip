@@ -9,7 +9,7 @@
 // exchange gathers / scatters / swaps the modules' buffers against such a flat array bit for bit.
 //
 // Latency-bound (60 k elements: the launch is the cost, which is why there is ONE): a thread per element, its segment found by binary search as
-// sgd_segments_kernel does (train_ops.hip: ~7 dependent 16-byte table reads that hit L2 after the first wave), no grid-stride loop, no atomics, every
+// sgd_kernel<SEG> does (optim.hip: ~7 dependent 16-byte table reads that hit L2 after the first wave), no grid-stride loop, no atomics, every
 // element owned by one thread: bit-identical from run to run.  The fp64 sum is taken in call order, the division is one IEEE fp64 division and one rounding to
 // fp32, so the result equals numpy's np.float32(sum(np.float64(x_j)) / np.float64(k)) bit for bit.
 //

@@ -1,7 +1,7 @@
 """Averaged weights (EMA) and precise BatchNorm: the host side that needs no device -- the configuration checks and the per-step momentum.
 
 The average itself lives in the train engine (TrainEngine.enable_ema: a flat fp32 buffer beside flat_params, updated by the fused optimizer kernels,
-csrc/train_ops.hip / csrc/ema.hip); checkpoints carry it as a top-level 'ema' entry (checkpoint.averaged_state_dict).  Precise BatchNorm (TrainEngine.precise_bn, evaluation.PreciseBNHook)
+csrc/optim.hip / csrc/ema.hip); checkpoints carry it as a top-level 'ema' entry (checkpoint.averaged_state_dict).  Precise BatchNorm (TrainEngine.precise_bn, evaluation.PreciseBNHook)
 recomputes the running statistics before evaluation, also for the averaged weights."""
 import numpy as np
 

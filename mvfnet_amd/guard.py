@@ -1,7 +1,7 @@
 """Non-finite step guard: the host side that needs no device -- the configuration check.
 
 The guard itself lives in the train engine (TrainEngine.enable_step_guard): the fused optimizer decides on the device whether the step's clip norm is finite
-(csrc/train_ops.hip, mvf_sgd_step_guarded), a skipped step leaves parameters, momentum and the averaged weights untouched, and the BatchNorm running statistics
+(csrc/optim.hip, mvf_sgd_step_guarded), a skipped step leaves parameters, momentum and the averaged weights untouched, and the BatchNorm running statistics
 the step's forward passes have already moved are put back (csrc/precise_bn.hip, mvf_bn_stats_snapshot / mvf_bn_stats_restore).  The Runner reads the
 counters where it synchronises anyway and stops the run after `max_consecutive` skipped steps in a row."""
 import numpy as np

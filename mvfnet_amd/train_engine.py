@@ -1321,23 +1321,35 @@ class _ParamStore(object):
         self.param_options = {id(p): (float(a), float(b)) for p, (a, b) in options.items()} if options else None
         self._seg_tables = {}
 
+    def _segment_table(self, off, merge):
+        """(device table, nseg, name of the parameter that opens each segment) for the flat range [off, end): a parameter's (lr_mult, decay_mult) from
+        param_options, (-1, 0) = excluded with requires_grad False (norm, update and momentum skip it).  merge: neighbours with equal multipliers share a
+        segment; else ONE segment per parameter, in ascending flat order (checked).  The padding between parameters is zeros and joins the parameter in
+        front of it: zeros change no norm, and their update is 0."""
+        opts = self.param_options or {}
+        segs, names, last = [], [], None
+        for name, p in self.model.named_parameters():
+            first = self._grad_view[id(p)].storage_offset()
+            if first + p.numel() <= off:
+                continue
+            mult = opts.get(id(p), (1.0, 1.0)) if p.requires_grad else (-1.0, 0.0)
+            if merge and mult == last:
+                continue
+            start = max(first - off, 0) if segs else 0
+            if not merge and segs and start <= segs[-1].first:
+                raise RuntimeError("lamb: parameter %s does not lie behind its predecessor in the flat buffer" % name)      # (the table's contract, checked once)
+            segs.append(_lib.SgdSegment(start, mult[0], mult[1]))
+            names.append(name)
+            last = mult
+        arr = (_lib.SgdSegment * len(segs))(*segs)
+        return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device), len(segs), names
+
     def _segments(self, off):
-        """Device table of optimizer segments for the flat range [off, end): neighbours with equal (lr_mult, decay_mult) share a
-        segment; a parameter with requires_grad False gets lr_mult -1 = excluded (norm, update and momentum skip it)."""
+        """The merged table (SGD and the Adam forms), cached per (off, requires_grad pattern); set_param_options drops the cache."""
         tabs = self.__dict__.setdefault("_seg_tables", {})
         key = (off, tuple(p.requires_grad for p in self.model.parameters()))
         if key not in tabs:
-            segs, last = [], None
-            for p in self.model.parameters():
-                first = self._grad_view[id(p)].storage_offset()
-                if first + p.numel() <= off:
-                    continue
-                mult = (self.param_options or {}).get(id(p), (1.0, 1.0)) if p.requires_grad else (-1.0, 0.0)
-                if mult != last:                    # (padding elements between parameters are zeros: they may join either side)
-                    segs.append(_lib.SgdSegment(max(first - off, 0) if segs else 0, mult[0], mult[1]))
-                    last = mult
-            arr = (_lib.SgdSegment * len(segs))(*segs)
-            tabs[key] = (torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device), len(segs))
+            tabs[key] = self._segment_table(off, merge=True)[:2]
         return tabs[key]
 
     def apply_sgd(self, lr=None, world=1):
@@ -1405,9 +1417,10 @@ class _ParamStore(object):
             ent = ls["bn"][id(tab)] = (tab, torch.zeros(tab.nseg, dtype=torch.int64, device=self.device))
         check(lib.mvf_bn_stats_nonfinite(_p(tab.dev), tab.nseg, tab.n, _p(ent[1]), _p(self._guard["buf"]), _st()), "bn stats nonfinite")
 
-    def _apply_sgd(self, grads, grad_scale, lr=None):
-        """The optimizer's launch sequence on `grads` (a flat fp32 tensor laid out like flat_grads: flat_grads itself, or the accumulator of
-        TrainEngine.apply_accumulated) scaled by grad_scale."""
+    def _optimizer_operands(self):
+        """What every _apply_* opens with: (off, n, ema, ema_m, guard) -- the trainable range [off, off + n) of the flat buffers, the averaged copy's pointer
+        and this step's momentum (None, 0.0 without one: the average moves in the kernel that stores the new parameters, its momentum travels by value) and
+        the guard counters' pointer (None = unguarded) -- or None when nothing trains."""
         if not self.rehomed:
             raise RuntimeError("apply_sgd: this store does not own its parameters (stand-alone Bottleneck.forward); use the model's train engine or a torch optimizer")
         off = self.trainable_offset()
@@ -1416,41 +1429,48 @@ class _ParamStore(object):
             return None
         if self._ema_swapped:
             raise RuntimeError("apply_sgd inside averaged_weights(): the parameters are the averaged ones; leave the block before training")
+        ema, ema_m = None, 0.0
+        if self.flat_ema is not None:
+            ema, ema_m = _p(self.flat_ema[off:]), _ema_momentum_at(self.ema_momentum, self.ema_warmup_steps, self.ema_updates)
+        guard = _p(self._guard["buf"]) if self._guard is not None else None
+        return off, n, ema, ema_m, guard
+
+    def _optimizer_done(self):
+        """... and closes with, behind the launched step: the average has one more update, the guard's conditional restore of the BatchNorm statistics."""
+        if self.flat_ema is not None:
+            self.ema_updates += 1
+        if self._guard is not None:
+            self._guard_restore()
+        self.steps += 1
+        return self.norm_out
+
+    def _apply_sgd(self, grads, grad_scale, lr=None):
+        """The optimizer's launch sequence on `grads` (a flat fp32 tensor laid out like flat_grads: flat_grads itself, or the accumulator of
+        TrainEngine.apply_accumulated) scaled by grad_scale: the plain or _ema entry point, flat or with the segment table, or mvf_sgd_step_guarded (all four
+        forms) behind the non-finite guard."""
+        ops = self._optimizer_operands()
+        if ops is None:
+            return None
+        off, n, ema, ema_m, guard = ops
         ws = self.workspace(lib.mvf_sgd_workspace_bytes(n))
         args = (_p(self.flat_params[off:]), _p(grads[off:]), _p(self.flat_mom[off:]), n, C.c_float(grad_scale),
                 C.c_float(self.max_norm or 0.0), C.c_float(self.lr if lr is None else lr), C.c_float(self.momentum),
                 C.c_float(self.weight_decay), int(self.steps == 0))
         tail = (_p(self.norm_out), _p(ws), ws.numel(), _st())
         flat = self.nesterov and not self.param_options and not self._scattered_frozen
+        seg = ()
         if not flat:
             tab, nseg = self._segments(off)
-            args += (int(self.nesterov), _p(tab), nseg)
-        if self._guard is not None:
-            self._apply_sgd_guarded(args, tail, flat, off)
-        elif self.flat_ema is None:
-            check((lib.mvf_sgd_nesterov_step if flat else lib.mvf_sgd_step_segments)(*(args + tail)), "sgd step")
+            seg = (int(self.nesterov), _p(tab), nseg)
+        if guard is not None:
+            check(lib.mvf_sgd_step_guarded(*(args + (seg or (0, None, 0)) + (ema, C.c_float(ema_m), guard) + tail)), "sgd step (guarded)")
+        elif ema is None:
+            check((lib.mvf_sgd_nesterov_step if flat else lib.mvf_sgd_step_segments)(*(args + seg + tail)), "sgd step")
         else:
-            # the averaged copy moves in the kernel that stores the new parameters; the step's momentum travels by value (the optimizer runs outside the launch plans)
-            ema = (_p(self.flat_ema[off:]), C.c_float(_ema_momentum_at(self.ema_momentum, self.ema_warmup_steps, self.ema_updates)))
-            check((lib.mvf_sgd_nesterov_step_ema if flat else lib.mvf_sgd_step_segments_ema)(*(args + ema + tail)), "sgd step (ema)")
-            self.ema_updates += 1
-        self.steps += 1
-        return self.norm_out
+            check((lib.mvf_sgd_nesterov_step_ema if flat else lib.mvf_sgd_step_segments_ema)(*(args + seg + (ema, C.c_float(ema_m)) + tail)), "sgd step (ema)")
+        return self._optimizer_done()
 
     _guard = None      # non-finite step guard (TrainEngine.enable_step_guard): None = off, the launches above are all there is
-
-    def _apply_sgd_guarded(self, args, tail, flat, off):
-        """The optimizer behind the non-finite guard: mvf_sgd_step_guarded (all four forms), then the conditional restore of the BatchNorm statistics."""
-        g = self._guard
-        if flat:
-            args += (0, None, 0)
-        if self.flat_ema is None:
-            ema = (None, C.c_float(0.0))
-        else:
-            ema = (_p(self.flat_ema[off:]), C.c_float(_ema_momentum_at(self.ema_momentum, self.ema_warmup_steps, self.ema_updates)))
-            self.ema_updates += 1
-        check(lib.mvf_sgd_step_guarded(*(args + ema + (_p(g["buf"]),) + tail)), "sgd step (guarded)")
-        self._guard_restore()
 
     def _guard_restore(self):
         """Behind a guarded optimizer step: the conditional restore of the BatchNorm statistics snapshot taken before the step's first forward."""
@@ -1539,12 +1559,10 @@ class _ParamStore(object):
 
     def _apply_adamw(self, grads, grad_scale, lr=None):
         """mvf_adamw_step on `grads` scaled by grad_scale: norm + clip + Adam / AdamW (+ the averaged weights, + the guard) in one launch sequence."""
-        off = self.trainable_offset()
-        n = self.flat_params.numel() - off
-        if n <= 0:
+        ops = self._optimizer_operands()
+        if ops is None:
             return None
-        if self._ema_swapped:
-            raise RuntimeError("apply_sgd inside averaged_weights(): the parameters are the averaged ones; leave the block before training")
+        off, n, ema, ema_m, guard = ops
         a = self._adam
         ws = self.workspace(lib.mvf_adamw_workspace_bytes(n))
         h = a["hyper"]
@@ -1553,18 +1571,10 @@ class _ParamStore(object):
         tab, nseg = (None, 0)
         if self.param_options or self._scattered_frozen:
             tab, nseg = self._segments(off)
-        ema, ema_m = None, 0.0
-        if self.flat_ema is not None:
-            ema, ema_m = _p(self.flat_ema[off:]), _ema_momentum_at(self.ema_momentum, self.ema_warmup_steps, self.ema_updates)
-            self.ema_updates += 1
-        guard = _p(self._guard["buf"]) if self._guard is not None else None
         check(lib.mvf_adamw_step(_p(self.flat_params[off:]), _p(grads[off:]), _p(self.flat_mom[off:]), _p(self.flat_var[off:]), n, C.c_float(grad_scale),
-                                 C.c_float(self.max_norm or 0.0), C.byref(h), _p(tab) if tab is not None else None, nseg, ema, C.c_float(ema_m), guard,
+                                 C.c_float(self.max_norm or 0.0), C.byref(h), _p(tab), nseg, ema, C.c_float(ema_m), guard,
                                  _p(a["count"]), _p(self.norm_out), _p(ws), ws.numel(), _st()), "adamw step")
-        if self._guard is not None:
-            self._guard_restore()
-        self.steps += 1
-        return self.norm_out
+        return self._optimizer_done()
 
     # ---- LAMB: mvf_lamb_step in place of mvf_adamw_step -----------------------------------------------------------------------------------------------------
     # Selected with TrainEngine(optimizer='lamb', betas=, eps=, trust_clip=, always_adapt=).  It lives in the Adam forms' slot (_adam): flat_mom / flat_var are
@@ -1573,38 +1583,21 @@ class _ParamStore(object):
     # merges neighbours with equal multipliers) and one float per parameter for the ratio applied last.  An engine that never selects LAMB allocates and
     # launches exactly what it did.
     def _lamb_segments(self, off):
-        """(device table, nseg, parameter names, device ratios) for the flat range [off, end): ONE segment per parameter, frozen parameters at lr_mult -1.
-        Cached like _seg_tables; set_param_options drops the cache.  The padding between parameters is zeros and joins the parameter in front of it: zeros
-        change neither norm, and their update is 0."""
+        """(device table, nseg, parameter names, device ratios) for the flat range [off, end): the UNMERGED table, ONE segment per parameter, frozen
+        parameters at lr_mult -1.  Cached per (off, requires_grad pattern, param_options)."""
         tabs = self._adam["lamb"]["tables"]
-        opts = self.param_options or {}
-        key = (off, tuple(p.requires_grad for p in self.model.parameters()), tuple(sorted(opts.items())))
+        key = (off, tuple(p.requires_grad for p in self.model.parameters()), tuple(sorted((self.param_options or {}).items())))
         if key not in tabs:
-            segs, names, last = [], [], -1
-            for name, p in self.model.named_parameters():
-                first = self._grad_view[id(p)].storage_offset()
-                if first + p.numel() <= off:
-                    continue
-                mult = opts.get(id(p), (1.0, 1.0)) if p.requires_grad else (-1.0, 0.0)
-                start = max(first - off, 0) if segs else 0
-                if start <= last:
-                    raise RuntimeError("lamb: parameter %s does not lie behind its predecessor in the flat buffer" % name)      # (the table's contract, checked once)
-                last = start
-                segs.append(_lib.SgdSegment(start, mult[0], mult[1]))
-                names.append(name)
-            arr = (_lib.SgdSegment * len(segs))(*segs)
-            tabs[key] = (torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device), len(segs), names,
-                         torch.zeros(max(len(segs), 1), device=self.device))
+            tab, nseg, names = self._segment_table(off, merge=False)
+            tabs[key] = (tab, nseg, names, torch.zeros(max(nseg, 1), device=self.device))
         return tabs[key]
 
     def _apply_lamb(self, grads, grad_scale, lr=None):
         """mvf_lamb_step on `grads` scaled by grad_scale: norm + clip + moments + per-parameter trust ratios + update (+ the averaged weights, + the guard)."""
-        off = self.trainable_offset()
-        n = self.flat_params.numel() - off
-        if n <= 0:
+        ops = self._optimizer_operands()
+        if ops is None:
             return None
-        if self._ema_swapped:
-            raise RuntimeError("apply_sgd inside averaged_weights(): the parameters are the averaged ones; leave the block before training")
+        off, n, ema, ema_m, guard = ops
         a = self._adam
         lamb = a["lamb"]
         tab, nseg, names, ratios = self._lamb_segments(off)
@@ -1612,19 +1605,11 @@ class _ParamStore(object):
         h = lamb["hyper"]
         h.lr, h.weight_decay = float(self.lr if lr is None else lr), float(self.weight_decay or 0.0)
         h.beta1, h.beta2, h.eps, h.trust_clip, h.always_adapt = a["betas"][0], a["betas"][1], a["eps"], lamb["trust_clip"], lamb["always_adapt"]
-        ema, ema_m = None, 0.0
-        if self.flat_ema is not None:
-            ema, ema_m = _p(self.flat_ema[off:]), _ema_momentum_at(self.ema_momentum, self.ema_warmup_steps, self.ema_updates)
-            self.ema_updates += 1
-        guard = _p(self._guard["buf"]) if self._guard is not None else None
         check(lib.mvf_lamb_step(_p(self.flat_params[off:]), _p(grads[off:]), _p(self.flat_mom[off:]), _p(self.flat_var[off:]), n, C.c_float(grad_scale),
                                 C.c_float(self.max_norm or 0.0), C.byref(h), _p(tab), nseg, ema, C.c_float(ema_m), guard, _p(a["count"]), _p(self.norm_out),
                                 _p(ratios), _p(ws), ws.numel(), _st()), "lamb step")
         lamb["last"] = (names, ratios)
-        if self._guard is not None:
-            self._guard_restore()
-        self.steps += 1
-        return self.norm_out
+        return self._optimizer_done()
 
     def trust_ratios(self):
         """{parameter name: the trust ratio the last applied LAMB step used}: 1 where the parameter does not adapt (its weight decay is 0 and always_adapt is

@@ -94,7 +94,7 @@ def test_plan_run_generic_call_marshals_integers_and_floats_in_order():
 
 
 def test_head_and_optimizer_argument_failures_return_before_any_launch():
-    """The head's and the optimizer's entry points check their arguments before the first launch (csrc/train_ops.hip, csrc/net_ops.hip): the codes come back on
+    """The head's and the optimizer's entry points check their arguments before the first launch (csrc/train_ops.hip, csrc/optim.hip, csrc/net_ops.hip): the codes come back on
     a machine without a GPU, from host addresses that are never read."""
     import ctypes as C
     from mvfnet_amd import _lib

@@ -1,4 +1,4 @@
-"""The fused clip + Adam / AdamW step (mvf_adamw_step; csrc/train_ops.hip adamw_norm_finalize / adamw_kernel) through the C ABI against the fp64 restatement
+"""The fused clip + Adam / AdamW step (mvf_adamw_step; csrc/optim.hip norm_finalize / adamw_kernel) through the C ABI against the fp64 restatement
 in adamw_numpy.py, and the engine / runner / checkpoint layers above it (TrainEngine(optimizer='adamw'), build_optimizer(type='AdamW'), Runner.resume).
 
 Settings: lr 1e-3, betas (0.9, 0.999), eps 1e-8, weight_decay 0.05, max_norm 40 (adamw_numpy's constants).  Gradients follow test_head_optimizer_gpu.sgd_grads:

@@ -1,4 +1,4 @@
-"""GPU: averaged weights (EMA) -- mvf_ema_update / mvf_ema_swap (csrc/ema.hip), the _ema twins of the fused optimizer steps (csrc/train_ops.hip) and the
+"""GPU: averaged weights (EMA) -- mvf_ema_update / mvf_ema_swap (csrc/ema.hip), the _ema twins of the fused optimizer steps (csrc/optim.hip) and the
 engine / runner / checkpoint layers above them (TrainEngine.enable_ema, averaged_weights, Runner(ema=...), checkpoint.averaged_state_dict).
 
 The arithmetic is pinned: e' = fmaf(m, p' - e, e) in fp32 once per optimizer step, e' = p' itself at m = 1.  Against an fp64 restatement every update makes

@@ -1,7 +1,7 @@
 """The last two stages of a training step through the C ABI, each against an fp64 restatement written here: the TSN head (tsn_clshead.py: per-frame
 average pool -> dropout -> fc -> consensus mean over the segments -> cross-entropy; csrc/train_ops.hip frame_pool / head_fc_seg / ce_loss / head_fc_bwd_w /
 head_dpool / head_dfeat and csrc/net_ops.hip head_pool / head_fc / average_clip) and the fused clip_grad_norm_ + SGD step (dist_utils.py:61-67 +
-torch.optim.SGD; sqsum_* / norm_finalize / sgd_nesterov / sgd_segments).  The references take the same explicit dropout mask, labels and segment table as
+torch.optim.SGD; csrc/optim.hip sqsum_* / norm_finalize / sgd_kernel).  The references take the same explicit dropout mask, labels and segment table as
 the kernels; inputs come from seeded generators.
 
 Bounds.  Every bound is one the suite already uses for these kernels (test_train_gpu.py test_stem_wgrad_maxpool_head_sgd_vs_oracle, test_conv_gpu.py):
@@ -353,6 +353,51 @@ def test_sgd_step_segments_vs_fp64(nesterov, fill):
 def test_sgd_step_segments_single_segment_equals_the_flat_reference():
     """nseg = 1, {0, 1, 1}, nesterov = 1 is the flat form: against the flat form's fp64 reference, same bounds."""
     run_sgd_steps(SEG_N, 0.125, segs=((0, 1.0, 1.0),), nesterov=1)
+
+
+@pytest.mark.parametrize("form", ["plain", "ema", "guarded"])
+@pytest.mark.parametrize("n", [1, 257, 5000, 1048576 + 5], ids=lambda n: "n%d" % n)
+def test_sgd_one_segment_table_equals_the_flat_form_bit_for_bit(n, form):
+    """The flat entry point against the segment entry point with the table {0, 1, 1} and nesterov = 1, from the same start state, over a clipping step with
+    first_step = 1, a non-clipping one and one with max_norm = 0: parameters, momentum and norm_out (ema: and the average; guarded: mvf_sgd_step_guarded with
+    segments = NULL against the table, with the average and the counters) equal as int32 bit patterns after every step.  n = 1048581 takes the update
+    grid (4096 x 256) into a second sweep."""
+    lib, check = _lib()
+    dev, gs, ema_m = "cuda", 0.125, 0.25
+    gen = torch.Generator().manual_seed(n * 7 + 3)
+    start = [torch.randn(n, generator=gen).to(dev) for _ in range(3)]                     # parameters, momentum, average
+    tab = torch.from_numpy(np.array([(0, 1.0, 1.0)], dtype=SEG_DTYPE).view(np.uint8)).to(dev)
+
+    def side():
+        return dict(p=start[0].clone(), b=start[1].clone(), e=start[2].clone(), norm=torch.full((2,), float("nan"), device=dev),
+                    guard=torch.zeros(4, dtype=torch.int32, device=dev), ws=torch.empty(lib.mvf_sgd_workspace_bytes(n), dtype=torch.uint8, device=dev))
+
+    def step(s, g, max_norm, first, seg):
+        head = (P(s["p"]), P(g), P(s["b"]), n, gs, max_norm, LR, MOM, WD, first)
+        segs = (1, P(tab), 1) if seg else ()
+        tail = (P(s["norm"]), P(s["ws"]), s["ws"].numel(), None)
+        if form == "plain":
+            fn, mid = (lib.mvf_sgd_step_segments if seg else lib.mvf_sgd_nesterov_step), ()
+        elif form == "ema":
+            fn, mid = (lib.mvf_sgd_step_segments_ema if seg else lib.mvf_sgd_nesterov_step_ema), (P(s["e"]), ema_m)
+        else:
+            fn, segs, mid = lib.mvf_sgd_step_guarded, segs or (1, None, 0), (P(s["e"]), ema_m, P(s["guard"]))
+        check(fn(*(head + segs + mid + tail)), "sgd %s, %s" % (form, "table" if seg else "flat"))
+
+    flat, seg = side(), side()
+    for k in range(3):
+        g = torch.from_numpy(sgd_grads(n, gs, k, gen)).to(dev)
+        before = flat["p"].clone()
+        for s, with_table in ((flat, False), (seg, True)):
+            step(s, g, 0.0 if k == 2 else MAX_NORM, int(k == 0), with_table)
+        torch.cuda.synchronize()
+        for name in ("p", "b", "norm", "e", "guard"):
+            assert torch.equal(flat[name].view(torch.int32), seg[name].view(torch.int32)), (k, name)
+        coef = float(flat["norm"][1])
+        assert (coef < 0.5) if k == 0 else (coef == 1.0), (k, coef)
+        assert not torch.equal(flat["p"], before), k                                      # a step was applied
+        assert torch.equal(flat["e"], start[2]) == (form == "plain"), k                   # the average moves in the forms that keep one
+        assert flat["guard"].tolist() == ([0, 0, 0, k + 1] if form == "guarded" else [0, 0, 0, 0]), k
 
 
 # ------------------------------------------------------------------------------------------------ 5. one engine step with the shipped dropout

@@ -1,4 +1,4 @@
-"""The fused clip + LAMB step (mvf_lamb_step; csrc/train_ops.hip lamb_moments / lamb_ratio / lamb_apply kernels) through the C ABI against the fp64 restatement in
+"""The fused clip + LAMB step (mvf_lamb_step; csrc/optim.hip lamb_moments / lamb_ratio / lamb_apply kernels) through the C ABI against the fp64 restatement in
 lamb_numpy.py, and the engine / runner / checkpoint layers above it (TrainEngine(optimizer='lamb'), build_optimizer(type='Lamb'), trust_ratios()).
 
 Settings: lr 5e-3, betas (0.9, 0.999), eps 1e-6, weight_decay 0.02, max_norm 40 (lamb_numpy's constants).  Gradients follow test_adamw_gpu: the scaled norm is

@@ -1,4 +1,4 @@
-"""GPU: the non-finite step guard -- mvf_sgd_step_guarded (csrc/train_ops.hip), mvf_bn_stats_snapshot / mvf_bn_stats_restore (csrc/precise_bn.hip) and the
+"""GPU: the non-finite step guard -- mvf_sgd_step_guarded (csrc/optim.hip), mvf_bn_stats_snapshot / mvf_bn_stats_restore (csrc/precise_bn.hip) and the
 engine / runner / checkpoint layers above them (TrainEngine.enable_step_guard, guard_state, Runner(nonfinite_guard=...)).
 
 Everything is compared as bit patterns (int32 / int64 views) unless a test says otherwise: the guard adds no arithmetic, so there is no tolerance to state.
