@@ -498,6 +498,52 @@ int mvf_maxpool_bn_relu_bwd_apply(const unsigned char* argmax, const void* g, in
                                   const float* dbeta, void* dz, int dtype, void* stream);
 int mvf_maxpool_bn_relu_bwd_sums(const unsigned char* argmax, const void* g, int n, int h, int w, int c, void* ga, const void* z, const float* mean,
                                  const float* invstd, const float* scale, const float* shift, float* sums_part, int dtype, void* stream);
+/* Which kernels the calling thread's LAST BatchNorm / max-pool call launched: the counterpart of mvf_conv2d_wgrad_last_launch for csrc/train_ops.hip
+ * (host-side, thread-local, plain stores next to the launches; no device work).  The entry points that have an MVF_BN_ENTRY_* value below, and only those,
+ * start a new record: mvf_bn_train_stats, mvf_bn_train_finalize, mvf_bn_apply[_bits], mvf_bn_apply_colmeans, mvf_bn_bwd_reduce, mvf_bn_bwd_finalize,
+ * mvf_bn_bwd_apply[_masked], mvf_bn_bwd_pair, mvf_bn_bwd_pair_wgrad and the four mvf_maxpool_bn_relu_* calls.  A call refused before its first launch leaves
+ * `entry` = that entry point, launches = 0, vn = 0 and both forms NONE; a launch the runtime refuses (MVF_EHIP) is not counted.  Every other call leaves the
+ * record alone: the plan queries (mvf_bn_workspace_bytes, mvf_maxpool_bwd_sums_rows, mvf_bn_bwd_wgrad_*) and the entry points whose kernels live in other
+ * files (mvf_bn_train_stats_gram, mvf_bn_bwd_apply_wgrad, mvf_conv1x1_bwd_fused, mvf_conv1x1_bnbwd_sums_pair).  mvf_bn_bwd_pair_wgrad records its sums
+ * (reduce + finalize: launches = 2, the reduce kernel's plan); the fused apply + weight-gradient launch of csrc/bnbwd_wgrad.hip is not part of the record. */
+enum {
+    MVF_BN_ENTRY_NONE = 0,
+    MVF_BN_ENTRY_TRAIN_STATS = 1, MVF_BN_ENTRY_TRAIN_FINALIZE = 2,
+    MVF_BN_ENTRY_APPLY = 3,               /* mvf_bn_apply / mvf_bn_apply_bits                                                                */
+    MVF_BN_ENTRY_APPLY_COLMEANS = 4,
+    MVF_BN_ENTRY_BWD_REDUCE = 5, MVF_BN_ENTRY_BWD_FINALIZE = 6,
+    MVF_BN_ENTRY_BWD_APPLY = 7,           /* mvf_bn_bwd_apply / mvf_bn_bwd_apply_masked                                                      */
+    MVF_BN_ENTRY_BWD_PAIR = 8, MVF_BN_ENTRY_BWD_PAIR_WGRAD = 9,
+    MVF_BN_ENTRY_POOL_FWD = 10, MVF_BN_ENTRY_POOL_BWD = 11, MVF_BN_ENTRY_POOL_BWD_SUMS = 12, MVF_BN_ENTRY_POOL_BWD_APPLY = 13
+};
+enum {
+    MVF_BN_FIN_NONE = 0,
+    MVF_BN_FIN_ROW_MAJOR = 1,             /* partials [rows][c][2]: a workgroup per 4 channels (the library's own column kernels)            */
+    MVF_BN_FIN_CM_WORKGROUP = 2,          /* channel-major partials [c][rows][2], rows >= 1024: a workgroup per channel                      */
+    MVF_BN_FIN_CM_WAVE = 3                /* channel-major, fewer rows: a wave per channel, 4 channels per workgroup                         */
+};
+enum {
+    MVF_POOL_FORM_NONE = 0,
+    MVF_POOL_FORM_ELEMENT = 1,            /* forward / backward: a thread per (pixel, 4 channels)                                            */
+    MVF_POOL_FORM_ROWS = 2,               /* backward: a workgroup per input row (w * c / 4 >= 256)                                          */
+    MVF_POOL_FORM_BLOCK = 3,              /* forward (h, w % 4 == 0), backward sums / apply (even h, w; policy pool_*_block): 2 x 2 blocks   */
+    MVF_POOL_FORM_ROWS_SUMS = 4,          /* mvf_maxpool_bn_relu_bwd_sums: 8 input rows per workgroup + the BatchNorm sums                   */
+    MVF_POOL_FORM_ROWS_APPLY = 5          /* mvf_maxpool_bn_relu_bwd_apply: the same walk, re-gathering ga                                   */
+};
+typedef struct {
+    int32_t entry;                        /* MVF_BN_ENTRY_*                                                                                  */
+    int32_t dtype;                        /* MVF_F32 | MVF_BF16 (the two finalize entry points: MVF_F32)                                     */
+    int32_t vn;                           /* elements per lane of the LAST column-plan kernel of the call: 4 (fp32, or bf16 in 8-byte        */
+                                          /* lanes) | 8 (bf16 in 16-byte lanes); 0: none ran (finalize and pool entry points, refusals)      */
+    int32_t cqb, rows, gx, gy;            /* that kernel's column plan: channel groups and rows per workgroup, grid                          */
+    int32_t mask_mode;                    /* the backward entry points: 0 - 4 (pair: 4; pool sums / apply: 2); else -1                       */
+    int32_t specialised;                  /* 1: the kernel instantiated for that mask mode ran (policy bn_spec); 0: the run-time select      */
+    int32_t finalize;                     /* MVF_BN_FIN_*                                                                                    */
+    int32_t part_rows;                    /* partial rows per channel the finalize summed, or the pool sums kernel wrote; else 0             */
+    int32_t pool;                         /* MVF_POOL_FORM_*                                                                                 */
+    int32_t launches;                     /* kernel launches the call made                                                                   */
+} mvf_bn_launch_info_t;
+int mvf_bn_last_launch(mvf_bn_launch_info_t* out);
 /* head: avg-pool per frame -> new_fc -> mean over the clip's t frames -> cross-entropy (mean over clips).
  * pooled (clips*t, c), scores (clips, classes), dscores = dloss/dscores, loss_part (clips), loss (1): all fp32. */
 int mvf_head_train_fwd(const void* feat, int clips, int t, int hw, int c, const float* fc_w, const float* fc_b, int classes,

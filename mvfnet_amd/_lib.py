@@ -76,6 +76,19 @@ class TapgradLaunchInfo(C.Structure):
 TAPGRAD_KERNELS = {0: "none", 1: "rows", 2: "bands"}
 
 
+class BnLaunchInfo(C.Structure):
+    """mvf_bn_launch_info_t: which kernels the calling thread's last BatchNorm / max-pool call of csrc/train_ops.hip launched (host-side record)."""
+    _fields_ = [("entry", C.c_int32), ("dtype", C.c_int32), ("vn", C.c_int32), ("cqb", C.c_int32), ("rows", C.c_int32), ("gx", C.c_int32), ("gy", C.c_int32),
+                ("mask_mode", C.c_int32), ("specialised", C.c_int32), ("finalize", C.c_int32), ("part_rows", C.c_int32), ("pool", C.c_int32),
+                ("launches", C.c_int32)]
+
+
+BN_ENTRIES = {0: "none", 1: "train_stats", 2: "train_finalize", 3: "apply", 4: "apply_colmeans", 5: "bwd_reduce", 6: "bwd_finalize", 7: "bwd_apply", 8: "bwd_pair",
+              9: "bwd_pair_wgrad", 10: "pool_fwd", 11: "pool_bwd", 12: "pool_bwd_sums", 13: "pool_bwd_apply"}
+BN_FINALIZE_FORMS = {0: "none", 1: "row_major", 2: "cm_workgroup", 3: "cm_wave"}
+POOL_FORMS = {0: "none", 1: "element", 2: "rows", 3: "block", 4: "rows_sums", 5: "rows_apply"}
+
+
 class PackJob(C.Structure):
     _fields_ = [("w", C.c_void_p), ("out", C.c_void_p), ("cout", C.c_int32), ("cin", C.c_int32), ("kh", C.c_int32), ("kw", C.c_int32),
                 ("kw_pad", C.c_int32), ("cin_pad", C.c_int32), ("kind", C.c_int32), ("first_block", C.c_int32)]
@@ -241,6 +254,8 @@ def _load():
     lib.mvf_maxpool_bn_relu_bwd_apply.argtypes = [vp, vp, i32, i32, i32, i32, vp, fp, fp, fp, fp, fp, fp, fp, vp, i32, vp]
     lib.mvf_maxpool_bn_relu_bwd_sums.restype = i32
     lib.mvf_maxpool_bn_relu_bwd_sums.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, fp, fp, fp, fp, fp, i32, vp]
+    lib.mvf_bn_last_launch.restype = i32
+    lib.mvf_bn_last_launch.argtypes = [C.POINTER(BnLaunchInfo)]
     lib.mvf_head_train_fwd.restype = i32
     lib.mvf_head_train_fwd.argtypes = [vp, i32, i32, i32, i32, fp, fp, i32, ll, fp, fp, fp, fp, fp, fp, i32, vp]
     lib.mvf_conv2d_nhwc_fwd_mvf.restype = i32

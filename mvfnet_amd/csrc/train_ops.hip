@@ -290,7 +290,7 @@ __global__ __launch_bounds__(256) void bn_stats_finalize_kernel(int C, int nblk,
     const double d = s1 / (double)M;
     const double mean = K + d;
     double var = s2 / (double)M - d * d;
-    if (var < 0.0) var = 0.0;
+    if (var < 0.0 || M == 1) var = 0.0;          // one row: the variance IS zero (s2 - d * d would be the fp32 rounding of (z - K)^2, ~ 1e-6 against eps = 1e-5)
     const float invstd = 1.0f / sqrtf((float)var + eps);
     save_mean[c] = (float)mean;
     save_invstd[c] = invstd;
@@ -1340,6 +1340,38 @@ __global__ void head_dfeat_kernel(const float* dpool, const float* drop_mask, in
 
 inline int grid_for(long total, int cap) { return (int)std::min<long>((total + 255) / 256, cap); }      // (the max-pool launchers' grids)
 
+// Host-side record of the calling thread's last BatchNorm / max-pool call (mvf_bn_last_launch): plain host stores next to the launches, nothing on the device.
+thread_local mvf_bn_launch_info_t t_last_bn = {};
+// every entry point starts with this: a call refused before its first launch leaves entry = the entry point, launches = 0 and every form NONE
+inline void bn_rec_begin(int entry, int dtype, int mask_mode = -1) {
+    t_last_bn = mvf_bn_launch_info_t{};
+    t_last_bn.entry = entry;
+    t_last_bn.dtype = dtype;
+    t_last_bn.mask_mode = mask_mode;
+}
+// (the stores follow a launch and come before its MVF_LAUNCH_CHECK: a launch the runtime refused -- the error stays pending for that check -- is not recorded)
+inline bool bn_launched() { return hipPeekAtLastError() == hipSuccess; }
+// a column-plan launch (MVF_BN_DISPATCH*): the plan of the LAST such launch of the call stays in the record
+inline void bn_rec_plan(const ColPlan& p, int vn, bool spec) {
+    if (!bn_launched()) return;
+    mvf_bn_launch_info_t& r = t_last_bn;
+    r.vn = vn; r.cqb = p.cqb; r.rows = p.rows; r.gx = p.gx; r.gy = p.gy;
+    r.specialised = spec ? 1 : 0;
+    r.launches += 1;
+}
+inline void bn_rec_finalize(int form, int part_rows) {
+    if (!bn_launched()) return;
+    t_last_bn.finalize = form;
+    t_last_bn.part_rows = part_rows;
+    t_last_bn.launches += 1;
+}
+inline void bn_rec_pool(int form, int part_rows = 0) {
+    if (!bn_launched()) return;
+    t_last_bn.pool = form;
+    t_last_bn.part_rows = part_rows;
+    t_last_bn.launches += 1;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1359,14 +1391,17 @@ size_t mvf_bn_workspace_bytes(long m, int c) {
             using ET = float;                                                                                                \
             const ColPlan p = col_plan(m, c, 4, BLOCKS);                                                                     \
             hipLaunchKernelGGL((KERNEL<float, 4>), dim3(p.gx, p.gy), dim3(kThreads), 0, st, __VA_ARGS__);                    \
+            bn_rec_plan(p, 4, false);                                                                                        \
         } else if (WIDE_OK) {                                                                                                \
             using ET = bf16_t;                                                                                               \
             const ColPlan p = col_plan(m, c, 8, BLOCKS);                                                                     \
             hipLaunchKernelGGL((KERNEL<bf16_t, 8>), dim3(p.gx, p.gy), dim3(kThreads), 0, st, __VA_ARGS__);                   \
+            bn_rec_plan(p, 8, false);                                                                                        \
         } else {                                                                                                             \
             using ET = bf16_t;                                                                                               \
             const ColPlan p = col_plan(m, c, 4, BLOCKS);                                                                     \
             hipLaunchKernelGGL((KERNEL<bf16_t, 4>), dim3(p.gx, p.gy), dim3(kThreads), 0, st, __VA_ARGS__);                   \
+            bn_rec_plan(p, 4, false);                                                                                        \
         }                                                                                                                    \
     } while (0)
 
@@ -1377,14 +1412,17 @@ size_t mvf_bn_workspace_bytes(long m, int c) {
             using ET = float;                                                                                                \
             const ColPlan p = col_plan(m, c, 4, BLOCKS);                                                                     \
             hipLaunchKernelGGL((KERNEL<float, 4, MMV>), dim3(p.gx, p.gy), dim3(kThreads), 0, st, __VA_ARGS__);               \
+            bn_rec_plan(p, 4, true);                                                                                         \
         } else if (WIDE_OK) {                                                                                                \
             using ET = bf16_t;                                                                                               \
             const ColPlan p = col_plan(m, c, 8, BLOCKS);                                                                     \
             hipLaunchKernelGGL((KERNEL<bf16_t, 8, MMV>), dim3(p.gx, p.gy), dim3(kThreads), 0, st, __VA_ARGS__);              \
+            bn_rec_plan(p, 8, true);                                                                                         \
         } else {                                                                                                             \
             using ET = bf16_t;                                                                                               \
             const ColPlan p = col_plan(m, c, 4, BLOCKS);                                                                     \
             hipLaunchKernelGGL((KERNEL<bf16_t, 4, MMV>), dim3(p.gx, p.gy), dim3(kThreads), 0, st, __VA_ARGS__);              \
+            bn_rec_plan(p, 4, true);                                                                                         \
         }                                                                                                                    \
     } while (0)
 #define MVF_BN_DISPATCH_MM(KERNEL, MODE, WIDE_OK, BLOCKS, ...)                                \
@@ -1404,6 +1442,7 @@ static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 int mvf_bn_train_stats(const void* z, long m, int c, const float* gamma, const float* beta, float eps, float momentum,
                        float* running_mean, float* running_var, float* save_mean, float* save_invstd, float* scale,
                        float* shift, void* ws, size_t ws_bytes, int dtype, void* stream) {
+    bn_rec_begin(MVF_BN_ENTRY_TRAIN_STATS, dtype);
     MVF_REQUIRE(z && gamma && beta && save_mean && save_invstd && scale && shift && m > 0 && c > 0 && c % 4 == 0, MVF_EINVAL, "bn_train_stats: bad argument (c %% 4?)");
     MVF_REQUIRE(ws && ws_bytes >= mvf_bn_workspace_bytes(m, c), MVF_EWS, "bn_train_stats: workspace too small");
     hipStream_t st = (hipStream_t)stream;
@@ -1414,6 +1453,7 @@ int mvf_bn_train_stats(const void* z, long m, int c, const float* gamma, const f
     MVF_LAUNCH_CHECK();
     hipLaunchKernelGGL(bn_stats_finalize_kernel<0>, dim3((c + kFinCh - 1) / kFinCh), dim3(256), 0, st, c, gy, m, part, gamma, beta, eps, momentum,
                        running_mean, running_var, save_mean, save_invstd, scale, shift);
+    bn_rec_finalize(MVF_BN_FIN_ROW_MAJOR, gy);
     MVF_LAUNCH_CHECK();
     return MVF_OK;
 }
@@ -1423,6 +1463,7 @@ int mvf_bn_train_stats(const void* z, long m, int c, const float* gamma, const f
 int mvf_bn_train_finalize(const float* part, int nblk, long m, int c, const float* gamma, const float* beta, float eps,
                           float momentum, float* running_mean, float* running_var, float* save_mean, float* save_invstd,
                           float* scale, float* shift, void* stream) {
+    bn_rec_begin(MVF_BN_ENTRY_TRAIN_FINALIZE, MVF_F32);
     MVF_REQUIRE(part && gamma && beta && save_mean && save_invstd && scale && shift && nblk > 0 && m > 0 && c > 0, MVF_EINVAL, "bn_train_finalize: bad argument");
     if (nblk >= kFinLongRows)
         hipLaunchKernelGGL(bn_stats_finalize_kernel<1>, dim3(c), dim3(256), 0, (hipStream_t)stream, c, nblk, m, part, gamma, beta, eps, momentum,
@@ -1430,6 +1471,7 @@ int mvf_bn_train_finalize(const float* part, int nblk, long m, int c, const floa
     else
         hipLaunchKernelGGL(bn_stats_finalize_kernel<2>, dim3((c + 3) / 4), dim3(256), 0, (hipStream_t)stream, c, nblk, m, part, gamma, beta, eps, momentum,
                            running_mean, running_var, save_mean, save_invstd, scale, shift);
+    bn_rec_finalize(nblk >= kFinLongRows ? MVF_BN_FIN_CM_WORKGROUP : MVF_BN_FIN_CM_WAVE, nblk);
     MVF_LAUNCH_CHECK();
     return MVF_OK;
 }
@@ -1437,6 +1479,7 @@ int mvf_bn_train_finalize(const float* part, int nblk, long m, int c, const floa
 int mvf_bn_apply_bits(const void* z, long m, int c, const float* scale, const float* shift, const void* residual,
                       const float* rscale, const float* rshift, int relu, void* out, unsigned char* sign_bits, int dtype,
                       void* stream) {
+    bn_rec_begin(MVF_BN_ENTRY_APPLY, dtype);
     MVF_REQUIRE(z && scale && shift && out && m > 0 && c > 0 && c % 4 == 0, MVF_EINVAL, "bn_apply: bad argument");
     MVF_REQUIRE((rscale == nullptr) == (rshift == nullptr), MVF_EINVAL, "bn_apply: rscale/rshift must come together");
     hipStream_t st = (hipStream_t)stream;
@@ -1451,6 +1494,7 @@ int mvf_bn_apply_bits(const void* z, long m, int c, const float* scale, const fl
 // means of conv3's input for mvf_bn_train_stats_gram without a pass over it
 int mvf_bn_apply_colmeans(const void* z, long m, int c, const float* scale, const float* shift, int act, void* out, float* mean_out, void* ws, size_t ws_bytes,
                           int dtype, void* stream) {
+    bn_rec_begin(MVF_BN_ENTRY_APPLY_COLMEANS, dtype);
     MVF_REQUIRE(z && scale && shift && out && mean_out && ws && m > 0 && c > 0 && c % 8 == 0, MVF_EINVAL, "bn_apply_colmeans: bad argument (c %% 8?)");
     MVF_REQUIRE(al16(z) && al16(out), MVF_EINVAL, "bn_apply_colmeans: z / out must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
@@ -1461,6 +1505,7 @@ int mvf_bn_apply_colmeans(const void* z, long m, int c, const float* scale, cons
     MVF_BN_DISPATCH(bn_apply_cs_kernel, wide, 4096, (const ET*)z, m, c, scale, shift, act, (ET*)out, p.cqb, p.rows, part);
     MVF_LAUNCH_CHECK();
     hipLaunchKernelGGL(colmean_finalize_kernel, dim3((c + kFinCh - 1) / kFinCh), dim3(256), 0, st, c, gy, m, part, mean_out);
+    bn_rec_finalize(MVF_BN_FIN_ROW_MAJOR, gy);
     MVF_LAUNCH_CHECK();
     return MVF_OK;
 }
@@ -1473,6 +1518,7 @@ int mvf_bn_apply(const void* z, long m, int c, const float* scale, const float* 
 int mvf_bn_bwd_reduce(const void* g, int g_pitch, const void* z, const void* ymask, long m, int c, const float* mean, const float* invstd,
                       const float* scale, const float* shift, int mask_mode, void* gm_out, float* dgamma, float* dbeta,
                       void* ws, size_t ws_bytes, int dtype, void* stream) {
+    bn_rec_begin(MVF_BN_ENTRY_BWD_REDUCE, dtype, mask_mode);
     MVF_REQUIRE(g && z && mean && invstd && dgamma && dbeta && m > 0 && c > 0 && c % 4 == 0, MVF_EINVAL, "bn_bwd_reduce: bad argument");
     MVF_REQUIRE(mask_mode >= 0 && mask_mode <= 4 && ((mask_mode != 1 && mask_mode != 4) || ymask) &&
                     ((mask_mode != 2 && mask_mode != 3) || (scale && shift)) && g_pitch >= c && g_pitch % 4 == 0,
@@ -1489,16 +1535,19 @@ int mvf_bn_bwd_reduce(const void* g, int g_pitch, const void* z, const void* yma
         MVF_BN_DISPATCH(bn_bwd_reduce_kernel, wide, 2048, (const ET*)g, g_pitch, (const ET*)z, (const ET*)ymask, m, c, mean, invstd, scale, shift, mask_mode, (ET*)gm_out, p.cqb, p.rows, part);
     MVF_LAUNCH_CHECK();
     hipLaunchKernelGGL(bn_bwd_finalize_kernel<0>, dim3((c + kFinCh - 1) / kFinCh), dim3(256), 0, st, c, gy, part, dgamma, dbeta);
+    bn_rec_finalize(MVF_BN_FIN_ROW_MAJOR, gy);
     MVF_LAUNCH_CHECK();
     return MVF_OK;
 }
 
 int mvf_bn_bwd_finalize(const float* sums_part, int nblk, int c, float* dgamma, float* dbeta, void* stream) {
+    bn_rec_begin(MVF_BN_ENTRY_BWD_FINALIZE, MVF_F32);
     MVF_REQUIRE(sums_part && dgamma && dbeta && nblk > 0 && c > 0, MVF_EINVAL, "bn_bwd_finalize: bad argument");
     if (nblk >= kFinLongRows)
         hipLaunchKernelGGL(bn_bwd_finalize_kernel<1>, dim3(c), dim3(256), 0, (hipStream_t)stream, c, nblk, sums_part, dgamma, dbeta);
     else
         hipLaunchKernelGGL(bn_bwd_finalize_kernel<2>, dim3((c + 3) / 4), dim3(256), 0, (hipStream_t)stream, c, nblk, sums_part, dgamma, dbeta);
+    bn_rec_finalize(nblk >= kFinLongRows ? MVF_BN_FIN_CM_WORKGROUP : MVF_BN_FIN_CM_WAVE, nblk);
     MVF_LAUNCH_CHECK();
     return MVF_OK;
 }
@@ -1506,6 +1555,7 @@ int mvf_bn_bwd_finalize(const float* sums_part, int nblk, int c, float* dgamma, 
 int mvf_bn_bwd_apply_masked(const void* g, int g_pitch, const void* z, const void* ymask, long m, int c, const float* gamma,
                             const float* mean, const float* invstd, const float* scale, const float* shift, const float* dgamma,
                             const float* dbeta, int mask_mode, void* dz, int dtype, void* stream) {
+    bn_rec_begin(MVF_BN_ENTRY_BWD_APPLY, dtype, mask_mode);
     MVF_REQUIRE(g && z && gamma && mean && invstd && dgamma && dbeta && dz && m > 0 && c > 0 && c % 4 == 0, MVF_EINVAL, "bn_bwd_apply: bad argument");
     MVF_REQUIRE(mask_mode >= 0 && mask_mode <= 4 && ((mask_mode != 1 && mask_mode != 4) || ymask) &&
                     ((mask_mode != 2 && mask_mode != 3) || (scale && shift)) && g_pitch >= c && g_pitch % 4 == 0,
@@ -1527,6 +1577,7 @@ int mvf_bn_bwd_apply_masked(const void* g, int g_pitch, const void* z, const voi
 int mvf_bn_bwd_apply(const void* g, int g_pitch, const void* z, long m, int c, const float* gamma, const float* mean, const float* invstd,
                      const float* scale, const float* shift, const float* dgamma, const float* dbeta, int mask_mode, void* dz,
                      int dtype, void* stream) {
+    bn_rec_begin(MVF_BN_ENTRY_BWD_APPLY, dtype, mask_mode);
     MVF_REQUIRE(mask_mode == 0 || mask_mode == 2 || mask_mode == 3, MVF_EINVAL, "bn_bwd_apply: mask_mode must be 0, 2 or 3 (use mvf_bn_bwd_apply_masked)");
     return mvf_bn_bwd_apply_masked(g, g_pitch, z, nullptr, m, c, gamma, mean, invstd, scale, shift, dgamma, dbeta, mask_mode, dz, dtype, stream);
 }
@@ -1535,6 +1586,7 @@ int mvf_bn_bwd_pair(const void* g, int g_pitch, const void* z_a, const void* z_b
                     const float* gamma_a, const float* mean_a, const float* invstd_a, float* dgamma_a, float* dbeta_a,
                     const float* gamma_b, const float* mean_b, const float* invstd_b, float* dgamma_b, float* dbeta_b,
                     void* dz_a, void* dz_b, void* ws, size_t ws_bytes, int dtype, void* stream) {
+    bn_rec_begin(MVF_BN_ENTRY_BWD_PAIR, dtype, 4);
     MVF_REQUIRE(g && z_a && z_b && sign_bits && gamma_a && mean_a && invstd_a && dgamma_a && dbeta_a && gamma_b && mean_b && invstd_b && dgamma_b && dbeta_b &&
                     dz_a && dz_b && m > 0 && c > 0 && c % 4 == 0 && g_pitch >= c && g_pitch % 4 == 0, MVF_EINVAL, "bn_bwd_pair: bad argument");
     MVF_REQUIRE(ws && ws_bytes >= 2 * mvf_bn_workspace_bytes(m, c), MVF_EWS, "bn_bwd_pair: workspace too small (2 x mvf_bn_workspace_bytes)");
@@ -1549,6 +1601,7 @@ int mvf_bn_bwd_pair(const void* g, int g_pitch, const void* z_a, const void* z_b
         MVF_LAUNCH_CHECK();
         const int gA = (c + kFinCh - 1) / kFinCh;
         hipLaunchKernelGGL(bn_bwd_finalize2_kernel, dim3(2 * gA), dim3(256), 0, st, c, gy, part_a, part_b, dgamma_a, dbeta_a, dgamma_b, dbeta_b);
+        bn_rec_finalize(MVF_BN_FIN_ROW_MAJOR, gy);
         MVF_LAUNCH_CHECK();
     }
     const bool wide = c % 8 == 0 && g_pitch % 8 == 0 && al16(g) && al16(z_a) && al16(z_b) && al16(dz_a) && al16(dz_b) && ((uintptr_t)sign_bits & 1) == 0;
@@ -1601,6 +1654,7 @@ int mvf_bn_bwd_pair_wgrad(const void* g, int g_pitch, const void* z_a, const voi
                           const float* gamma_b, const float* mean_b, const float* invstd_b, float* dgamma_b, float* dbeta_b,
                           void* dz_a, void* dz_b, const void* x_a, int xa_pitch, const void* x_b, int xb_pitch, int k,
                           float* slabs_a, float* slabs_b, size_t slab_bytes, void* ws, size_t ws_bytes, int dtype, void* stream) {
+    bn_rec_begin(MVF_BN_ENTRY_BWD_PAIR_WGRAD, dtype, 4);
     MVF_REQUIRE(g && z_a && z_b && sign_bits && gamma_a && mean_a && invstd_a && dgamma_a && dbeta_a && gamma_b && mean_b && invstd_b && dgamma_b && dbeta_b &&
                     dz_a && dz_b && x_a && slabs_a && (!x_b || slabs_b) && m > 0 && c > 0 && k > 0 && g_pitch >= c && xa_pitch >= k && (!x_b || xb_pitch >= k),
                 MVF_EINVAL, "bn_bwd_pair_wgrad: bad argument");
@@ -1626,6 +1680,7 @@ int mvf_bn_bwd_pair_wgrad(const void* g, int g_pitch, const void* z_a, const voi
         MVF_LAUNCH_CHECK();
         const int gA = (c + kFinCh - 1) / kFinCh;
         hipLaunchKernelGGL(bn_bwd_finalize2_kernel, dim3(2 * gA), dim3(256), 0, st, c, gy, part_a, part_b, dgamma_a, dbeta_a, dgamma_b, dbeta_b);
+        bn_rec_finalize(MVF_BN_FIN_ROW_MAJOR, gy);
         MVF_LAUNCH_CHECK();
     }
     a.g = g; a.g_pitch = g_pitch; a.z[0] = z_a; a.z[1] = z_b; a.bits = sign_bits;
@@ -1685,6 +1740,7 @@ int mvf_wgrad_slab_reduce(const float* slabs, int nsplit, int cout, int k, float
 
 int mvf_maxpool_bn_relu_fwd(const void* z, int n, int h, int w, int c, const float* scale, const float* shift, void* y,
                             unsigned char* argmax, int dtype, void* stream) {
+    bn_rec_begin(MVF_BN_ENTRY_POOL_FWD, dtype);
     MVF_REQUIRE(z && y && scale && shift && n > 0 && h > 0 && w > 0 && c > 0 && c % 4 == 0, MVF_EINVAL, "maxpool_bn_relu_fwd: bad argument");
     const int ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1;
     const long total = (long)n * ho * wo * (c / 4);
@@ -1697,6 +1753,7 @@ int mvf_maxpool_bn_relu_fwd(const void* z, int n, int h, int w, int c, const flo
                 hipLaunchKernelGGL(maxpool_bn_fwd_blk_kernel<float>, dim3(grid_for(tb, 256 * 8)), dim3(256), 0, (hipStream_t)stream, (const float*)z, n, h, w, c, ho, wo, scale, shift, (float*)y, argmax);
             else
                 hipLaunchKernelGGL(maxpool_bn_fwd_blk_kernel<bf16_t>, dim3(grid_for(tb, 256 * 8)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)z, n, h, w, c, ho, wo, scale, shift, (bf16_t*)y, argmax);
+            bn_rec_pool(MVF_POOL_FORM_BLOCK);
             MVF_LAUNCH_CHECK();
             return MVF_OK;
         }
@@ -1705,11 +1762,13 @@ int mvf_maxpool_bn_relu_fwd(const void* z, int n, int h, int w, int c, const flo
         hipLaunchKernelGGL(maxpool_bn_fwd_kernel<float>, dim3(grid_for(total, 256 * 32)), dim3(256), 0, (hipStream_t)stream, (const float*)z, n, h, w, c, ho, wo, scale, shift, (float*)y, argmax);
     else
         hipLaunchKernelGGL(maxpool_bn_fwd_kernel<bf16_t>, dim3(grid_for(total, 256 * 32)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)z, n, h, w, c, ho, wo, scale, shift, (bf16_t*)y, argmax);
+    bn_rec_pool(MVF_POOL_FORM_ELEMENT);
     MVF_LAUNCH_CHECK();
     return MVF_OK;
 }
 
 int mvf_maxpool_bn_relu_bwd(const unsigned char* argmax, const void* g, int n, int h, int w, int c, void* ga, int dtype, void* stream) {
+    bn_rec_begin(MVF_BN_ENTRY_POOL_BWD, dtype);
     MVF_REQUIRE(argmax && g && ga && n > 0 && h > 0 && w > 0 && c > 0 && c % 4 == 0, MVF_EINVAL, "maxpool_bn_relu_bwd: bad argument");
     const int ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1;
     const long total = (long)n * h * w * (c / 4);
@@ -1718,6 +1777,7 @@ int mvf_maxpool_bn_relu_bwd(const unsigned char* argmax, const void* g, int n, i
             hipLaunchKernelGGL(maxpool_bn_bwd_rows_kernel<float>, dim3(n * h), dim3(256), 0, (hipStream_t)stream, argmax, (const float*)g, n, h, w, c, ho, wo, (float*)ga);
         else
             hipLaunchKernelGGL(maxpool_bn_bwd_rows_kernel<bf16_t>, dim3(n * h), dim3(256), 0, (hipStream_t)stream, argmax, (const bf16_t*)g, n, h, w, c, ho, wo, (bf16_t*)ga);
+        bn_rec_pool(MVF_POOL_FORM_ROWS);
         MVF_LAUNCH_CHECK();
         return MVF_OK;
     }
@@ -1725,6 +1785,7 @@ int mvf_maxpool_bn_relu_bwd(const unsigned char* argmax, const void* g, int n, i
         hipLaunchKernelGGL(maxpool_bn_bwd_kernel<float>, dim3(grid_for(total, 256 * 64)), dim3(256), 0, (hipStream_t)stream, argmax, (const float*)g, n, h, w, c, ho, wo, (float*)ga);
     else
         hipLaunchKernelGGL(maxpool_bn_bwd_kernel<bf16_t>, dim3(grid_for(total, 256 * 64)), dim3(256), 0, (hipStream_t)stream, argmax, (const bf16_t*)g, n, h, w, c, ho, wo, (bf16_t*)ga);
+    bn_rec_pool(MVF_POOL_FORM_ELEMENT);
     MVF_LAUNCH_CHECK();
     return MVF_OK;
 }
@@ -1741,6 +1802,7 @@ int mvf_maxpool_bwd_sums_rows(int n, int h) { return n > 0 && h > 0 ? (int)(((lo
 
 int mvf_maxpool_bn_relu_bwd_sums(const unsigned char* argmax, const void* g, int n, int h, int w, int c, void* ga, const void* z, const float* mean,
                                  const float* invstd, const float* scale, const float* shift, float* sums_part, int dtype, void* stream) {
+    bn_rec_begin(MVF_BN_ENTRY_POOL_BWD_SUMS, dtype, 2);
     MVF_REQUIRE(argmax && g && z && mean && invstd && scale && shift && sums_part && n > 0 && h > 0 && w > 0 && c > 0 && c % 4 == 0, MVF_EINVAL,
                 "maxpool_bn_relu_bwd_sums: bad argument");             // ga may be NULL (mvf_maxpool_bn_relu_bwd_apply re-gathers it)
     MVF_REQUIRE(256 % (c / 4) == 0 && (long)n * h < (1L << 31), MVF_EUNSUPPORTED, "maxpool_bn_relu_bwd_sums: needs c/4 to divide 256 (use the two-pass form)");
@@ -1752,6 +1814,7 @@ int mvf_maxpool_bn_relu_bwd_sums(const unsigned char* argmax, const void* g, int
         else
             hipLaunchKernelGGL((maxpool_bn_bwd_blk_kernel<bf16_t, 0>), dim3(nblk), dim3(256), 0, (hipStream_t)stream, argmax, (const bf16_t*)g, n, h, w, c, ho, wo, (bf16_t*)ga,
                                (const bf16_t*)z, nullptr, mean, invstd, scale, shift, nullptr, nullptr, 0.f, sums_part, nblk, nullptr);
+        bn_rec_pool(MVF_POOL_FORM_BLOCK, nblk);
         MVF_LAUNCH_CHECK();
         return MVF_OK;
     }
@@ -1761,6 +1824,7 @@ int mvf_maxpool_bn_relu_bwd_sums(const unsigned char* argmax, const void* g, int
     else
         hipLaunchKernelGGL(maxpool_bn_bwd_rows_sums_kernel<bf16_t>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, argmax, (const bf16_t*)g, n, h, w, c, ho, wo, (bf16_t*)ga,
                            (const bf16_t*)z, mean, invstd, scale, shift, sums_part, nblk);
+    bn_rec_pool(MVF_POOL_FORM_ROWS_SUMS, nblk);
     MVF_LAUNCH_CHECK();
     return MVF_OK;
 }
@@ -1768,6 +1832,7 @@ int mvf_maxpool_bn_relu_bwd_sums(const unsigned char* argmax, const void* g, int
 int mvf_maxpool_bn_relu_bwd_apply(const unsigned char* argmax, const void* g, int n, int h, int w, int c, const void* z, const float* gamma,
                                   const float* mean, const float* invstd, const float* scale, const float* shift, const float* dgamma,
                                   const float* dbeta, void* dz, int dtype, void* stream) {
+    bn_rec_begin(MVF_BN_ENTRY_POOL_BWD_APPLY, dtype, 2);
     MVF_REQUIRE(argmax && g && z && gamma && mean && invstd && scale && shift && dgamma && dbeta && dz && n > 0 && h > 0 && w > 0 && c > 0 && c % 4 == 0,
                 MVF_EINVAL, "maxpool_bn_relu_bwd_apply: bad argument");
     MVF_REQUIRE(256 % (c / 4) == 0 && (long)n * h < (1L << 31), MVF_EUNSUPPORTED, "maxpool_bn_relu_bwd_apply: needs c/4 to divide 256 (use the two-pass form)");
@@ -1780,6 +1845,7 @@ int mvf_maxpool_bn_relu_bwd_apply(const unsigned char* argmax, const void* g, in
         else
             hipLaunchKernelGGL((maxpool_bn_bwd_blk_kernel<bf16_t, 1>), dim3(nblk), dim3(256), 0, (hipStream_t)stream, argmax, (const bf16_t*)g, n, h, w, c, ho, wo, (bf16_t*)nullptr,
                                (const bf16_t*)z, gamma, mean, invstd, scale, shift, dgamma, dbeta, inv_m, nullptr, nblk, (bf16_t*)dz);
+        bn_rec_pool(MVF_POOL_FORM_BLOCK);
         MVF_LAUNCH_CHECK();
         return MVF_OK;
     }
@@ -1789,7 +1855,14 @@ int mvf_maxpool_bn_relu_bwd_apply(const unsigned char* argmax, const void* g, in
     else
         hipLaunchKernelGGL(maxpool_bn_bwd_rows_apply_kernel<bf16_t>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, argmax, (const bf16_t*)g, n, h, w, c, ho, wo,
                            (const bf16_t*)z, gamma, mean, invstd, scale, shift, dgamma, dbeta, inv_m, (bf16_t*)dz);
+    bn_rec_pool(MVF_POOL_FORM_ROWS_APPLY);
     MVF_LAUNCH_CHECK();
+    return MVF_OK;
+}
+
+int mvf_bn_last_launch(mvf_bn_launch_info_t* out) {
+    MVF_REQUIRE(out, MVF_EINVAL, "bn_last_launch: NULL argument");
+    *out = t_last_bn;
     return MVF_OK;
 }
 

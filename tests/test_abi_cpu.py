@@ -195,3 +195,51 @@ def test_refused_tap_gradient_calls_leave_an_empty_launch_record():
         assert lib.mvf_nhwc_tapgrad_last_launch(C.byref(info)) == 0
         assert (info.kernel, info.launches, info.nblk) == (0, 0, 0)
     assert lib.mvf_nhwc_tapgrad_last_launch(None) == -1
+
+
+@pytest.mark.cpu
+def test_refused_batchnorm_and_pool_calls_leave_a_record_that_says_so():
+    """mvf_bn_last_launch is a host-side record: every BatchNorm / max-pool entry point of csrc/train_ops.hip starts a new one, so a call refused before its first
+    launch -- checked here from host addresses that are never read -- names the entry point and reports no launch, no lane width and no kernel form."""
+    import ctypes as C
+    from mvfnet_amd import _lib
+    lib = _lib.lib
+    host = (C.c_float * 64)()
+    a = C.cast(host, C.c_void_p)
+    f = lambda v: C.c_float(v)  # noqa: E731
+    info = _lib.BnLaunchInfo()
+    assert C.sizeof(info) == 13 * 4 and len(_lib.BN_ENTRIES) == 14 and len(_lib.BN_FINALIZE_FORMS) == 4 and len(_lib.POOL_FORMS) == 6
+    EINVAL, EWS, EUNSUPPORTED = -1, -3, -5
+    nb = lib.mvf_bn_workspace_bytes(8, 8)
+    assert nb > 0 and nb % 256 == 0 and lib.mvf_bn_workspace_bytes(8, 6) == 0
+    E = {v: k for k, v in _lib.BN_ENTRIES.items()}
+    calls = (
+        ("train_stats", -1, EINVAL, lambda: lib.mvf_bn_train_stats(a, 8, 6, a, a, f(1e-5), f(0.1), a, a, a, a, a, a, a, nb, 0, None)),                 # c % 4
+        ("train_stats", -1, EWS, lambda: lib.mvf_bn_train_stats(a, 8, 8, a, a, f(1e-5), f(0.1), a, a, a, a, a, a, a, nb - 1, 0, None)),               # one byte short
+        ("train_finalize", -1, EINVAL, lambda: lib.mvf_bn_train_finalize(a, 0, 8, 8, a, a, f(1e-5), f(0.1), a, a, a, a, a, a, None)),                 # no partial rows
+        ("apply", -1, EINVAL, lambda: lib.mvf_bn_apply_bits(a, 8, 8, a, a, a, a, None, 1, a, a, 0, None)),                                              # rscale without rshift
+        ("apply", -1, EINVAL, lambda: lib.mvf_bn_apply(a, 8, 6, a, a, None, None, None, 1, a, 1, None)),
+        ("apply_colmeans", -1, EINVAL, lambda: lib.mvf_bn_apply_colmeans(a, 8, 12, a, a, 1, a, a, a, nb, 1, None)),                                   # c % 8
+        ("bwd_reduce", 1, EINVAL, lambda: lib.mvf_bn_bwd_reduce(a, 8, a, None, 8, 8, a, a, a, a, 1, None, a, a, a, nb, 0, None)),                    # mode 1 without ymask
+        ("bwd_reduce", 2, EINVAL, lambda: lib.mvf_bn_bwd_reduce(a, 8, a, None, 8, 8, a, a, None, None, 2, None, a, a, a, nb, 0, None)),              # mode 2 without scale
+        ("bwd_reduce", 0, EINVAL, lambda: lib.mvf_bn_bwd_reduce(a, 4, a, None, 8, 8, a, a, a, a, 0, None, a, a, a, nb, 0, None)),                    # g_pitch < c
+        ("bwd_reduce", 0, EWS, lambda: lib.mvf_bn_bwd_reduce(a, 8, a, None, 8, 8, a, a, a, a, 0, None, a, a, a, nb - 1, 0, None)),
+        ("bwd_finalize", -1, EINVAL, lambda: lib.mvf_bn_bwd_finalize(a, 0, 8, a, a, None)),
+        ("bwd_apply", 4, EINVAL, lambda: lib.mvf_bn_bwd_apply(a, 8, a, 8, 8, a, a, a, a, a, a, a, 4, a, 0, None)),                                    # bits need _masked
+        ("bwd_apply", 4, EINVAL, lambda: lib.mvf_bn_bwd_apply_masked(a, 8, a, None, 8, 8, a, a, a, a, a, a, a, 4, a, 0, None)),
+        ("bwd_pair", 4, EWS, lambda: lib.mvf_bn_bwd_pair(a, 8, a, a, a, 8, 8, a, a, a, a, a, a, a, a, a, a, a, a, a, 2 * nb - 1, 0, None)),
+        ("pool_fwd", -1, EINVAL, lambda: lib.mvf_maxpool_bn_relu_fwd(a, 1, 4, 4, 6, a, a, a, a, 0, None)),
+        ("pool_bwd", -1, EINVAL, lambda: lib.mvf_maxpool_bn_relu_bwd(a, a, 1, 4, 4, 8, None, 0, None)),
+        ("pool_bwd_sums", 2, EUNSUPPORTED, lambda: lib.mvf_maxpool_bn_relu_bwd_sums(a, a, 1, 4, 4, 12, a, a, a, a, a, a, a, 0, None)),                # 256 % (c / 4)
+        ("pool_bwd_apply", 2, EUNSUPPORTED, lambda: lib.mvf_maxpool_bn_relu_bwd_apply(a, a, 1, 4, 4, 12, a, a, a, a, a, a, a, a, a, 0, None)),
+    )
+    for entry, mode, rc_want, call in calls:
+        for k, _ in info._fields_:
+            setattr(info, k, 99)
+        assert call() == rc_want, (entry, lib.mvf_last_error())
+        assert lib.mvf_bn_last_launch(C.byref(info)) == 0
+        assert (info.entry, info.mask_mode) == (E[entry], mode), (entry, info.entry, info.mask_mode)
+        assert (info.launches, info.vn, info.cqb, info.rows, info.gx, info.gy, info.specialised, info.finalize, info.part_rows, info.pool) == (0,) * 10, entry
+    assert lib.mvf_bn_workspace_bytes(8, 8) == nb and lib.mvf_maxpool_bwd_sums_rows(2, 9) == 3           # plan queries leave the record alone
+    assert lib.mvf_bn_last_launch(C.byref(info)) == 0 and info.entry == E["pool_bwd_apply"]
+    assert lib.mvf_bn_last_launch(None) == -1
