@@ -607,6 +607,53 @@ int mvf_head_train_fwd_bce(const void* feat, int clips, int t, int hw, int c, co
                            const float* targets, const float* drop_mask /* (clips*t, c) pre-scaled keep mask or NULL */,
                            const float* pos_weight /* (classes) or NULL */, float target_threshold /* NaN = off */, int sum_classes,
                            float* pooled, float* scores, float* dscores, float* loss_part, float* loss, int dtype, void* stream);
+/* Focal / asymmetric sigmoid losses (csrc/focal.hip) for long-tailed multi-label data: one element function covers the sigmoid focal loss (Lin et al.;
+ * torchvision's sigmoid_focal_loss), its class-balanced form (a per-class weight) and the asymmetric loss of Ridnik et al.  scores, targets (clips, classes)
+ * fp32; class_weight (classes) fp32 or NULL (= all ones).  Settings, in a host struct read at the call (a launch plan's call record carries at most four
+ * floats): gamma_pos, gamma_neg the focusing exponents g+ / g-, margin m the probability shift of the negatives, alpha the balance (alpha < 0 = off:
+ * a+ = a- = 1; else a+ = alpha, a- = 1 - alpha), target_threshold (NaN = off), sum_classes.  Per element, with s the score, t the target, c = class_weight[k],
+ * e = exp(-|s|), p = sigmoid(s) and pn = sigmoid(-s) both formed from e (e / (1 + e) or 1 / (1 + e) by the sign of s), never as 1 - p:
+ *   t    <- (t > target_threshold) ? 1 : 0                                  -- only with the threshold on, as in mvf_bce_loss
+ *   logp  = -(max(-s, 0) + log1p(e))                                        -- log sigmoid(s)
+ *   L+    = -(pn^g+) * logp                                                 -- pn^0 := 1
+ *   pm    = (p > m) ? p - m : 0                                             -- the shifted negative probability; m = 0: pm = p
+ *   log1m = (p > m) ? log(pn + m) : 0                                       -- log(1 - pm); with m = 0 it is -(max(s, 0) + log1p(e))
+ *   L-    = -(pm^g-) * log1m                                                -- pm^0 := 1
+ *   l     = c * (a+ * t * L+ + a- * (1 - t) * L-)
+ *   dL+/ds = pn^g+ * (g+ * p * logp - pn)
+ *   dpm/ds = (p > m) ? p * pn : 0
+ *   dL-/ds = -(g- * pm^(g- - 1) * dpm/ds) * log1m + pm^g- * (dpm/ds) / (pn + m)       -- the first term is absent for g- = 0
+ *   dl/ds  = c * (a+ * t * dL+/ds + a- * (1 - t) * dL-/ds)
+ * With m = 0 the closed forms stand in: log1m as above and (dpm/ds) / pn = p (pn is zero in fp64 beyond s = 745).
+ * The loss is LINEAR IN THE TARGET, as binary cross-entropy is: for a soft (Mixup / CutMix, smoothed) target it is the expectation of the hard-label loss.
+ * This differs from the formulas as published for soft targets only: the asymmetric paper's code mixes the exponents, (1 - p_t)^(g+ t + g- (1 - t)), and
+ * torchvision mixes p_t = p t + (1 - p)(1 - t); the mixed exponent has an infinite derivative where it falls below 1, the linear form has none.  For hard
+ * targets it is torchvision's sigmoid_focal_loss (g+ = g- = gamma, m = 0, alpha) and the paper's asymmetric loss (g+ = 1, g- = 4, m = 0.05) wherever that
+ * implementation's clamp(min=1e-8) is inactive; with g+ = g- = 0, m = 0, alpha off it is mvf_bce_loss without pos_weight.  No epsilon clamp: logp and log1m
+ * are finite for every finite s.  (Parity with timm's AsymmetricLossMultiLabel and mmaction2's CBFocalLoss is claimed from the papers' formulas, not from
+ * those sources.)
+ * Reduction, precision and determinism are those of mvf_bce_loss: with D = classes (sum_classes = 0) or D = 1 (sum_classes = 1)
+ *   loss_part[i]  = sum_k l_ik / D
+ *   loss[0]       = the mean of loss_part, clips in ascending order
+ *   dscores[i][k] = (dl/ds)_ik / (clips * D), or dscores == NULL: the same loss_part and loss bits, no gradient
+ * all per-row arithmetic in fp64 from widened fp32 inputs (pow, exp, log, log1p in double), sums in a fixed order (wavefront shuffle tree, wave partials in
+ * wave order, clips ascending), every output rounded to fp32 once.  No atomics, no workspace: bit-identical from run to run.  Any classes >= 1.
+ * MVF_EINVAL, checked before any launch (nothing is enqueued, no output is touched): a NULL scores / targets / prm / loss_part / loss; clips < 1 or
+ * classes < 1; a gamma that is neither 0 nor in [1, 16]; margin outside [0, 1); alpha NaN or > 1; an infinite target_threshold; sum_classes outside {0, 1}.
+ * A NaN score or a non-finite class_weight entry makes that clip's loss_part and loss[0] NaN (a NaN score's dscores element too): the non-finite step guard
+ * then skips the step. */
+typedef struct mvf_focal_params {
+    float gamma_pos, gamma_neg, margin, alpha, target_threshold;
+    int sum_classes, reserved[2];
+} mvf_focal_params_t;
+int mvf_focal_loss(const float* scores, const float* targets, int clips, int classes, const float* class_weight /* (classes) or NULL */,
+                   const mvf_focal_params_t* prm, float* dscores /* or NULL */, float* loss_part, float* loss, void* stream);
+/* mvf_head_train_fwd_bce with the loss of mvf_focal_loss in place of the binary cross-entropy: the same pool and fc launches (pooled and scores hold the
+ * same bits), then the two loss launches.  The checks of both, before any launch; dscores is required. */
+int mvf_head_train_fwd_focal(const void* feat, int clips, int t, int hw, int c, const float* fc_w, const float* fc_b, int classes,
+                             const float* targets, const float* drop_mask /* (clips*t, c) pre-scaled keep mask or NULL */,
+                             const float* class_weight /* (classes) or NULL */, const mvf_focal_params_t* prm,
+                             float* pooled, float* scores, float* dscores, float* loss_part, float* loss, int dtype, void* stream);
 /* Knowledge distillation (Hinton's loss) behind mvf_head_train_fwd / mvf_head_train_fwd_soft, which left the cross-entropy's dscores (clips, classes),
  * loss_part (clips) and loss (1) in device memory; scores = the student's (clips, classes), teacher_scores = the teacher's, all fp32.  Per clip i, with
  * s = scores[i], z = teacher_scores[i], T = temperature, a = alpha, p = softmax(z / T), q = softmax(s / T):
@@ -1070,6 +1117,35 @@ int mvf_multilabel_record(const float* scores, const unsigned char* labels, int 
                           long long* state, void* stream);
 int mvf_multilabel_ap(const float* rec_scores, const unsigned char* rec_labels, long capacity, int classes, const long long* state, int* tp, int* nn, double* ap,
                       long long* positives, void* stream);
+/* Sample-wise AP, precision / recall / F1 counts and the best-F1 threshold per class (csrc/multilabel_f1.hip), all over slots [0, word 0) of the record
+ * above, read on the device.  A slot that holds a NaN score (a NaN row, or padding) takes part in nothing.  No atomics; integer counts, or an fp64 sum in a
+ * fixed order: bit-identical from run to run.
+ * mvf_multilabel_sample_ap: the sample-wise AP that Multi-Moments in Time reports (mmaction2's mmit_mean_average_precision), the step-wise AP taken along
+ * a row.  For row i with positives P_i:
+ *   AP_i = (1 / |P_i|) * sum_{c in P_i} TP_ic / N_ic,     N_ic = #{k : s_ik >= s_ic},     TP_ic = #{k in P_i : s_ik >= s_ic}
+ * so ties need no special case.  sample_ap fp64 (capacity), sample_positives int32 (capacity): NaN and 0 for a row without a positive and for the slots
+ * beyond word 0.  sample mAP = the mean of AP_i over the rows with at least one positive (the caller's division).  One wavefront per row: a workgroup of
+ * four wavefronts owns 64 adjacent rows and stages tiles of 64 rows x 64 classes through LDS, so that the class-major record is read along its contiguous
+ * axis; lane l counts for classes l, l + 64, .. and adds their TP / N in ascending order, a shuffle tree adds the 64 lane sums.
+ * mvf_multilabel_prf: counts (classes, 4) int64 = TP, FP, FN, TN of "row i is predicted for class c iff its recorded value >= theta_c", theta_c =
+ * thresholds[c] (device, fp32, (classes)) when given and `threshold` otherwise.  The recorded values are compared as they are (probabilities under
+ * average_clips='sigmoid').  One wavefront per class.  A NaN `threshold` with thresholds == NULL is MVF_EINVAL; a NaN entry of `thresholds` is the
+ * caller's to refuse before the upload (the kernel then predicts nothing for that class).
+ * mvf_multilabel_best_f1: behind mvf_multilabel_ap, from its tp / nn / positives.  Per class it takes the positive i that maximises
+ *   F_i = 2 * TP_i / (N_i + |P_c|)        -- the F1 of the threshold s_ic: precision TP_i / N_i, recall TP_i / |P_c|
+ * compared exactly by integer cross-multiplication in 64 bits (capacity > 2^30 is MVF_ESHAPE here); among equal F the larger score wins (equal scores
+ * have equal counts).  The maximum of F1 over ALL thresholds is attained at a positive's score -- raising a threshold to the next predicted positive drops
+ * only false positives -- so best_tp[c], best_n[c] give the class's best achievable F1 = 2 best_tp / (best_n + |P_c|) and best_threshold[c] the threshold
+ * (>=) that attains it.  A class without a positive gets 0, 0, NaN.  best_tp, best_n int32 (classes), best_threshold fp32 (classes).  One wavefront per
+ * class: lane l takes rows l, l + 64, .. in ascending order, then a shuffle tree with the same comparison.
+ * Checked before any launch, as mvf_multilabel_ap: a NULL or misaligned operand (state, sample_ap, counts, positives 8 bytes; fp32 / int32 arrays 4) is
+ * MVF_EINVAL; classes outside [1, 65535] or a capacity outside the record's range is MVF_ESHAPE. */
+int mvf_multilabel_sample_ap(const float* rec_scores, const unsigned char* rec_labels, long capacity, int classes, const long long* state, double* sample_ap,
+                             int* sample_positives, void* stream);
+int mvf_multilabel_prf(const float* rec_scores, const unsigned char* rec_labels, long capacity, int classes, const long long* state, float threshold,
+                       const float* thresholds /* (classes) or NULL */, long long* counts /* (classes, 4): TP, FP, FN, TN */, void* stream);
+int mvf_multilabel_best_f1(const float* rec_scores, const int* tp, const int* nn, const long long* positives, long capacity, int classes,
+                           const long long* state, int* best_tp, int* best_n, float* best_threshold, void* stream);
 /* Per-parameter training statistics and the diagnosis of a skipped step (csrc/layer_stats.hip): where a NaN came from and whether every layer is learning,
  * from figures that stay on the device until the host asks.
  *

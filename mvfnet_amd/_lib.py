@@ -108,6 +108,13 @@ class AdamwHyper(C.Structure):
     _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double), ("decoupled", C.c_int32)]
 
 
+class FocalParams(C.Structure):
+    """mvf_focal_params_t: the settings of mvf_focal_loss / mvf_head_train_fwd_focal, in HOST memory, read at every call (alpha < 0 and a NaN
+    target_threshold = off)."""
+    _fields_ = [("gamma_pos", C.c_float), ("gamma_neg", C.c_float), ("margin", C.c_float), ("alpha", C.c_float), ("target_threshold", C.c_float),
+                ("sum_classes", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 class LambHyper(C.Structure):
     """mvf_lamb_hyper_t: the hyper-parameters of mvf_lamb_step, doubles in HOST memory (the library rounds 1 - beta and lr_k * r_k to fp32 once)."""
     _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double), ("trust_clip", C.c_int32),
@@ -299,12 +306,22 @@ def _load():
     lib.mvf_bce_loss.argtypes = [fp, fp, i32, i32, fp, f32, i32, fp, fp, fp, vp]
     lib.mvf_head_train_fwd_bce.restype = i32
     lib.mvf_head_train_fwd_bce.argtypes = [vp, i32, i32, i32, i32, fp, fp, i32, fp, fp, fp, f32, i32, fp, fp, fp, fp, fp, i32, vp]
+    lib.mvf_focal_loss.restype = i32
+    lib.mvf_focal_loss.argtypes = [fp, fp, i32, i32, fp, C.POINTER(FocalParams), fp, fp, fp, vp]
+    lib.mvf_head_train_fwd_focal.restype = i32
+    lib.mvf_head_train_fwd_focal.argtypes = [vp, i32, i32, i32, i32, fp, fp, i32, fp, fp, fp, C.POINTER(FocalParams), fp, fp, fp, fp, fp, i32, vp]
     lib.mvf_average_clip_sigmoid.restype = i32
     lib.mvf_average_clip_sigmoid.argtypes = [fp, i32, i32, fp, vp]
     lib.mvf_multilabel_record.restype = i32
     lib.mvf_multilabel_record.argtypes = [fp, vp, i32, i32, fp, vp, C.c_long, ll, vp]
     lib.mvf_multilabel_ap.restype = i32
     lib.mvf_multilabel_ap.argtypes = [fp, vp, C.c_long, i32, ll, vp, vp, vp, ll, vp]
+    lib.mvf_multilabel_sample_ap.restype = i32
+    lib.mvf_multilabel_sample_ap.argtypes = [fp, vp, C.c_long, i32, ll, vp, vp, vp]
+    lib.mvf_multilabel_prf.restype = i32
+    lib.mvf_multilabel_prf.argtypes = [fp, vp, C.c_long, i32, ll, f32, fp, ll, vp]
+    lib.mvf_multilabel_best_f1.restype = i32
+    lib.mvf_multilabel_best_f1.argtypes = [fp, vp, vp, ll, C.c_long, i32, ll, vp, vp, fp, vp]
     lib.mvf_head_train_bwd.restype = i32
     lib.mvf_head_train_bwd.argtypes = [fp, fp, fp, fp, i32, i32, i32, i32, i32, fp, fp, fp, vp, i32, vp]
     lib.mvf_conv2d_wgrad_workspace_bytes.restype = sz

@@ -233,6 +233,11 @@ int bce_check(const char* who, const float* scores, const float* targets, int cl
               const float* loss);
 int bce_launch(const float* scores, const float* targets, int clips, int classes, const float* pos_weight, float threshold, int sum_classes, float* dscores,
                float* loss_part, float* loss, hipStream_t st);
+// focal / asymmetric sigmoid losses (focal.hip): the same pair for mvf_focal_loss and mvf_head_train_fwd_focal
+int focal_check(const char* who, const float* scores, const float* targets, int clips, int classes, const mvf_focal_params_t* prm, const float* loss_part,
+                const float* loss);
+int focal_launch(const float* scores, const float* targets, int clips, int classes, const float* class_weight, const mvf_focal_params_t& prm, float* dscores,
+                 float* loss_part, float* loss, hipStream_t st);
 }
 
 #ifdef __HIPCC__

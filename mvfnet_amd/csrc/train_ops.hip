@@ -2008,6 +2008,29 @@ int mvf_head_train_fwd_bce(const void* feat, int clips, int t, int hw, int c, co
     return mvf_internal::bce_launch(scores, targets, clips, classes, pos_weight, target_threshold, sum_classes, dscores, loss_part, loss, st);
 }
 
+// mvf_head_train_fwd_bce with the focal / asymmetric loss of mvf_focal_loss (focal.hip) in place of the binary cross-entropy: the same frame_pool_kernel and
+// head_fc_seg_kernel launches, so pooled and scores hold the same bits.  Every argument is checked before the first launch; prm is read here, on the host.
+int mvf_head_train_fwd_focal(const void* feat, int clips, int t, int hw, int c, const float* fc_w, const float* fc_b, int classes,
+                             const float* targets, const float* drop_mask, const float* class_weight, const mvf_focal_params_t* prm,
+                             float* pooled, float* scores, float* dscores, float* loss_part, float* loss, int dtype, void* stream) {
+    MVF_REQUIRE(clips > 0 && t > 0 && hw > 0 && c > 0 && classes > 0, MVF_EINVAL, "head_train_fwd_focal: bad argument (clips=%d t=%d hw=%d c=%d classes=%d)",
+                clips, t, hw, c, classes);
+    MVF_REQUIRE(dtype == MVF_F32 || dtype == MVF_BF16, MVF_EINVAL, "head_train_fwd_focal: dtype %d", dtype);
+    MVF_REQUIRE((size_t)c * sizeof(float) <= 160 * 1024, MVF_EUNSUPPORTED, "head_train_fwd_focal: c=%d does not fit the LDS feature buffer", c);
+    MVF_REQUIRE((long)clips * t <= 65535, MVF_ESHAPE, "head_train_fwd_focal: %d x %d frames exceed the grid", clips, t);
+    MVF_REQUIRE(feat && fc_w && pooled && dscores, MVF_EINVAL, "head_train_fwd_focal: NULL argument");
+    const int rc = mvf_internal::focal_check("head_train_fwd_focal", scores, targets, clips, classes, prm, loss_part, loss);
+    if (rc != MVF_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    dim3 g((c + 255) / 256, clips * t);
+    if (dtype == MVF_F32) hipLaunchKernelGGL(frame_pool_kernel<float>, g, dim3(256), 0, st, (const float*)feat, hw, c, drop_mask, pooled);
+    else hipLaunchKernelGGL(frame_pool_kernel<bf16_t>, g, dim3(256), 0, st, (const bf16_t*)feat, hw, c, drop_mask, pooled);
+    MVF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(head_fc_seg_kernel, dim3(clips, kHeadSplit), dim3(256), (size_t)c * sizeof(float), st, pooled, fc_w, fc_b, clips, t, c, classes, scores);
+    MVF_LAUNCH_CHECK();
+    return mvf_internal::focal_launch(scores, targets, clips, classes, class_weight, *prm, dscores, loss_part, loss, st);
+}
+
 int mvf_ce_loss_soft(const float* scores, const float* targets, int clips, int classes, float* dscores, float* loss_part, float* loss, void* stream) {
     MVF_REQUIRE(clips > 0 && classes > 0, MVF_EINVAL, "ce_loss_soft: bad argument (clips=%d classes=%d)", clips, classes);
     MVF_REQUIRE(scores && targets && loss_part && loss, MVF_EINVAL, "ce_loss_soft: NULL argument");

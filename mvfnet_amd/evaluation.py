@@ -109,6 +109,110 @@ def mean_average_precision(scores, labels):
     return float(np.mean(ap[positives > 0])) if (positives > 0).any() else float("nan")
 
 
+def _multilabel_inputs(who, scores, labels):
+    s = np.asarray(scores, dtype=np.float64)
+    y = np.asarray(labels) != 0
+    if s.ndim != 2 or y.shape != s.shape:
+        raise ValueError("%s: scores %s and labels %s must be two (videos, classes) matrices" % (who, s.shape, y.shape))
+    return s, y, ~np.isnan(s).any(axis=1)
+
+
+def sample_average_precision(scores, labels):
+    """Per-VIDEO step-wise average precision: average_precision taken along a row, AP_i = (1 / |P_i|) * sum_{c in P_i} TP_ic / N_ic with
+    N_ic = #{k : s_ik >= s_ic} and TP_ic = #{k in P_i : s_ik >= s_ic}.  Returns (ap float64 (videos,), NaN for a row without a positive and for a row
+    holding a NaN score; positives int64 (videos,), 0 for such a row).  What csrc/multilabel_f1.hip computes on the device."""
+    s, y, keep = _multilabel_inputs("sample_average_precision", scores, labels)
+    ap, positives = np.full(s.shape[0], np.nan), np.zeros(s.shape[0], dtype=np.int64)
+    if keep.any():
+        ap[keep], positives[keep] = average_precision(s[keep].T, y[keep].T)
+    return ap, positives
+
+
+def mmit_mean_average_precision(scores, labels):
+    """The sample-wise mAP Multi-Moments in Time reports (mmaction2's mmit_mean_average_precision): the mean of sample_average_precision over the videos
+    with at least one positive; nan when no video has one."""
+    ap, positives = sample_average_precision(scores, labels)
+    return float(np.mean(ap[positives > 0])) if (positives > 0).any() else float("nan")
+
+
+def prf_from_counts(counts):
+    """Precision / recall / F1 from (classes, 4) integer counts TP, FP, FN, TN.  Conventions: a ratio whose denominator is 0 is 0 (precision of a class
+    never predicted, recall of a class without a positive, F1 = 2TP / (2TP + FP + FN) of a class with neither); micro_* come from the counts summed over
+    the classes; macro_f1 is the mean of the per-class F1 over the classes with at least one positive (TP + FN > 0), nan when there is none."""
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1, 4)
+    tp, fp, fn = (counts[:, i].astype(np.float64) for i in range(3))
+
+    def ratio(a, b):
+        return np.divide(a, b, out=np.zeros_like(np.asarray(a, dtype=np.float64)), where=np.asarray(b) > 0)
+    f1 = ratio(2.0 * tp, 2.0 * tp + fp + fn)
+    have = (counts[:, 0] + counts[:, 2]) > 0
+    stp, sfp, sfn = tp.sum(), fp.sum(), fn.sum()
+    return dict(counts=counts, precision=ratio(tp, tp + fp), recall=ratio(tp, tp + fn), f1=f1,
+                micro_precision=float(ratio(stp, stp + sfp)), micro_recall=float(ratio(stp, stp + sfn)), micro_f1=float(ratio(2.0 * stp, 2.0 * stp + sfp + sfn)),
+                macro_f1=float(np.mean(f1[have])) if have.any() else float("nan"))
+
+
+def precision_recall_f1(scores, labels, threshold=None, thresholds=None):
+    """Counts and precision / recall / F1 of "video i is predicted for class c iff s_ic >= theta_c", theta_c = thresholds[c] when given (one per class),
+    else `threshold`; the thresholds are rounded to fp32, as the device path takes them (metrics.DeviceMultiLabelMetrics.compute(threshold=...)).  Rows
+    holding a NaN score are left out.  Returns the dict of prf_from_counts (its conventions hold)."""
+    s, y, keep = _multilabel_inputs("precision_recall_f1", scores, labels)
+    th = check_thresholds("precision_recall_f1", threshold, thresholds, s.shape[1]).astype(np.float64)
+    s, y = s[keep], y[keep]
+    pred = s >= th[None, :]
+    counts = np.stack([(pred & y).sum(axis=0), (pred & ~y).sum(axis=0), (~pred & y).sum(axis=0), (~pred & ~y).sum(axis=0)], axis=1).astype(np.int64)
+    return prf_from_counts(counts)
+
+
+def check_thresholds(who, threshold, thresholds, classes):
+    """Exactly one of threshold (a number) / thresholds (one number per class), none NaN -> a float32 (classes,) array."""
+    if (threshold is None) == (thresholds is None):
+        raise ValueError("%s: give either threshold or thresholds" % who)
+    if thresholds is None:
+        if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)) or threshold != threshold:
+            raise ValueError("%s: threshold must be a number, not NaN, got %r" % (who, threshold))
+        return np.full(classes, threshold, dtype=np.float32)
+    th = np.asarray(thresholds, dtype=np.float32).reshape(-1)
+    if th.shape[0] != classes or np.isnan(th).any():
+        raise ValueError("%s: thresholds must hold %d numbers, none NaN, got %r" % (who, classes, thresholds))
+    return th
+
+
+def best_f1_from_counts(best_tp, best_n, positives):
+    """dict(best_f1 (classes,) = 2 TP / (N + |P_c|), NaN for a class without a positive; macro_best_f1 = its mean over the classes with one)."""
+    tp, n, p = (np.asarray(a, dtype=np.float64).reshape(-1) for a in (best_tp, best_n, positives))
+    f = np.full(tp.shape[0], np.nan)
+    have = p > 0
+    f[have] = 2.0 * tp[have] / (n[have] + p[have])
+    return dict(best_f1=f, macro_best_f1=float(np.mean(f[have])) if have.any() else float("nan"))
+
+
+def best_f1_thresholds(scores, labels):
+    """Per class, the threshold (>=) with the best achievable F1.  The maximum over all thresholds is attained at a positive's score (raising a threshold
+    to the next predicted positive drops only false positives), so the candidates are the positives i of the class, with F_i = 2 TP_i / (N_i + |P_c|)
+    from average_precision's counts; fractions are compared exactly and ties go to the larger score.  Rows holding a NaN score are left out.  Returns
+    dict(best_f1, best_threshold (NaN for a class without a positive), best_tp, best_n, positives, macro_best_f1)."""
+    from fractions import Fraction
+    s, y, keep = _multilabel_inputs("best_f1_thresholds", scores, labels)
+    s, y = s[keep], y[keep]
+    n, classes = s.shape
+    positives = y.sum(axis=0).astype(np.int64)
+    best_tp, best_n, best_th = np.zeros(classes, dtype=np.int64), np.zeros(classes, dtype=np.int64), np.full(classes, np.nan)
+    for c in range(classes):
+        if positives[c] == 0:
+            continue
+        order = np.argsort(s[:, c], kind="stable")
+        sc, yc = s[order, c], y[order, c]
+        first = np.searchsorted(sc, sc[yc], side="left")
+        below = np.concatenate(([0], np.cumsum(yc)))
+        tp, nn, sp = positives[c] - below[first], n - first, sc[yc]
+        f = 2.0 * tp / (nn + positives[c])
+        cand = np.nonzero(f >= f.max() * (1.0 - 1e-12))[0]          # the float picks the few candidates, the exact comparison the winner
+        k = max(cand, key=lambda i: (Fraction(int(tp[i]), int(nn[i] + positives[c])), sp[i]))
+        best_tp[c], best_n[c], best_th[c] = tp[k], nn[k], sp[k]
+    return dict(best_threshold=best_th, best_tp=best_tp, best_n=best_n, positives=positives, **best_f1_from_counts(best_tp, best_n, positives))
+
+
 WEIGHTS = ("live", "ema", "both")
 
 
@@ -199,9 +303,12 @@ class EvalMeanAPHook(EvalTopKAccuracyHook):
     """EvalTopKAccuracyHook for multi-label data: after every `interval`-th training epoch, score the validation set and log 'mAP' (mean_average_precision;
     'ema mAP' for the averaged weights).  labels: the (videos, classes) multi-hot matrix.  on_device = True: the pass is runner.device_test into a
     metrics.DeviceMultiLabelMetrics -- no score row leaves the device, the ranks' records are merged by all_gather() and ONE read ends the pass; it needs one
-    score row per video (test_cfg.average_clips 'sigmoid', 'prob' or 'score')."""
+    score row per video (test_cfg.average_clips 'sigmoid', 'prob' or 'score').
+    sample_map = True adds 'sample mAP' (mmit_mean_average_precision: the sample-wise mAP of Multi-Moments in Time); f1_threshold = a number adds 'micro F1'
+    and 'macro F1' of "predicted iff the score >= f1_threshold" (precision_recall_f1 and its conventions; the scores are compared as the model returns
+    them, probabilities under average_clips='sigmoid').  Both on either path, with the 'ema ' prefix as 'mAP'; without them the result is what it was."""
 
-    def __init__(self, loader, labels, interval=1, weights="live", on_device=False):
+    def __init__(self, loader, labels, interval=1, weights="live", on_device=False, sample_map=False, f1_threshold=None):
         if weights not in WEIGHTS:
             raise ValueError("weights must be one of %s, got %r" % (", ".join(map(repr, WEIGHTS)), weights))
         lab = np.asarray(labels)
@@ -209,6 +316,9 @@ class EvalMeanAPHook(EvalTopKAccuracyHook):
             raise ValueError("EvalMeanAPHook: labels must be a (videos, classes) multi-hot matrix, got shape %s" % (lab.shape,))
         self.loader, self.labels, self.interval, self.weights = loader, (lab != 0).astype(np.uint8), interval, weights
         self.on_device = bool(on_device)
+        if f1_threshold is not None:
+            check_thresholds("EvalMeanAPHook", f1_threshold, None, 1)
+        self.sample_map, self.f1_threshold = bool(sample_map), f1_threshold
         self._metrics, self._share = None, None
         self.history = []
 
@@ -222,7 +332,13 @@ class EvalMeanAPHook(EvalTopKAccuracyHook):
         if results is None:                          # not rank 0
             return None
         rows = np.stack([np.asarray(r).squeeze() for r in results])
-        return {"%smAP" % prefix: mean_average_precision(rows, self.labels[:len(rows)])}
+        out = {"%smAP" % prefix: mean_average_precision(rows, self.labels[:len(rows)])}
+        if self.sample_map:
+            out["%ssample mAP" % prefix] = mmit_mean_average_precision(rows, self.labels[:len(rows)])
+        if self.f1_threshold is not None:
+            fig = precision_recall_f1(rows, self.labels[:len(rows)], threshold=self.f1_threshold)
+            out["%smicro F1" % prefix], out["%smacro F1" % prefix] = fig["micro_f1"], fig["macro_f1"]
+        return out
 
     def _score_on_device(self, runner, prefix):
         from .dist import get_dist_info
@@ -244,10 +360,15 @@ class EvalMeanAPHook(EvalTopKAccuracyHook):
         runner.model.train(was_training)
         if world > 1:
             self._metrics.all_gather()
-        fig = self._metrics.compute()                # every rank holds the figures; rank 0 reports them
+        fig = self._metrics.compute(sample_ap=self.sample_map, threshold=self.f1_threshold)      # every rank holds the figures; rank 0 reports them
         if get_dist_info()[0] != 0:
             return None
-        return {"%smAP" % prefix: float(fig["mAP"])}
+        out = {"%smAP" % prefix: float(fig["mAP"])}
+        if self.sample_map:
+            out["%ssample mAP" % prefix] = float(fig["sample_mAP"])
+        if self.f1_threshold is not None:
+            out["%smicro F1" % prefix], out["%smacro F1" % prefix] = float(fig["micro_f1"]), float(fig["macro_f1"])
+        return out
 
 
 class PreciseBNHook(object):

@@ -1,3 +1,3 @@
-from .tsn_clshead import TSNClsHead
+from .tsn_clshead import TSNClsHead, class_balanced_weights
 
-__all__ = ["TSNClsHead"]
+__all__ = ["TSNClsHead", "class_balanced_weights"]

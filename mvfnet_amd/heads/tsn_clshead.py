@@ -20,14 +20,95 @@ import torch.nn as nn
 from ..builder import HEADS
 
 
-LOSS_TYPES = ("CrossEntropyLoss", "BCELossWithLogits")
+LOSS_TYPES = ("CrossEntropyLoss", "BCELossWithLogits", "SigmoidFocalLoss", "CBFocalLoss", "AsymmetricLossMultiLabel")
 BCE_KEYS = ("type", "pos_weight", "target_threshold", "sum_classes")
+# the focal family (csrc/focal.hip): one element function, three ways to name its settings
+FOCAL_KEYS = {"SigmoidFocalLoss": ("type", "gamma", "alpha", "class_weight", "target_threshold", "sum_classes"),
+              "AsymmetricLossMultiLabel": ("type", "gamma_neg", "gamma_pos", "clip", "class_weight", "target_threshold", "sum_classes"),
+              "CBFocalLoss": ("type", "samples_per_cls", "beta", "gamma", "alpha", "sum_classes")}
+
+
+def class_balanced_weights(samples_per_cls, beta=0.9999):
+    """The class-balanced weights of Cui et al. ("Class-Balanced Loss Based on Effective Number of Samples"): w_k = (1 - beta) / (1 - beta ** n_k), formed in
+    fp64 and normalised so that they sum to the number of classes; a float64 numpy array.  Every n_k an integer >= 1, 0 <= beta < 1 (beta = 0: all ones).
+    In CBFocalLoss the weight multiplies COLUMN k of the loss matrix: the project's own definition -- Cui et al. weight a sample by the class of its single
+    label, which is undefined with several labels per row."""
+    import numpy as np
+    if isinstance(beta, bool) or not isinstance(beta, numbers.Real) or not 0.0 <= beta < 1.0:
+        raise ValueError("class_balanced_weights: beta must lie in [0, 1), got %r" % (beta,))
+    try:
+        raw = list(samples_per_cls)
+    except TypeError:
+        raise ValueError("class_balanced_weights: samples_per_cls must be a sequence of integers >= 1, got %r" % (samples_per_cls,))
+    if not raw or any(isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 1 for v in raw):
+        raise ValueError("class_balanced_weights: samples_per_cls must be a non-empty sequence of integers >= 1, got %r" % (samples_per_cls,))
+    n = np.asarray([int(v) for v in raw], dtype=np.float64)
+    w = (1.0 - float(beta)) / (1.0 - np.power(float(beta), n))
+    return w * (len(raw) / w.sum())
+
+
+def _gamma(name, v):
+    if isinstance(v, bool) or not isinstance(v, numbers.Real) or not (v == 0 or 1.0 <= v <= 16.0):
+        raise ValueError("TSNClsHead: loss_cls %s must be 0 or lie in [1, 16], got %r" % (name, v))
+    return float(v)
+
+
+def _check_focal(kind, cfg, num_classes):
+    keys = FOCAL_KEYS[kind]
+    unknown = sorted(k for k in cfg.keys() if k not in keys)
+    if unknown:
+        raise ValueError("TSNClsHead: loss_cls %s: unknown key %s (known: %s)" % (kind, ", ".join(map(repr, unknown)), ", ".join(keys)))
+    alpha, margin, cw = None, 0.0, cfg.get("class_weight")
+    if kind == "AsymmetricLossMultiLabel":
+        gp, gn = _gamma("gamma_pos", cfg.get("gamma_pos", 1.0)), _gamma("gamma_neg", cfg.get("gamma_neg", 4.0))
+        clip = cfg.get("clip", 0.05)
+        if clip is not None:
+            if isinstance(clip, bool) or not isinstance(clip, numbers.Real) or not 0.0 <= clip < 1.0:
+                raise ValueError("TSNClsHead: loss_cls clip must be None or lie in [0, 1), got %r" % (clip,))
+            margin = float(clip)
+    else:
+        gp = gn = _gamma("gamma", cfg.get("gamma", 2.0))
+        alpha = cfg.get("alpha", 0.25 if kind == "SigmoidFocalLoss" else None)
+        if alpha is not None:
+            if isinstance(alpha, bool) or not isinstance(alpha, numbers.Real) or not 0.0 <= alpha <= 1.0:
+                raise ValueError("TSNClsHead: loss_cls alpha must be None or lie in [0, 1], got %r" % (alpha,))
+            alpha = float(alpha)
+    if kind == "CBFocalLoss":
+        if "samples_per_cls" not in cfg.keys():
+            raise ValueError("TSNClsHead: loss_cls CBFocalLoss needs samples_per_cls, %d integers >= 1" % num_classes)
+        try:
+            w = class_balanced_weights(cfg["samples_per_cls"], cfg.get("beta", 0.9999))
+        except ValueError as e:
+            raise ValueError("TSNClsHead: loss_cls CBFocalLoss: %s" % e)
+        if len(w) != num_classes:
+            raise ValueError("TSNClsHead: loss_cls samples_per_cls holds %d entries for num_classes=%d" % (len(w), num_classes))
+        cw = tuple(float(v) for v in w)
+    elif cw is not None:
+        try:
+            cw = tuple(float(v) for v in cw)
+        except (TypeError, ValueError):
+            raise ValueError("TSNClsHead: loss_cls class_weight must be None or a sequence of %d numbers, got %r" % (num_classes, cfg.get("class_weight")))
+        if len(cw) != num_classes:
+            raise ValueError("TSNClsHead: loss_cls class_weight holds %d entries for num_classes=%d" % (len(cw), num_classes))
+    thr, sc = cfg.get("target_threshold"), cfg.get("sum_classes", False)
+    if thr is not None:
+        if isinstance(thr, bool) or not isinstance(thr, numbers.Real) or thr != thr or thr in (float("inf"), float("-inf")):
+            raise ValueError("TSNClsHead: loss_cls target_threshold must be None or a finite number, got %r" % (thr,))
+        thr = float(thr)
+    if not isinstance(sc, bool):
+        raise ValueError("TSNClsHead: loss_cls sum_classes must be a bool, got %r" % (sc,))
+    return dict(kind="focal", type=kind, gamma_pos=gp, gamma_neg=gn, margin=margin, alpha=alpha, class_weight=cw, target_threshold=thr, sum_classes=sc)
 
 
 def check_loss_cls(cfg, num_classes):
     """loss_cls of the head: None / dict(type='CrossEntropyLoss') -> None (softmax cross-entropy, the default), or
     dict(type='BCELossWithLogits', pos_weight=None | sequence of num_classes numbers, target_threshold=None | finite float, sum_classes=False) -> a dict
-    with the three settings (pos_weight a tuple of floats or None).  Any other type raises NotImplementedError; an unknown key or a bad value ValueError."""
+    with the three settings (pos_weight a tuple of floats or None), or one of the focal family (csrc/focal.hip; the arithmetic is in include/mvfnet_hip.h):
+      dict(type='SigmoidFocalLoss', gamma=2.0, alpha=0.25 | None, class_weight=None, target_threshold=None, sum_classes=False)
+      dict(type='AsymmetricLossMultiLabel', gamma_neg=4.0, gamma_pos=1.0, clip=0.05, class_weight=None, target_threshold=None, sum_classes=False)
+      dict(type='CBFocalLoss', samples_per_cls=[...], beta=0.9999, gamma=2.0, alpha=None, sum_classes=False)      -- class_weight = class_balanced_weights
+    -> a dict with kind='focal' and gamma_pos, gamma_neg, margin, alpha, class_weight (a tuple or None), target_threshold, sum_classes.
+    Any other type raises NotImplementedError; an unknown key or a bad value ValueError."""
     if cfg is None:
         return None
     if not hasattr(cfg, "keys") or "type" not in cfg.keys():
@@ -40,6 +121,8 @@ def check_loss_cls(cfg, num_classes):
         if extra:
             raise ValueError("TSNClsHead: loss_cls CrossEntropyLoss takes no options here, got %s" % ", ".join(map(repr, extra)))
         return None
+    if kind in FOCAL_KEYS:
+        return _check_focal(kind, cfg, num_classes)
     unknown = sorted(k for k in cfg.keys() if k not in BCE_KEYS)
     if unknown:
         raise ValueError("TSNClsHead: loss_cls BCELossWithLogits: unknown key %s (known: %s)" % (", ".join(map(repr, unknown)), ", ".join(BCE_KEYS)))
@@ -68,6 +151,8 @@ class TSNClsHead(nn.Module):
         super().__init__()
         self.loss_cls = check_loss_cls(loss_cls, num_classes)
         self._pos_weight_dev = None
+        self._class_weight_dev = None
+        self._focal_params = None
         if isinstance(label_smooth_eps, bool) or not isinstance(label_smooth_eps, numbers.Real) or not 0.0 <= label_smooth_eps < 1.0:
             raise ValueError("TSNClsHead: label_smooth_eps must lie in [0, 1) (got %r)" % (label_smooth_eps,))
         self.label_smooth_eps = float(label_smooth_eps)
@@ -93,12 +178,13 @@ class TSNClsHead(nn.Module):
     def _apply(self, fn, *a, **k):
         self._engine = None
         self._pos_weight_dev = None
+        self._class_weight_dev = None
         return super()._apply(fn, *a, **k)
 
     def bce_settings(self, device):
         """None for the default loss; else (pos_weight, target_threshold, sum_classes) as mvf_bce_loss takes them: a persistent fp32 device tensor (uploaded
         once per device) or None, a float with NaN = off, 0 / 1."""
-        if self.loss_cls is None:
+        if self.loss_cls is None or self.loss_cls.get("kind") == "focal":
             return None
         pw = None
         if self.loss_cls["pos_weight"] is not None:
@@ -107,6 +193,26 @@ class TSNClsHead(nn.Module):
                 pw = self._pos_weight_dev = torch.tensor(self.loss_cls["pos_weight"], dtype=torch.float32, device=device)
         thr = self.loss_cls["target_threshold"]
         return pw, float("nan") if thr is None else thr, int(self.loss_cls["sum_classes"])
+
+    def focal_settings(self, device):
+        """None unless loss_cls is one of the focal family; else (class_weight, params) as mvf_focal_loss takes them: a persistent fp32 device tensor
+        (uploaded once per device) or None, and the _lib.FocalParams struct (host memory, built once: it is immutable for the head's life -- a launch
+        plan records its address; other settings need another head)."""
+        if self.loss_cls is None or self.loss_cls.get("kind") != "focal":
+            return None
+        cw = None
+        if self.loss_cls["class_weight"] is not None:
+            cw, dev = self._class_weight_dev, torch.device(device)
+            if cw is None or cw.device.type != dev.type or (dev.index is not None and cw.device.index != dev.index):
+                cw = self._class_weight_dev = torch.tensor(self.loss_cls["class_weight"], dtype=torch.float32, device=device)
+        if self._focal_params is None:
+            from .._lib import FocalParams
+            lc = self.loss_cls
+            self._focal_params = FocalParams(gamma_pos=lc["gamma_pos"], gamma_neg=lc["gamma_neg"], margin=lc["margin"],
+                                             alpha=-1.0 if lc["alpha"] is None else lc["alpha"],
+                                             target_threshold=float("nan") if lc["target_threshold"] is None else lc["target_threshold"],
+                                             sum_classes=int(lc["sum_classes"]))
+        return cw, self._focal_params
 
     def load_state_dict(self, *a, **k):
         self._engine = None
@@ -148,22 +254,23 @@ class TSNClsHead(nn.Module):
         labels: integers (B,) / (B, 1), or a floating-point (B, num_classes) matrix of soft labels (mvf_ce_loss_soft).  In training mode integer labels are
         smoothed with label_smooth_eps (mvf_soft_targets) as mmaction's head does.
         With loss_cls = BCELossWithLogits the loss is mvf_bce_loss against a target matrix: a bool / uint8 / floating-point (B, num_classes) matrix as it
-        is (multi-hot labels), integer labels through mvf_soft_targets."""
+        is (multi-hot labels), integer labels through mvf_soft_targets.  With one of the focal family (SigmoidFocalLoss, CBFocalLoss,
+        AsymmetricLossMultiLabel) the same, through mvf_focal_loss."""
         import ctypes as C
         from .._lib import check, lib
         if not cls_score.is_cuda:
             raise RuntimeError("TSNClsHead.loss: mvfnet_amd runs on MI355X tensors only; no CPU fallback (tests use oracle/)")
         s = cls_score.detach().to(torch.float32).contiguous()
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        bce = self.bce_settings(s.device)
-        if bce is not None and labels.dtype in (torch.bool, torch.uint8) and labels.dim() == 2 and tuple(labels.shape) == tuple(s.shape):
+        bce, focal = self.bce_settings(s.device), self.focal_settings(s.device)
+        if (bce is not None or focal is not None) and labels.dtype in (torch.bool, torch.uint8) and labels.dim() == 2 and tuple(labels.shape) == tuple(s.shape):
             labels = labels.to(torch.float32)                # multi-hot labels
         soft = labels.is_floating_point() and labels.dim() == 2 and tuple(labels.shape) == tuple(s.shape)
         eps = self.label_smooth_eps if self.training else 0.0
         if soft and eps > 0.0:
             raise ValueError("TSNClsHead.loss: soft (B, num_classes) labels are taken as they are; label_smooth_eps needs integer labels")
-        if bce is not None:
-            # loss_cls = BCELossWithLogits: always against a target matrix -- the caller's (multi-hot or soft), or mvf_soft_targets' one-hot / smoothed one
+        if bce is not None or focal is not None:
+            # loss_cls = BCELossWithLogits or one of the focal family: always against a target matrix -- the caller's (multi-hot or soft), or mvf_soft_targets' one-hot / smoothed one
             P = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
             if soft:
                 tgt = labels.detach().to(device=s.device, dtype=torch.float32).contiguous()
@@ -175,6 +282,10 @@ class TSNClsHead(nn.Module):
                 check(lib.mvf_soft_targets(P(lab), None, None, s.shape[0], s.shape[1], C.c_float(eps), P(tgt), stream), "mvf_soft_targets")
             part = torch.empty(s.shape[0], dtype=torch.float32, device=s.device)
             out = torch.empty(1, dtype=torch.float32, device=s.device)
+            if focal is not None:
+                cw, prm = focal
+                check(lib.mvf_focal_loss(P(s), P(tgt), s.shape[0], s.shape[1], P(cw), prm, None, P(part), P(out), stream), "mvf_focal_loss")
+                return dict(loss_cls=out.reshape(()))
             pw, thr, sum_classes = bce
             check(lib.mvf_bce_loss(P(s), P(tgt), s.shape[0], s.shape[1], P(pw), C.c_float(thr), sum_classes, None, P(part), P(out), stream), "mvf_bce_loss")
             return dict(loss_cls=out.reshape(()))

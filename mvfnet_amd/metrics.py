@@ -248,18 +248,60 @@ class DeviceMultiLabelMetrics(object):
         dist.all_gather(sts, self.state)
         self.merge(list(zip(scs, lbs, sts)))
 
-    def compute(self, strict=True):
+    def compute(self, strict=True, sample_ap=False, threshold=None, thresholds=None, best_f1=False):
         """The one synchronising call: dict(mAP, ap (num_classes,) float64 with NaN where a class has no positive, positives (num_classes,) int64,
-        classes_with_positives, rows, nan_rows, overflow).  strict=True raises RuntimeError when rows did not fit the record."""
-        tp = torch.empty((self.num_classes, self.capacity), dtype=torch.int32, device=self.device)
-        nn = torch.empty((self.num_classes, self.capacity), dtype=torch.int32, device=self.device)
-        ap = torch.empty(self.num_classes, dtype=torch.float64, device=self.device)
-        positives = torch.empty(self.num_classes, dtype=torch.int64, device=self.device)
+        classes_with_positives, rows, nan_rows, overflow).  strict=True raises RuntimeError when rows did not fit the record.
+        Each option adds keys (csrc/multilabel_f1.hip; evaluation.py holds the same definitions in numpy); the defaults return exactly the dict above.
+          sample_ap=True            sample_mAP (the sample-wise mAP of Multi-Moments in Time: the mean of the per-row AP over the rows with at least one
+                                    positive, nan if none), sample_ap (slots,) float64 with NaN for such a row, rows_with_positives
+          threshold= / thresholds=  a number, or one per class (none NaN): "predicted iff the recorded value >= it" (the values are compared as recorded:
+                                    probabilities under average_clips='sigmoid').  counts (num_classes, 4) int64 = TP, FP, FN, TN; per-class precision,
+                                    recall, f1; micro_precision, micro_recall, micro_f1, macro_f1.  Conventions (evaluation.prf_from_counts): a ratio with a
+                                    zero denominator is 0 -- f1 = 2TP / (2TP + FP + FN) --, macro_f1 is the mean over the classes with at least one positive
+          best_f1=True              best_f1, best_threshold (num_classes,): the best achievable F1 of each class and the threshold (>=) that attains it, a
+                                    positive's score, ties to the larger score, NaN for a class without a positive; macro_best_f1 over the classes with one"""
+        from .evaluation import best_f1_from_counts, check_thresholds, prf_from_counts
+        dev, i32 = self.device, torch.int32
+        stream = torch.cuda.current_stream(self.state.device).cuda_stream
+        th = None
+        if threshold is not None or thresholds is not None:
+            th = check_thresholds("DeviceMultiLabelMetrics.compute", threshold, thresholds, self.num_classes)
+        tp = torch.empty((self.num_classes, self.capacity), dtype=i32, device=dev)
+        nn = torch.empty((self.num_classes, self.capacity), dtype=i32, device=dev)
+        ap = torch.empty(self.num_classes, dtype=torch.float64, device=dev)
+        positives = torch.empty(self.num_classes, dtype=torch.int64, device=dev)
         _lib.check(_lib.lib.mvf_multilabel_ap(self.rec_scores.data_ptr(), self.rec_labels.data_ptr(), self.capacity, self.num_classes, self.state.data_ptr(),
-                                              tp.data_ptr(), nn.data_ptr(), ap.data_ptr(), positives.data_ptr(),
-                                              torch.cuda.current_stream(self.state.device).cuda_stream), "multilabel_ap")
+                                              tp.data_ptr(), nn.data_ptr(), ap.data_ptr(), positives.data_ptr(), stream), "multilabel_ap")
         self._pairs = (tp, nn)
-        return figures_from_ap(ap.cpu().numpy(), positives.cpu().numpy(), self.state.cpu().numpy(), strict)
+        if sample_ap:
+            s_ap = torch.empty(self.capacity, dtype=torch.float64, device=dev)
+            s_pos = torch.empty(self.capacity, dtype=i32, device=dev)
+            _lib.check(_lib.lib.mvf_multilabel_sample_ap(self.rec_scores.data_ptr(), self.rec_labels.data_ptr(), self.capacity, self.num_classes,
+                                                         self.state.data_ptr(), s_ap.data_ptr(), s_pos.data_ptr(), stream), "multilabel_sample_ap")
+        if th is not None:
+            counts = torch.empty((self.num_classes, 4), dtype=torch.int64, device=dev)
+            th_d = None if thresholds is None else torch.from_numpy(th).to(dev)
+            _lib.check(_lib.lib.mvf_multilabel_prf(self.rec_scores.data_ptr(), self.rec_labels.data_ptr(), self.capacity, self.num_classes, self.state.data_ptr(),
+                                                   C.c_float(float(th[0])), None if th_d is None else th_d.data_ptr(), counts.data_ptr(), stream), "multilabel_prf")
+        if best_f1:
+            b_tp, b_n = torch.empty(self.num_classes, dtype=i32, device=dev), torch.empty(self.num_classes, dtype=i32, device=dev)
+            b_th = torch.empty(self.num_classes, dtype=torch.float32, device=dev)
+            _lib.check(_lib.lib.mvf_multilabel_best_f1(self.rec_scores.data_ptr(), tp.data_ptr(), nn.data_ptr(), positives.data_ptr(), self.capacity,
+                                                       self.num_classes, self.state.data_ptr(), b_tp.data_ptr(), b_n.data_ptr(), b_th.data_ptr(), stream),
+                       "multilabel_best_f1")
+        state = self.state.cpu().numpy()
+        positives_h = positives.cpu().numpy()
+        out = figures_from_ap(ap.cpu().numpy(), positives_h, state, strict)
+        if sample_ap:
+            slots = int(min(max(state[_lib.MULTILABEL_SLOTS], 0), self.capacity))
+            sa, sp = s_ap.cpu().numpy()[:slots], s_pos.cpu().numpy()[:slots]
+            have = sp > 0
+            out.update(sample_mAP=float(np.mean(sa[have])) if have.any() else float("nan"), sample_ap=sa, rows_with_positives=int(have.sum()))
+        if th is not None:
+            out.update(prf_from_counts(counts.cpu().numpy()))
+        if best_f1:
+            out.update(best_f1_from_counts(b_tp.cpu().numpy(), b_n.cpu().numpy(), positives_h), best_threshold=b_th.cpu().numpy())
+        return out
 
     def pairs(self):
         """(tp, nn, slots): the int32 (num_classes, capacity) device arrays of TP_i and N_i the last compute() made (0 / 0 for a row that is no positive of

@@ -166,10 +166,13 @@ class Recognizer2D(nn.Module):
             eng.bce = self.cls_head.bce_settings(eng.device)
         else:
             eng.bce = None
+        # the focal family (SigmoidFocalLoss, CBFocalLoss, AsymmetricLossMultiLabel): bce_settings is None for it, and focal_settings for everything else
+        focal = getattr(self.cls_head, "focal_settings", None)
+        eng.focal = focal(eng.device) if focal is not None and getattr(self.cls_head, "loss_cls", None) is not None else None
 
     def forward_train(self, imgs, labels, **kwargs):
         """imgs [B, T, 3, H, W], labels [B, 1] -> {'loss_cls': scalar tensor} (reference recognizer2d.py:132-149).
-        labels may also be a floating-point (B, num_classes) matrix of soft labels -- or, with the head's loss_cls = BCELossWithLogits, a bool / uint8
+        labels may also be a floating-point (B, num_classes) matrix of soft labels -- or, with the head's loss_cls = BCELossWithLogits or one of the focal family, a bool / uint8
         (B, num_classes) matrix of multi-hot labels.  While self.training, train_cfg['erasing'] (RandomErasing),
         train_cfg['blending'] (Mixup / CutMix) and the head's label_smooth_eps are applied on the device (mvfnet_amd/erasing.py, mvfnet_amd/blending.py).
         The returned loss supports .backward(): gradients land in the parameters' .grad (copies of the engine's flat gradient
@@ -197,7 +200,7 @@ class Recognizer2D(nn.Module):
         eng.trainable_offset()
         eng.input_pipeline, eng.input_window = getattr(self, "input_pipeline", None), kwargs.get("window")
         self._set_soft_options(eng, self.training)
-        if eng.bce is not None and torch.is_tensor(labels) and labels.dtype in (torch.bool, torch.uint8) and labels.dim() == 2 \
+        if (eng.bce is not None or eng.focal is not None) and torch.is_tensor(labels) and labels.dtype in (torch.bool, torch.uint8) and labels.dim() == 2 \
                 and tuple(labels.shape) == (imgs.shape[0], self.cls_head.num_classes):
             # multi-hot labels: the fp32 target matrix is made HERE, in front of the engine's recorded region (a torch op inside it is dropped on replay)
             labels = labels.to(device=imgs.device, dtype=torch.float32)

@@ -1967,6 +1967,11 @@ class TrainEngine(_ParamStore):
         # labels), and mvf_head_train_fwd_bce stands where mvf_head_train_fwd_soft stood.  Part of the plan key, appended only when set: with None the key,
         # the allocations and the launches are what they were.
         self.bce = None
+        # Focal / asymmetric sigmoid head (TSNClsHead(loss_cls=dict(type='SigmoidFocalLoss' | 'CBFocalLoss' | 'AsymmetricLossMultiLabel', ...)).focal_settings:
+        # (class_weight device tensor | None, _lib.FocalParams host struct); None = off).  Everything said of `bce` holds: the target-matrix path, with
+        # mvf_head_train_fwd_focal in that place.  The struct's address is a frozen word of a recorded call (the recorder keeps the struct alive with the
+        # plan), so the struct is never written after it is built: other settings are another struct, and every setting's value is part of the plan key.
+        self.focal = None
 
     def _pack_all(self, kind):
         """All forward (kind 0) or data-gradient (kind 1) weight packs in ONE launch (mvf_pack_conv_weights_batched); the job
@@ -2173,12 +2178,12 @@ class TrainEngine(_ParamStore):
     def _soft_labels(self, imgs, labels):
         """The caller hands the (B, num_classes) soft-label matrix itself (floating point) instead of integer labels."""
         matrix = labels.dim() == 2 and tuple(labels.shape) == (imgs.shape[0], self.num_classes)
-        if self.bce is not None and matrix and labels.dtype in (torch.bool, torch.uint8):
-            return True                  # multi-hot labels under the BCE head: _step_tensors widens them to fp32, outside any recorded region
+        if (self.bce is not None or self.focal is not None) and matrix and labels.dtype in (torch.bool, torch.uint8):
+            return True                  # multi-hot labels under the BCE / focal head: _step_tensors widens them to fp32, outside any recorded region
         return labels.is_floating_point() and matrix
 
     def _uses_soft_head(self, lab):
-        return self.blending is not None or self.label_smooth_eps > 0.0 or lab.is_floating_point() or self.bce is not None
+        return self.blending is not None or self.label_smooth_eps > 0.0 or lab.is_floating_point() or self.bce is not None or self.focal is not None
 
     def set_options(self, lr=None, momentum=None, weight_decay=None, max_norm=None, dtype=None, optimizer=None, betas=None, eps=None, trust_clip=None,
                     always_adapt=None):
@@ -2269,7 +2274,12 @@ class TrainEngine(_ParamStore):
                 targets = self.buf("soft_targets", (b, self.num_classes), f32)
                 check(lib.mvf_soft_targets(_p(lab), _p(rows_d), _p(wts_d), b, self.num_classes, C.c_float(self.label_smooth_eps), _p(targets), _st()),
                       "soft_targets")
-            if self.bce is not None:
+            if self.focal is not None:
+                class_weight, prm = self.focal
+                check(lib.mvf_head_train_fwd_focal(_p(xcur), b, t, hc * wc, cc, _p(self.fc_w), _p(self.fc_b), self.num_classes, _p(targets), _p(mask),
+                                                   _p(class_weight), prm, _p(pooled), _p(scores), _p(dscores), _p(loss_part), _p(loss), self.dt, _st()),
+                      "head fwd (focal)")
+            elif self.bce is not None:
                 pos_weight, thr, sum_classes = self.bce
                 check(lib.mvf_head_train_fwd_bce(_p(xcur), b, t, hc * wc, cc, _p(self.fc_w), _p(self.fc_b), self.num_classes, _p(targets), _p(mask),
                                                  _p(pos_weight), C.c_float(thr), sum_classes, _p(pooled), _p(scores), _p(dscores), _p(loss_part), _p(loss),
@@ -2433,6 +2443,7 @@ class TrainEngine(_ParamStore):
     # (mvf_plan_run); MVF_POLICY=plan=0 keeps every step on the Python launch sequence
     use_plan = _policy("plan", 1) != 0
     plan_warmup = 2          # eager steps before the first recording (buffers and workspaces reach their final sizes in the first two)
+    focal = None             # (the class default of the instance attribute __init__ sets: None is no plan-key switch, see _switch_names)
 
     def _plan_key(self, imgs, labels):
         """None = this step cannot run from a plan; else what a plan is valid for."""
@@ -2455,7 +2466,11 @@ class TrainEngine(_ParamStore):
                     # erasing off: the key of every existing configuration is what it was.  The table's width is a frozen integer word of the recorded call.
                     (("erasing", int(self.erasing.max_boxes)),) if self.erasing is not None else ()) + (
                     # the loss kind and its three settings (the threshold and sum_classes are frozen words of the recorded call, pos_weight a frozen address)
-                    (("bce", self.bce[0].data_ptr() if self.bce[0] is not None else 0, repr(float(self.bce[1])), int(self.bce[2])),) if self.bce is not None else ())
+                    (("bce", self.bce[0].data_ptr() if self.bce[0] is not None else 0, repr(float(self.bce[1])), int(self.bce[2])),) if self.bce is not None else ()) + (
+                    # the focal family: the struct's address is a frozen word too, so its identity and every value it holds join the key
+                    (("focal", self.focal[0].data_ptr() if self.focal[0] is not None else 0, C.addressof(self.focal[1])) + tuple(
+                        repr(float(getattr(self.focal[1], k))) for k in ("gamma_pos", "gamma_neg", "margin", "alpha", "target_threshold")) + (
+                            int(self.focal[1].sum_classes),),) if self.focal is not None else ())
 
     def _record_step(self, imgs, labels, prepared):
         """One eager step with every library call and stream ordering recorded; returns (loss, Plan | None)."""
