@@ -675,6 +675,55 @@ int mvf_head_train_fwd_focal(const void* feat, int clips, int t, int hw, int c, 
 int mvf_distill_loss(const float* scores, const float* teacher_scores, int clips, int classes, float temperature, float alpha,
                      float* dscores /* in/out */, float* loss_part /* in/out */, float* loss /* out */, float* terms /* out, 2 floats, or NULL */,
                      void* stream);
+/* Temporal-relation head (csrc/trn_head.hip): TSNClsHead with consensus 'TRN' / 'TRNmultiscale' (Zhou et al., "Temporal Relational Reasoning in Videos";
+ * the reference's segmental_consensuses/relation_consensus.py).  feat (clips * t, hw, c) in `dtype`; everything else fp32.  2 <= t <= MVF_TRN_MAX_FRAMES.
+ * Scale index i (0 <= i < n_scales <= t - 1) is the s_i = t - i frame relation; its operands, one mvf_trn_scale_t of a HOST array read at the call:
+ *   w1 (hidden, s_i * fdim), b1 (hidden), w2 (classes, hidden), b2 (classes) and, for the backward, the gradient destinations dw1, db1, dw2, db2.
+ * 'TRN' is n_scales = 1 (hidden 512 in the reference), 'TRNmultiscale' n_scales = t - 1 (hidden 256); fdim is new_fc's output width (256).
+ * table: int32 (rows, 1 + t) in DEVICE memory, one relation per row: scale_index, then the s_i frame indices of the relation, then -1 padding.  The kernels
+ * clamp scale_index into [0, n_scales) and every frame index into [0, t): a bad table cannot read outside a tensor (refusing bad tables is the caller's job:
+ * mvfnet_amd.heads.relation.check_relation_table).
+ * mvf_trn_head_fwd, 5 launches whatever `rows` is (the hidden GEMM runs as up to MVF_TRN_KSPLIT_MAX K splits into hpart and a reduce over them in ascending order):
+ *   pooled[n][ch]   = (mean over hw of feat[n][.][ch]) * drop_mask[n][ch]              (clips * t, c); drop_mask the pre-scaled keep mask or NULL
+ *   f[n][d]         = fc_w[d] . pooled[n] + fc_b[d]                                    (clips * t, fdim); fc_b may be NULL
+ *   h[r][i][j]      = relu(w1_s[j] . relu(concat_{p < s} f[i * t + frame_r(p)]) + b1_s[j])   (rows, clips, hidden), s the scale of row r
+ *   scores[i][k]    = sum over r = 0 .. rows - 1, in that order, of (w2_s[k] . h[r][i] + b2_s[k])   (clips, classes): b2_s counts once per row
+ * mvf_trn_head_bwd, 7 launches whatever `rows` is, from dscores (clips, classes) and the forward's pooled, f, h:
+ *   dw2_s[k][j]     = sum over the rows of scale s in table order, clips ascending, of dscores[i][k] * h[r][i][j];   db2_s[k] the same sum of dscores[i][k]
+ *   dh[r][i][j]     = [h[r][i][j] > 0] * sum_k dscores[i][k] * w2_s[k][j]
+ *   dw1_s[j][q]     = the same row / clip sum of dh[r][i][j] * relu(f[i * t + frame_r(q / fdim)][q % fdim]);           db1_s[j] the same sum of dh[r][i][j]
+ *   df[n][d]        = [f[n][d] > 0] * sum over the rows that hold frame n % t, in table order (a gather, no scatter), of sum_j dh[r][i][j] * w1_s[j][p * fdim + d]
+ *   dfc_w[d][ch]    = sum over the frames ascending of df[n][d] * pooled[n][ch];   dfc_b[d] the same sum of df[n][d]
+ *   dpool[n][ch]    = (sum_d df[n][d] * fc_w[d][ch]) / hw * drop_mask[n][ch]       (clips * t, c) workspace
+ *   dfeat[n][.][ch] = dpool[n][ch], rounded once to `dtype`
+ * A scale without a row in the table gets zero gradients.  Every sum is taken in fp32 in a fixed order: one accumulator per output element, or a fixed number of
+ * partial sums (the K splits of the hidden GEMM; 8 interleaved accumulators and four quarters of the reduction in dh, df, dfc_w, dpool) combined in a fixed tree,
+ * rows in table order.  No atomics, no counters: bit-identical from run to run.  Any clips >= 1, classes >= 1, hw >= 1; c a multiple of 4 (as mvf_head_train_bwd).
+ * Checked before any launch: MVF_EINVAL (a NULL argument, a size < 1, a dtype, n_scales outside [1, t - 1], a NULL operand of a scale), MVF_EUNSUPPORTED (t outside
+ * [2, MVF_TRN_MAX_FRAMES]), MVF_ESHAPE (c % 4, clips * t > 65535, classes / hidden / fdim > 65535, rows > 1024, dpool not 16-byte aligned, dfeat not 16-byte (fp32) / 8-byte (bf16) aligned).
+ * hpart: a workspace of MVF_TRN_KSPLIT_MAX * rows * clips * hidden floats.
+ * mvf_trn_head_last_launch: the calling thread's last call of the two (a host-side record): a refused call leaves launches = 0. */
+#define MVF_TRN_MAX_FRAMES 16
+#define MVF_TRN_KSPLIT_MAX 8
+typedef struct mvf_trn_scale {
+    const float *w1, *b1, *w2, *b2;
+    float *dw1, *db1, *dw2, *db2;
+} mvf_trn_scale_t;
+enum { MVF_TRN_ENTRY_NONE = 0, MVF_TRN_ENTRY_FWD = 1, MVF_TRN_ENTRY_BWD = 2 };
+typedef struct mvf_trn_launch_info {
+    int32_t entry;                        /* MVF_TRN_ENTRY_*                                                                                  */
+    int32_t dtype;
+    int32_t rows, n_scales;               /* 0 after a refused call                                                                           */
+    int32_t launches;                     /* kernel launches the call made: 5 (forward) / 7 (backward)                                        */
+} mvf_trn_launch_info_t;
+int mvf_trn_head_fwd(const void* feat, int clips, int t, int hw, int c, const float* fc_w, const float* fc_b, int fdim, const mvf_trn_scale_t* scales,
+                     int n_scales, int hidden, int classes, const int* table, int rows, const float* drop_mask /* (clips*t, c) or NULL */, float* pooled,
+                     float* f, float* h, float* hpart /* workspace */, float* scores, int dtype, void* stream);
+int mvf_trn_head_bwd(const float* dscores, const float* pooled, const float* f, const float* h, const float* fc_w, const mvf_trn_scale_t* scales, int n_scales,
+                     int hidden, int classes, const int* table, int rows, const float* drop_mask /* (clips*t, c) or NULL */, int clips, int t, int hw, int c,
+                     int fdim, float* dfc_w, float* dfc_b, float* dh /* (rows, clips, hidden) */, float* df /* (clips*t, fdim) */, float* dpool /* (clips*t, c) */,
+                     void* dfeat, int dtype, void* stream);
+int mvf_trn_head_last_launch(mvf_trn_launch_info_t* out);
 /* RandomErasing (timm's, as PySlowFast and mmaction2 use it) on the stem operand, IN PLACE.  xp = (planes, hp, wp, 4) in `dtype` as mvf_stem_prep lays it
  * out, 16-byte aligned; no plane reads another plane.  One table per step, three DEVICE arrays:
  *   boxes int32  (planes, max_boxes, 5): y0, x0, y1, x1, mode -- a half-open box in image pixels (before the pad), 0 <= y0 <= y1 <= H, 0 <= x0 <= x1 <= W;

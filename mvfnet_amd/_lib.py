@@ -115,6 +115,20 @@ class FocalParams(C.Structure):
                 ("sum_classes", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+TRN_MAX_FRAMES, TRN_KSPLIT_MAX = 16, 8
+
+
+class TrnScale(C.Structure):
+    """mvf_trn_scale_t: the operands of one relation scale of mvf_trn_head_fwd / mvf_trn_head_bwd (device addresses), in a HOST array read at every call."""
+    _fields_ = [("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p),
+                ("dw1", C.c_void_p), ("db1", C.c_void_p), ("dw2", C.c_void_p), ("db2", C.c_void_p)]
+
+
+class TrnLaunchInfo(C.Structure):
+    """mvf_trn_launch_info_t: the calling thread's last mvf_trn_head_fwd / mvf_trn_head_bwd call (host-side record)."""
+    _fields_ = [("entry", C.c_int32), ("dtype", C.c_int32), ("rows", C.c_int32), ("n_scales", C.c_int32), ("launches", C.c_int32)]
+
+
 class LambHyper(C.Structure):
     """mvf_lamb_hyper_t: the hyper-parameters of mvf_lamb_step, doubles in HOST memory (the library rounds 1 - beta and lr_k * r_k to fp32 once)."""
     _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double), ("trust_clip", C.c_int32),
@@ -310,6 +324,12 @@ def _load():
     lib.mvf_focal_loss.argtypes = [fp, fp, i32, i32, fp, C.POINTER(FocalParams), fp, fp, fp, vp]
     lib.mvf_head_train_fwd_focal.restype = i32
     lib.mvf_head_train_fwd_focal.argtypes = [vp, i32, i32, i32, i32, fp, fp, i32, fp, fp, fp, C.POINTER(FocalParams), fp, fp, fp, fp, fp, i32, vp]
+    lib.mvf_trn_head_fwd.restype = i32
+    lib.mvf_trn_head_fwd.argtypes = [vp, i32, i32, i32, i32, fp, fp, i32, C.POINTER(TrnScale), i32, i32, i32, vp, i32, fp, fp, fp, fp, fp, fp, i32, vp]
+    lib.mvf_trn_head_bwd.restype = i32
+    lib.mvf_trn_head_bwd.argtypes = [fp, fp, fp, fp, fp, C.POINTER(TrnScale), i32, i32, i32, vp, i32, fp, i32, i32, i32, i32, i32, fp, fp, fp, fp, fp, vp, i32, vp]
+    lib.mvf_trn_head_last_launch.restype = i32
+    lib.mvf_trn_head_last_launch.argtypes = [C.POINTER(TrnLaunchInfo)]
     lib.mvf_average_clip_sigmoid.restype = i32
     lib.mvf_average_clip_sigmoid.argtypes = [fp, i32, i32, fp, vp]
     lib.mvf_multilabel_record.restype = i32

@@ -344,12 +344,51 @@ class HeadEngine(object):
 
     KINDS = {None: 0, "score": 1, "prob": 2}
 
-    def __init__(self, fc, device):
+    def __init__(self, fc, device, relation=None, relation_type=None):
         """fc: the head's nn.Linear.  Its parameters are read at EVERY call (fp32 contiguous GPU parameters are used in place, no
         copy): a training engine re-points them at its flat buffer and updates them in place, so a cached copy would score with
-        stale weights after the first optimizer step."""
+        stale weights after the first optimizer step.
+        relation / relation_type: the head's segmental_consensus module (heads/relation.py) and 'TRN' | 'TRNmultiscale': scores() then runs the
+        temporal-relation head (mvf_trn_head_fwd) behind fc, whose rows are the 256 frame features instead of the classes."""
         self.fc, self.device = fc, device
         self.classes, self.c = fc.weight.shape
+        self.relation, self.relation_type = relation, relation_type
+        if relation is not None:
+            self.fdim, self.classes = self.classes, relation.num_class
+
+    def relation_operands(self, grads=None):
+        """-> (the _lib.TrnScale host array of the relation head's scales, the tensors it points into -- keep them alive until the launches are queued).  The
+        parameters are read at every call, as w / b are.  grads: a function parameter -> its gradient destination (the backward), or None."""
+        from .heads.relation import scale_operands
+        return scale_operands(self.relation, lambda p: p.detach().to(device=self.device, dtype=torch.float32).contiguous(), grads)
+
+    def upload_relations(self, relations, num_seg):
+        """The step's relation table on the device: `relations` checked (heads/relation.check_relation_table), or this forward's draw from numpy's global
+        generator -- the reference samples in eval mode too."""
+        from .heads.relation import check_relation_table, draw_relation_table
+        table = draw_relation_table(self.relation_type, num_seg) if relations is None else relations
+        table = check_relation_table(table, self.relation_type, num_seg)
+        return torch.from_numpy(table).to(self.device), int(table.shape[0])
+
+    def relation_forward(self, feat, num_seg, table_d, rows, mask=None, out=None):
+        """mvf_trn_head_fwd on channels-last features (nt, h, w, c) -> dict(pooled, f, h, scores): every stage's stored output (the backward's inputs)."""
+        nt, h, w, c = feat.shape
+        if c != self.c or nt % num_seg or num_seg != self.relation.num_frames:
+            raise ValueError("head: features %s do not match in_channels=%d / num_frames=%d (num_seg=%d)" % (tuple(feat.shape), self.c, self.relation.num_frames, num_seg))
+        clips, hidden, f32 = nt // num_seg, self.relation.num_bottleneck, torch.float32
+        pooled = torch.empty(nt, c, dtype=f32, device=feat.device)
+        fbuf = torch.empty(nt, self.fdim, dtype=f32, device=feat.device)
+        hbuf = torch.empty(rows, clips, hidden, dtype=f32, device=feat.device)
+        hpart = torch.empty(_lib.TRN_KSPLIT_MAX, rows, clips, hidden, dtype=f32, device=feat.device)      # the hidden GEMM's K-split workspace
+        if out is None:
+            out = torch.empty(clips, self.classes, dtype=f32, device=feat.device)
+        elif tuple(out.shape) != (clips, self.classes) or out.dtype != f32 or not out.is_contiguous() or out.device != feat.device:
+            raise ValueError("head: the score buffer %s %s does not match (%d, %d) float32" % (tuple(out.shape), out.dtype, clips, self.classes))
+        wgt, bias = self.w, self.b
+        arr, keep = self.relation_operands()
+        check(lib.mvf_trn_head_fwd(_p(feat), clips, num_seg, h * w, c, _p(wgt), _p(bias), self.fdim, arr, len(arr), hidden, self.classes, _p(table_d), rows,
+                                   _p(mask), _p(pooled), _p(fbuf), _p(hbuf), _p(hpart), _p(out), _DT[feat.dtype], _stream()), "mvf_trn_head_fwd")
+        return dict(pooled=pooled, f=fbuf, h=hbuf, scores=out)
 
     @property
     def w(self):
@@ -359,8 +398,14 @@ class HeadEngine(object):
     def b(self):
         return self.fc.bias.detach().to(device=self.device, dtype=torch.float32).contiguous() if self.fc.bias is not None else None
 
-    def scores(self, feat, num_seg, out=None):
-        """(clips, classes) fp32 scores; out: a contiguous fp32 buffer of that shape to write them into (a train engine's persistent one)."""
+    def scores(self, feat, num_seg, out=None, relations=None):
+        """(clips, classes) fp32 scores; out: a contiguous fp32 buffer of that shape to write them into (a train engine's persistent one).
+        relations (relation heads only): the int32 (R, 1 + T) table to evaluate instead of this call's draw."""
+        if self.relation is not None:
+            table_d, rows = self.upload_relations(relations, num_seg)
+            return self.relation_forward(feat, num_seg, table_d, rows, out=out)["scores"]
+        if relations is not None:
+            raise ValueError("head: relations= is an argument of the 'TRN' / 'TRNmultiscale' heads")
         return self._pool_fc(feat, num_seg, out)[1]
 
     def features(self, feat, num_seg):

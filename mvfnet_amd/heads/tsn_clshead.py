@@ -11,6 +11,16 @@ SURVEY.md 2.2 measured 1e-5), which is how the HIP head kernel computes them in 
 
 extract_feat=True (the reference's feature_extractor.py entry point; tsn_clshead.py:89-90, :110-112): eval-mode forward returns that mean
 itself, (clips, in_channels) fp32, for both branches; in training mode it is refused.
+
+consensus_cfg=dict(type='TRN' | 'TRNmultiscale', num_frames=T) (tsn_clshead.py:39-44, :63-67; heads/relation.py): the temporal-relation head.  new_fc is
+Linear(in_channels, 256), `segmental_consensus` the reference's RelationModule / RelationModuleMultiScale tree (same state_dict keys), and forward is pool ->
+(dropout) -> new_fc -> per relation relu(W1 relu(concat f) + b1) -> sum of (W2 h + b2) over the step's relations, in the HIP kernels of csrc/trn_head.hip.  The
+relations of the scales below T are drawn per forward from numpy's global generator, in training AND in eval, as the reference does.
+DIVERGENCE from the reference: its head passes in_channels as the relation module's img_feature_dim while new_fc emits 256 features per frame, so with
+in_channels != 256 its RelationModule.forward raises ("shape '[4, 16384]' is invalid for input of size 8192"); it runs only at in_channels == 256.  This head
+builds the relation module with img_feature_dim = 256 whatever in_channels is: at in_channels == 256 the module tree and the numbers are the reference
+head's, otherwise those of the reference's RelationModule / RelationModuleMultiScale classes constructed with 256.  init_weights touches new_fc only, as the
+reference does.  2 <= T <= 16.  fcn_testing / extract_feat and consensus_cfg keys other than type / num_frames are refused with ValueError.
 """
 import numbers
 
@@ -18,6 +28,7 @@ import torch
 import torch.nn as nn
 
 from ..builder import HEADS
+from .relation import IMG_FEATURE_DIM, RELATION_TYPES, check_num_frames, return_TRN
 
 
 LOSS_TYPES = ("CrossEntropyLoss", "BCELossWithLogits", "SigmoidFocalLoss", "CBFocalLoss", "AsymmetricLossMultiLabel")
@@ -156,19 +167,41 @@ class TSNClsHead(nn.Module):
         if isinstance(label_smooth_eps, bool) or not isinstance(label_smooth_eps, numbers.Real) or not 0.0 <= label_smooth_eps < 1.0:
             raise ValueError("TSNClsHead: label_smooth_eps must lie in [0, 1) (got %r)" % (label_smooth_eps,))
         self.label_smooth_eps = float(label_smooth_eps)
-        if spatial_type != "avg" or consensus_cfg.get("type") != "avg" or consensus_cfg.get("dim", 1) != 1:
-            raise NotImplementedError("TSNClsHead: only spatial_type='avg' with the 'avg' consensus over dim 1 is built "
-                                      "(the MVFNet configuration)")
+        relation = consensus_cfg.get("type") in RELATION_TYPES
+        if spatial_type != "avg" or not (relation or (consensus_cfg.get("type") == "avg" and consensus_cfg.get("dim", 1) == 1)):
+            raise NotImplementedError("TSNClsHead: only spatial_type='avg' with the 'avg' consensus over dim 1 (the MVFNet configuration) or the "
+                                      "'TRN' / 'TRNmultiscale' relation consensus is built")
         if with_avg_pool or temporal_feature_size != 1 or spatial_feature_size != 1:
             raise NotImplementedError("TSNClsHead: with_avg_pool / feature sizes != 1 are not built")
         self.spatial_type, self.spatial_size = spatial_type, spatial_size
-        self.consensus_type = "avg"
+        self.consensus_type = consensus_cfg["type"] if relation else "avg"
         self.dropout_ratio, self.in_channels, self.num_classes, self.init_std = dropout_ratio, in_channels, num_classes, init_std
         self.dropout = nn.Dropout(p=dropout_ratio) if dropout_ratio != 0 else None
-        self.new_fc = nn.Linear(in_channels, num_classes)
+        if relation:
+            # Every refusal before a module is built, let alone a launch.  The reference's fcn_testing branch would load new_fc's 256 rows into a num_classes
+            # Conv3d, and its extract_feat branch skips new_fc: neither is a configuration of the relation head.
+            unknown = sorted(k for k in consensus_cfg.keys() if k not in ("type", "num_frames"))
+            if unknown:
+                raise ValueError("TSNClsHead: consensus_cfg %s: unknown key %s (known: 'type', 'num_frames')" % (self.consensus_type, ", ".join(map(repr, unknown))))
+            if "num_frames" not in consensus_cfg.keys():
+                raise ValueError("TSNClsHead: consensus_cfg %s needs num_frames (the recognizer's n_segment)" % self.consensus_type)
+            self.num_frames = check_num_frames(self.consensus_type, consensus_cfg["num_frames"])
+            if fcn_testing:
+                raise ValueError("TSNClsHead: fcn_testing=True is not a configuration of the %s relation head" % self.consensus_type)
+            if extract_feat:
+                raise ValueError("TSNClsHead: extract_feat=True is not a configuration of the %s relation head" % self.consensus_type)
+            # img_feature_dim = 256 = what new_fc emits, NOT in_channels as the reference passes (see the module docstring)
+            self.segmental_consensus = return_TRN(self.consensus_type, IMG_FEATURE_DIM, self.num_frames, num_classes)
+            self.new_fc = nn.Linear(in_channels, IMG_FEATURE_DIM)
+        else:
+            self.new_fc = nn.Linear(in_channels, num_classes)
         self.fcn_testing = fcn_testing
         self.extract_feat = extract_feat
         self._engine = None
+
+    @property
+    def is_relation_head(self):
+        return self.consensus_type in RELATION_TYPES
 
     def init_weights(self):
         nn.init.normal_(self.new_fc.weight, 0, self.init_std)
@@ -221,15 +254,26 @@ class TSNClsHead(nn.Module):
     def engine(self):
         if self._engine is None:
             from ..engine import HeadEngine
-            self._engine = HeadEngine(self.new_fc, self.new_fc.weight.device)
+            if self.is_relation_head:
+                self._engine = HeadEngine(self.new_fc, self.new_fc.weight.device, relation=self.segmental_consensus, relation_type=self.consensus_type)
+            else:
+                self._engine = HeadEngine(self.new_fc, self.new_fc.weight.device)
         return self._engine
 
     def invalidate_engine(self):
         self._engine = None
 
-    def forward(self, x, num_seg):
+    def forward(self, x, num_seg, relations=None):
         """x: (N*T, C, h, w) features [or (clips, C, T, h, w) with fcn_testing] -> (clips, num_classes) scores, or with extract_feat the
-        (clips, in_channels) consensus of the pooled features."""
+        (clips, in_channels) consensus of the pooled features.  relations (relation heads only): the int32 (R, 1 + T) table to evaluate instead of
+        this forward's draw (heads/relation.py)."""
+        if self.is_relation_head:
+            if num_seg != self.num_frames:
+                raise ValueError("TSNClsHead: consensus_cfg num_frames=%d, but the features come in clips of %d frames" % (self.num_frames, num_seg))
+            if x.dim() != 4:
+                raise ValueError("TSNClsHead: the %s relation head takes (N*T, C, h, w) features, got %s" % (self.consensus_type, tuple(x.shape)))
+        elif relations is not None:
+            raise ValueError("TSNClsHead: relations= is an argument of the 'TRN' / 'TRNmultiscale' heads")
         if self.extract_feat and self.training:
             raise NotImplementedError("TSNClsHead: extract_feat=True is an eval-mode path (feature extraction); call .eval() first")
         if not x.is_cuda:
@@ -245,6 +289,8 @@ class TSNClsHead(nn.Module):
             feat = feat.contiguous()
         if self.extract_feat:
             return self.engine().features(feat, num_seg)
+        if self.is_relation_head:
+            return self.engine().scores(feat, num_seg, relations=relations)
         return self.engine().scores(feat, num_seg)
 
     def loss(self, cls_score, labels):

@@ -53,6 +53,13 @@ class Recognizer2D(nn.Module):
         self.fp16_enabled = False
         self.backbone = build_backbone(backbone)
         self.cls_head = build_head(cls_head) if cls_head is not None else None
+        if getattr(self.cls_head, "is_relation_head", False):
+            # the 'TRN' / 'TRNmultiscale' head (heads/relation.py) concatenates the clip's frames in order: its num_frames is the recognizer's n_segment
+            if fcn_testing:
+                raise ValueError("Recognizer2D: fcn_testing=True is not a configuration of the %s relation head" % self.cls_head.consensus_type)
+            n_seg = module_cfg.get("n_segment") if module_cfg else None
+            if n_seg is not None and n_seg != self.cls_head.num_frames:
+                raise ValueError("Recognizer2D: cls_head consensus_cfg num_frames=%d, module_cfg n_segment=%d: they must be equal" % (self.cls_head.num_frames, n_seg))
         self.init_weights()
         self.fcn_testing, self.modality = fcn_testing, modality
         self.train_cfg, self.test_cfg = train_cfg, test_cfg

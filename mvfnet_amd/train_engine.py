@@ -1917,6 +1917,16 @@ class TrainEngine(_ParamStore):
         self.dfc_w, self.dfc_b = self.grad_of(head.new_fc.weight), self.grad_of(head.new_fc.bias)
         self.dropout = head.dropout_ratio if head.dropout is not None else 0.0
         self.num_classes = head.num_classes
+        # Temporal-relation head (TSNClsHead(consensus_cfg=dict(type='TRN' | 'TRNmultiscale', num_frames=T)), heads/relation.py; None = the average consensus):
+        # new_fc then emits 256 frame features, and mvf_trn_head_fwd / mvf_trn_head_bwd (csrc/trn_head.hip) stand where the average head's fused entry points
+        # stood, with the loss from the stand-alone entry points (mvf_ce_loss, mvf_ce_loss_soft, mvf_bce_loss, mvf_focal_loss) on the scores they leave.  The
+        # step's relation table is drawn on the host (numpy's global generator, the reference's draw) and uploaded as the blend table is.  Such steps run
+        # eagerly (_plan_key): the per-scale operands are a host array built per call, which a recorded plan would freeze.  `relations`: an explicit int32
+        # (R, 1 + T) table for the following steps instead of the draw (tests).  With None the step allocates and launches exactly what it did without it.
+        self.trn, self.relations, self._relation_table = None, None, None
+        if getattr(head, "is_relation_head", False):
+            self.trn = dict(kind=head.consensus_type, t=head.num_frames, module=head.segmental_consensus, hidden=head.segmental_consensus.num_bottleneck,
+                            fdim=head.new_fc.weight.shape[0])
         # Gradient exchange in two buckets (see _launch_tail_allreduce): the flat buffer follows model.parameters() order (stem,
         # layer1..4, head), backward produces it back to front, so the slice from the first parameter of the third residual
         # stage to the end (layer3 + layer4 + fc = 94 % of ResNet-50) is complete when backward enters layer2.
@@ -2010,6 +2020,8 @@ class TrainEngine(_ParamStore):
             self._randaug_refusals(imgs)
         if self.distill is not None:
             self._distill_refusals()
+        if self.trn is not None:
+            self._relation_refusals(imgs)
         if self._ema_swapped:
             self._ema_live("a training forward")
         self._main = torch.cuda.current_stream()
@@ -2052,6 +2064,15 @@ class TrainEngine(_ParamStore):
         self._randaug_table = None
         if self.randaug is not None:
             self._randaug_table = self._draw_randaug(imgs)
+        self._relation_table = None
+        if self.trn is not None:
+            # as above: the table lives in a persistent device buffer filled here, never in a by-value argument
+            from .heads.relation import check_relation_table, draw_relation_table
+            self._relation_refusals(imgs)
+            table = draw_relation_table(self.trn["kind"], self.trn["t"]) if self.relations is None else self.relations
+            table = check_relation_table(table, self.trn["kind"], self.trn["t"])
+            (table_d,) = self._upload_table("relation_table", [table])
+            self._relation_table = (table_d, int(table.shape[0]))
         mask = None
         if self.dropout > 0.0:
             nt, cc = imgs.shape[0] * imgs.shape[1], self.fc_w.shape[1]
@@ -2129,6 +2150,62 @@ class TrainEngine(_ParamStore):
             raise ValueError("TrainEngine: randaug takes packed (B, T, Hs, Ws, 3) frames; %s input (decoder-native planes) is out of scope" % type(pipe).__name__)
         if pipe is not None and (imgs.dim() != 5 or imgs.shape[-1] != 3):
             raise ValueError("TrainEngine: randaug takes (B, T, Hs, Ws, 3) uint8 frames, got %s" % (tuple(imgs.shape),))
+
+    def _relation_refusals(self, imgs):
+        """The relation head concatenates the clip's frames: clips of another length than its num_frames are refused before the step's first launch."""
+        if imgs.dim() < 2 or imgs.shape[1] != self.trn["t"]:
+            raise ValueError("TrainEngine: the %s head was built with num_frames=%d, the batch holds clips of %s frames"
+                             % (self.trn["kind"], self.trn["t"], imgs.shape[1] if imgs.dim() >= 2 else "?"))
+
+    def _trn_operands(self):
+        """The _lib.TrnScale host array of the relation head: parameter and gradient addresses inside the flat buffers, read NOW (a re-homed store moves them)."""
+        from .heads.relation import scale_operands
+        return scale_operands(self.trn["module"], lambda p: p, self.grad_of)[0]
+
+    def _trn_head_forward(self, feat, b, t, hw, c, lab, mask, pooled, scores, dscores, loss_part, loss):
+        """Scores from mvf_trn_head_fwd, then the loss and dscores from the stand-alone entry point of the step's label kind."""
+        f32, trn = torch.float32, self.trn
+        table_d, rows = self._relation_table
+        fbuf = self.buf("trn_f", (b * t, trn["fdim"]), f32)
+        hbuf = self.buf("trn_h", (rows, b, trn["hidden"]), f32)
+        hpart = self.buf("trn_hpart", (_lib.TRN_KSPLIT_MAX, rows, b, trn["hidden"]), f32)
+        arr = self._trn_operands()
+        check(lib.mvf_trn_head_fwd(_p(feat), b, t, hw, c, _p(self.fc_w), _p(self.fc_b), trn["fdim"], arr, len(arr), trn["hidden"], self.num_classes, _p(table_d), rows,
+                                   _p(mask), _p(pooled), _p(fbuf), _p(hbuf), _p(hpart), _p(scores), self.dt, _st()), "trn head fwd")
+        if self._uses_soft_head(lab):
+            if lab.is_floating_point():
+                targets = lab
+            else:
+                rows_d, wts_d = self._blend_table if self.blending is not None else (None, None)
+                targets = self.buf("soft_targets", (b, self.num_classes), f32)
+                check(lib.mvf_soft_targets(_p(lab), _p(rows_d), _p(wts_d), b, self.num_classes, C.c_float(self.label_smooth_eps), _p(targets), _st()),
+                      "soft_targets")
+            if self.focal is not None:
+                class_weight, prm = self.focal
+                check(lib.mvf_focal_loss(_p(scores), _p(targets), b, self.num_classes, _p(class_weight), prm, _p(dscores), _p(loss_part), _p(loss), _st()),
+                      "focal loss")
+            elif self.bce is not None:
+                pos_weight, thr, sum_classes = self.bce
+                check(lib.mvf_bce_loss(_p(scores), _p(targets), b, self.num_classes, _p(pos_weight), C.c_float(thr), sum_classes, _p(dscores), _p(loss_part),
+                                       _p(loss), _st()), "bce loss")
+            else:
+                check(lib.mvf_ce_loss_soft(_p(scores), _p(targets), b, self.num_classes, _p(dscores), _p(loss_part), _p(loss), _st()), "ce loss (soft targets)")
+        else:
+            check(lib.mvf_ce_loss(_p(scores), _p(lab), b, self.num_classes, _p(dscores), _p(loss_part), _p(loss), _st()), "ce loss")
+        self.saved.update(trn_f=fbuf, trn_h=hbuf, trn_table=(table_d, rows))
+
+    def _trn_head_backward(self, s, g):
+        """mvf_trn_head_bwd: the gradients of every relation MLP and of new_fc, and the feature gradient in `g` (the gfeat buffer the blocks consume)."""
+        f32, trn = torch.float32, self.trn
+        b, t = s["b"], s["t"]
+        table_d, rows = s["trn_table"]
+        dh = self.buf("trn_dh", (rows, b, trn["hidden"]), f32)
+        df = self.buf("trn_df", (b * t, trn["fdim"]), f32)
+        dpool = self.buf("trn_dpool", (b * t, s["c"]), f32)
+        arr = self._trn_operands()
+        check(lib.mvf_trn_head_bwd(_p(s["dscores"]), _p(s["pooled"]), _p(s["trn_f"]), _p(s["trn_h"]), _p(self.fc_w), arr, len(arr), trn["hidden"], self.num_classes,
+                                   _p(table_d), rows, _p(s["mask"]), b, t, s["hw"], s["c"], trn["fdim"], _p(self.dfc_w), _p(self.dfc_b), _p(dh), _p(df), _p(dpool),
+                                   _p(g), self.dt, _st()), "trn head bwd")
 
     def _distill_refusals(self):
         """A teacher that cannot teach this model (the model itself, another device, class count or n_segment) or a request for a teacher in another
@@ -2265,7 +2342,9 @@ class TrainEngine(_ParamStore):
         scores = self.buf("scores", (b, self.num_classes), f32)
         dscores = self.buf("dscores", (b, self.num_classes), f32)
         loss_part = self.buf("loss_part", (b,), f32)
-        if self._uses_soft_head(lab):
+        if self.trn is not None:
+            self._trn_head_forward(xcur, b, t, hc * wc, cc, lab, mask, pooled, scores, dscores, loss_part, loss)
+        elif self._uses_soft_head(lab):
             if lab.is_floating_point():
                 targets = lab                            # the caller's soft labels: their address is the plan's `labels` slot
             else:
@@ -2333,10 +2412,13 @@ class TrainEngine(_ParamStore):
         if getattr(self, "_packs_on_side", False):
             self._wait(self.main_stream(), self._side)     # data-gradient weight packs (queued at the start of forward)
         nt, b, t = s["nt"], s["b"], s["t"]
-        dpool = self.buf("dpool", (b, s["c"]), torch.float32)
+        dpool = self.buf("dpool", (b, s["c"]), torch.float32) if self.trn is None else None
         g = self.buf("gfeat", tuple(s["feat_shape"]))
-        check(lib.mvf_head_train_bwd(_p(s["dscores"]), _p(s["pooled"]), _p(self.fc_w), _p(s["mask"]), b, t, s["hw"], s["c"], self.num_classes,
-                                     _p(self.dfc_w), _p(self.dfc_b), _p(dpool), _p(g), self.dt, _st()), "head bwd")
+        if self.trn is not None:
+            self._trn_head_backward(s, g)
+        else:
+            check(lib.mvf_head_train_bwd(_p(s["dscores"]), _p(s["pooled"]), _p(self.fc_w), _p(s["mask"]), b, t, s["hw"], s["c"], self.num_classes,
+                                         _p(self.dfc_w), _p(self.dfc_b), _p(dpool), _p(g), self.dt, _st()), "head bwd")
         gated = sums = False
         for i in range(len(self.blocks) - 1, -1, -1):
             req = self.blocks[i - 1].wants_gated_gradient(self) if i > 0 else None       # the block below takes gm = g * [out > 0] as a tensor
@@ -2444,6 +2526,7 @@ class TrainEngine(_ParamStore):
     use_plan = _policy("plan", 1) != 0
     plan_warmup = 2          # eager steps before the first recording (buffers and workspaces reach their final sizes in the first two)
     focal = None             # (the class default of the instance attribute __init__ sets: None is no plan-key switch, see _switch_names)
+    trn = relations = None   # (likewise: the relation head's settings and the explicit relation table)
 
     def _plan_key(self, imgs, labels):
         """None = this step cannot run from a plan; else what a plan is valid for."""
@@ -2455,6 +2538,8 @@ class TrainEngine(_ParamStore):
             return None                  # an erasing object that does not name its table width (max_boxes) may change it from step to step
         if self.distill is not None:
             return None                  # the teacher's calls go through engine.py, which a plan does not record; back at None the recorded plans are replayed
+        if self.trn is not None:
+            return None                  # the relation head's per-scale operands are a host array built per call; the average head's key is what it was
         sw = self.__dict__.get("_switch_names")
         if sw is None:
             sw = self._switch_names = sorted(k for c_ in type(self).__mro__ for k, v in vars(c_).items()
@@ -2509,6 +2594,8 @@ class TrainEngine(_ParamStore):
             self._randaug_refusals(imgs)
         if self.distill is not None:
             self._distill_refusals()
+        if self.trn is not None:
+            self._relation_refusals(imgs)
         if self._ema_swapped:
             self._ema_live("a training step")
         if self._guard is not None:
