@@ -544,7 +544,16 @@ typedef struct {
     int32_t launches;                     /* kernel launches the call made                                                                   */
 } mvf_bn_launch_info_t;
 int mvf_bn_last_launch(mvf_bn_launch_info_t* out);
-/* head: avg-pool per frame -> new_fc -> mean over the clip's t frames -> cross-entropy (mean over clips).
+/* The train head (csrc/head.hip).  The four fused forward forms -- mvf_head_train_fwd, _soft, _bce, _focal -- make the same two score launches (pooled and
+ * scores hold the same bits in every form) and share one argument check, made before any launch (a refused call enqueues nothing and touches no output), in
+ * this order: clips, t, hw, c, classes >= 1 (MVF_EINVAL); dtype MVF_F32 or MVF_BF16 (MVF_EINVAL); c * 4 bytes <= 160 KiB, the LDS feature buffer
+ * (MVF_EUNSUPPORTED); clips * t <= 65535, a grid dimension (MVF_ESHAPE); feat, fc_w, pooled, dscores non-NULL (MVF_EINVAL).  Then the form's own loss check:
+ * labels / targets, scores, loss_part, loss non-NULL (MVF_EINVAL), for _bce and _focal the checks of mvf_bce_loss / mvf_focal_loss.  mvf_head_train_bwd checks,
+ * before any launch: its pointers (MVF_EINVAL), c % 4 (MVF_ESHAPE), dtype (MVF_EINVAL), clips * t, clips and (classes + 3) / 4 <= 65535 (MVF_ESHAPE).
+ * (mvf_head_train_fwd used to take any dtype != 0 as bf16, test the LDS limit after its first launch and leave the grid to the runtime, and mvf_head_train_bwd
+ * tested neither dtype nor grids: those calls, which ended in MVF_EHIP or in undefined results, are now refused as the other three forms always refused them.)
+ *
+ * head: avg-pool per frame -> new_fc -> mean over the clip's t frames -> cross-entropy (mean over clips).
  * pooled (clips*t, c), scores (clips, classes), dscores = dloss/dscores, loss_part (clips), loss (1): all fp32. */
 int mvf_head_train_fwd(const void* feat, int clips, int t, int hw, int c, const float* fc_w, const float* fc_b, int classes,
                        const long long* labels, const float* drop_mask /* (clips*t, c) pre-scaled keep mask or NULL */,
@@ -602,7 +611,7 @@ int mvf_head_train_fwd_soft(const void* feat, int clips, int t, int hw, int c, c
 int mvf_bce_loss(const float* scores, const float* targets, int clips, int classes, const float* pos_weight /* (classes) or NULL */,
                  float target_threshold /* NaN = off */, int sum_classes, float* dscores /* or NULL */, float* loss_part, float* loss, void* stream);
 /* mvf_head_train_fwd_soft with the loss of mvf_bce_loss in place of the soft-target cross-entropy: the same pool and fc launches (pooled and scores hold
- * the same bits), then the two loss launches.  The checks of both, before any launch; dscores is required. */
+ * the same bits), then the two loss launches.  dscores is required. */
 int mvf_head_train_fwd_bce(const void* feat, int clips, int t, int hw, int c, const float* fc_w, const float* fc_b, int classes,
                            const float* targets, const float* drop_mask /* (clips*t, c) pre-scaled keep mask or NULL */,
                            const float* pos_weight /* (classes) or NULL */, float target_threshold /* NaN = off */, int sum_classes,
@@ -649,7 +658,7 @@ typedef struct mvf_focal_params {
 int mvf_focal_loss(const float* scores, const float* targets, int clips, int classes, const float* class_weight /* (classes) or NULL */,
                    const mvf_focal_params_t* prm, float* dscores /* or NULL */, float* loss_part, float* loss, void* stream);
 /* mvf_head_train_fwd_bce with the loss of mvf_focal_loss in place of the binary cross-entropy: the same pool and fc launches (pooled and scores hold the
- * same bits), then the two loss launches.  The checks of both, before any launch; dscores is required. */
+ * same bits), then the two loss launches.  dscores is required. */
 int mvf_head_train_fwd_focal(const void* feat, int clips, int t, int hw, int c, const float* fc_w, const float* fc_b, int classes,
                              const float* targets, const float* drop_mask /* (clips*t, c) pre-scaled keep mask or NULL */,
                              const float* class_weight /* (classes) or NULL */, const mvf_focal_params_t* prm,

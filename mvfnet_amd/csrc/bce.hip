@@ -12,7 +12,7 @@
 // Launches, both on the caller's stream, no atomics, no workspace:
 //   1. bce_clip_kernel: one workgroup per clip, 256 threads, a strided loop over the classes (any classes >= 1): the element losses, their sum, loss_part[i]
 //      and, when asked for, the clip's row of dscores.
-//   2. bce_mean_kernel: one wavefront, loss[0] = the mean of loss_part.
+//   2. loss_mean_kernel (loss_common.h): one wavefront, loss[0] = the mean of loss_part.
 // Every reduction has a fixed order -- a shuffle tree inside the wavefront, then the wave partials from LDS in wave order, then clips in ascending order --
 // and the grids depend on clips alone: bit-identical from run to run.
 //
@@ -25,16 +25,9 @@
 
 #pragma clang fp contract(off)
 
+#include "loss_common.h"
+
 namespace {
-
-constexpr int kWave = 64;
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / kWave;
-
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-    return v;
-}
 
 __global__ __launch_bounds__(kThreads) void bce_clip_kernel(const float* __restrict__ scores, const float* __restrict__ targets, int clips, int classes,
                                                             const float* __restrict__ pos_weight, float threshold, int sum_classes,
@@ -62,22 +55,8 @@ __global__ __launch_bounds__(kThreads) void bce_clip_kernel(const float* __restr
             dscores[(long)cl * classes + k] = s != s ? NAN : (float)g;
         }
     }
-    acc = wave_sum(acc);
-    if ((tid & (kWave - 1)) == 0) red[tid / kWave] = acc;
-    __syncthreads();
-    if (tid == 0) {
-        double r = red[0];
-        for (int w = 1; w < kWaves; ++w) r += red[w];
-        loss_part[cl] = (float)(r / D);
-    }
-}
-
-// lanes take clips l, l + 64, .. in ascending order, a shuffle tree adds the 64 lane sums
-__global__ __launch_bounds__(kWave) void bce_mean_kernel(const float* __restrict__ loss_part, int clips, float* __restrict__ loss) {
-    double s = 0.0;
-    for (int i = threadIdx.x; i < clips; i += kWave) s += (double)loss_part[i];
-    const double m = wave_sum(s) / (double)clips;
-    if (threadIdx.x == 0) loss[0] = (float)m;
+    const double r = clip_sum(acc, red);
+    if (tid == 0) loss_part[cl] = (float)(r / D);
 }
 
 }  // namespace
@@ -97,7 +76,7 @@ int bce_launch(const float* scores, const float* targets, int clips, int classes
                float* loss_part, float* loss, hipStream_t st) {
     hipLaunchKernelGGL(bce_clip_kernel, dim3(clips), dim3(kThreads), 0, st, scores, targets, clips, classes, pos_weight, threshold, sum_classes, dscores, loss_part);
     MVF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(bce_mean_kernel, dim3(1), dim3(kWave), 0, st, (const float*)loss_part, clips, loss);
+    hipLaunchKernelGGL(loss_mean_kernel, dim3(1), dim3(kWave), 0, st, (const float*)loss_part, clips, loss);
     MVF_LAUNCH_CHECK();
     return MVF_OK;
 }

@@ -14,7 +14,7 @@
 //      them, and terms[1] = the mean of T^2 * kd_i.  The entry point takes no workspace, so this launch computes kd_i itself, clip after clip, with the
 //      same row function and the same reduction order as launch 2: the same bits.
 //   2. distill_clip_kernel: one workgroup per clip, 256 threads, strided loops over the classes: kd_i, then loss_part[i] and the clip's row of dscores.
-//   3. distill_mean_kernel: one wavefront, loss[0] = the mean of the new loss_part.
+//   3. loss_mean_kernel (loss_common.h): one wavefront, loss[0] = the mean of the new loss_part.
 // Every reduction has a fixed order -- a shuffle tree inside the wavefront, then the wave partials from LDS in wave order, then clips in ascending order --
 // and the grids depend on clips alone: bit-identical from run to run.
 //
@@ -28,16 +28,9 @@
 
 #pragma clang fp contract(off)
 
+#include "loss_common.h"
+
 namespace {
-
-constexpr int kWave = 64;
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / kWave;
-
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-    return v;
-}
 
 __device__ __forceinline__ double wave_max(double v) {
     for (int off = kWave / 2; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, kWave));
@@ -114,13 +107,6 @@ __global__ __launch_bounds__(kThreads) void distill_clip_kernel(const float* sco
     }
 }
 
-// lanes take clips l, l + 64, .. in ascending order, a shuffle tree adds the 64 lane sums
-__device__ __forceinline__ double wave_mean(const float* v, int n, int lane) {
-    double s = 0.0;
-    for (int i = lane; i < n; i += kWave) s += (double)v[i];
-    return wave_sum(s) / (double)n;
-}
-
 __global__ __launch_bounds__(kThreads) void distill_terms_kernel(const float* scores, const float* teacher, int clips, int classes, float temperature,
                                                                  const float* loss_part, float* terms) {
     __shared__ double red[kWaves];
@@ -134,11 +120,6 @@ __global__ __launch_bounds__(kThreads) void distill_terms_kernel(const float* sc
             terms[1] = (float)(kd_sum / (double)clips);
         }
     }
-}
-
-__global__ __launch_bounds__(kWave) void distill_mean_kernel(const float* loss_part, int clips, float* loss) {
-    const double m = wave_mean(loss_part, clips, threadIdx.x);
-    if (threadIdx.x == 0) loss[0] = (float)m;
 }
 
 }  // namespace
@@ -159,7 +140,7 @@ int mvf_distill_loss(const float* scores, const float* teacher_scores, int clips
     }
     hipLaunchKernelGGL(distill_clip_kernel, dim3(clips), dim3(kThreads), 0, st, scores, teacher_scores, clips, classes, temperature, alpha, dscores, loss_part);
     MVF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(distill_mean_kernel, dim3(1), dim3(kWave), 0, st, (const float*)loss_part, clips, loss);
+    hipLaunchKernelGGL(loss_mean_kernel, dim3(1), dim3(kWave), 0, st, (const float*)loss_part, clips, loss);
     MVF_LAUNCH_CHECK();
     return MVF_OK;
 }

@@ -1,9 +1,8 @@
 // Training-mode companions of the conv stack (all HBM-bound, channels-last [M][C] matrices):
-// batch-statistics BatchNorm forward/backward, residual/ReLU, max-pool fwd/bwd, TSN head + cross-entropy fwd/bwd.
+// batch-statistics BatchNorm forward/backward, residual/ReLU, max-pool fwd/bwd (the TSN head and its losses are csrc/head.hip).
 // Reference semantics: torch BatchNorm2d defaults (biased var to normalise, unbiased into
 // running_var, momentum 0.1; codes/models/common/norm.py:59 sets eps), Bottleneck.forward
-// (codes/models/backbones/resnet.py:208-244), TSNClsHead.forward + BaseHead.loss (heads/tsn_clshead.py:71-98,
-// heads/base.py:40-45).
+// (codes/models/backbones/resnet.py:208-244).
 //
 // Reductions over M are two-stage and atomic-free: per-block column partials [blocks][C][k] in fp32, then a
 // finalize kernel that sums them in fp64 in block order -> deterministic run to run.
@@ -1171,173 +1170,6 @@ __global__ void maxpool_bn_bwd_kernel(const unsigned char* amax, const ET* g, in
     }
 }
 
-// ---- head: per-frame avg-pool -> fc -> mean over segments -> cross-entropy (mean over clips) ----
-// pooled[frame][ch] = mean over hw ; lanes along channels
-template <typename ET>
-__global__ void frame_pool_kernel(const ET* feat, int hw, int c, const float* drop_mask, float* pooled) {
-    const int f = blockIdx.y, ch = blockIdx.x * blockDim.x + threadIdx.x;
-    if (ch >= c) return;
-    const ET* p = feat + (long)f * hw * c + ch;
-    float s = 0.f;
-    for (int r = 0; r < hw; ++r) s += ldf(p + (long)r * c);
-    s = s / (float)hw;
-    if (drop_mask) s *= drop_mask[(long)f * c + ch];      // nn.Dropout: mask already scaled by 1/(1-p) (tsn_clshead.py:86-87)
-    pooled[(long)f * c + ch] = s;
-}
-
-// one block per clip: softmax CE of scores[clip] against label; writes loss contribution and dscores = (p - onehot)/clips
-__global__ void ce_loss_kernel(const float* scores, const long long* labels, int clips, int classes, float* loss_part, float* dscores) {
-    __shared__ float red[256];
-    const int cl = blockIdx.x, tid = threadIdx.x;
-    const float* s = scores + (long)cl * classes;
-    float mx = -INFINITY;
-    for (int k = tid; k < classes; k += blockDim.x) mx = fmaxf(mx, s[k]);
-    red[tid] = mx;
-    __syncthreads();
-    for (int o = blockDim.x >> 1; o > 0; o >>= 1) { if (tid < o) red[tid] = fmaxf(red[tid], red[tid + o]); __syncthreads(); }
-    mx = red[0];
-    __syncthreads();
-    float e = 0.f;
-    for (int k = tid; k < classes; k += blockDim.x) e += expf(s[k] - mx);
-    red[tid] = e;
-    __syncthreads();
-    for (int o = blockDim.x >> 1; o > 0; o >>= 1) { if (tid < o) red[tid] += red[tid + o]; __syncthreads(); }
-    const float den = red[0];
-    const int lab = (int)labels[cl];
-    if (tid == 0) loss_part[cl] = (logf(den) + mx) - s[lab];
-    if (!dscores) return;
-    for (int k = tid; k < classes; k += blockDim.x) {
-        const float p = expf(s[k] - mx) / den;
-        dscores[(long)cl * classes + k] = (p - (k == lab ? 1.f : 0.f)) / (float)clips;
-    }
-}
-
-// the same against a row of soft targets t (any non-negative fp32 row, not assumed to sum to 1: blended and / or smoothed labels, mvf_soft_targets):
-// loss = sum_k t_k * (lse - s_k) -- exactly 0 for one class --, dscores = (softmax * sum_k t_k - t) / clips.  Fixed-order block reductions: deterministic.
-__global__ void ce_loss_soft_kernel(const float* scores, const float* targets, int clips, int classes, float* loss_part, float* dscores) {
-    __shared__ float red[256];
-    const int cl = blockIdx.x, tid = threadIdx.x;
-    const float* s = scores + (long)cl * classes;
-    const float* tg = targets + (long)cl * classes;
-    float mx = -INFINITY;
-    for (int k = tid; k < classes; k += blockDim.x) mx = fmaxf(mx, s[k]);
-    red[tid] = mx;
-    __syncthreads();
-    for (int o = blockDim.x >> 1; o > 0; o >>= 1) { if (tid < o) red[tid] = fmaxf(red[tid], red[tid + o]); __syncthreads(); }
-    mx = red[0];
-    __syncthreads();
-    float e = 0.f;
-    for (int k = tid; k < classes; k += blockDim.x) e += expf(s[k] - mx);
-    red[tid] = e;
-    __syncthreads();
-    for (int o = blockDim.x >> 1; o > 0; o >>= 1) { if (tid < o) red[tid] += red[tid + o]; __syncthreads(); }
-    const float den = red[0];
-    __syncthreads();
-    const float lse = logf(den) + mx;
-    float acc = 0.f, tsum = 0.f;
-    for (int k = tid; k < classes; k += blockDim.x) {
-        const float tk = tg[k];
-        acc += tk * (lse - s[k]);
-        tsum += tk;
-    }
-    red[tid] = acc;
-    __syncthreads();
-    for (int o = blockDim.x >> 1; o > 0; o >>= 1) { if (tid < o) red[tid] += red[tid + o]; __syncthreads(); }
-    if (tid == 0) loss_part[cl] = red[0];
-    if (!dscores) return;
-    __syncthreads();
-    red[tid] = tsum;
-    __syncthreads();
-    for (int o = blockDim.x >> 1; o > 0; o >>= 1) { if (tid < o) red[tid] += red[tid + o]; __syncthreads(); }
-    tsum = red[0];
-    for (int k = tid; k < classes; k += blockDim.x) {
-        const float p = expf(s[k] - mx) / den;
-        dscores[(long)cl * classes + k] = (p * tsum - tg[k]) / (float)clips;
-    }
-}
-
-__global__ void mean_reduce_kernel(const float* v, int n, float* out) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        double s = 0.0;
-        for (int i = 0; i < n; ++i) s += v[i];
-        out[0] = (float)(s / n);
-    }
-}
-
-// dW[k][c] = sum_clip dscores[clip][k] * pooledclip[clip][c] ; db[k] = sum_clip dscores[clip][k]   (pooledclip = mean over T)
-// thread = one channel, workgroup = (256 channels, kHeadKc classes): the channel's clip-mean features are formed once per thread
-// (clips are walked in chunks of 16 registers) and reused for every class of the range, instead of re-reading the T frame rows for
-// each of the 400 classes (69 -> ~15 us).  Fixed clip order: deterministic.
-constexpr int kHeadKc = 4;
-__global__ void head_clipmean_kernel(const float* pooled, int T, int c, float* pcm) {
-    const int cl = blockIdx.y, ch = blockIdx.x * blockDim.x + threadIdx.x;
-    if (ch >= c) return;
-    float s = 0.f;
-    for (int t = 0; t < T; ++t) s += pooled[((long)cl * T + t) * c + ch];
-    pcm[(long)cl * c + ch] = s / (float)T;
-}
-__global__ __launch_bounds__(256) void head_fc_bwd_w_kernel(const float* dscores, const float* pcm, int clips, int T, int c, int classes, float* dw, float* db) {
-    const int k0 = blockIdx.y * kHeadKc, ch = blockIdx.x * blockDim.x + threadIdx.x;
-    const int nk = min(kHeadKc, classes - k0);
-    if (ch < c) {
-        float acc[kHeadKc];
-#pragma unroll
-        for (int j = 0; j < kHeadKc; ++j) acc[j] = 0.f;
-        for (int cl0 = 0; cl0 < clips; cl0 += 16) {
-            float pcv[16];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) pcv[q] = pcm[(long)min(cl0 + q, clips - 1) * c + ch];      // clamped: unconditional loads
-#pragma unroll
-            for (int j = 0; j < kHeadKc; ++j) {
-                if (j < nk) {
-#pragma unroll
-                    for (int q = 0; q < 16; ++q)
-                        if (cl0 + q < clips) acc[j] += dscores[(long)(cl0 + q) * classes + k0 + j] * pcv[q];
-                }
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < kHeadKc; ++j)
-            if (j < nk) dw[(long)(k0 + j) * c + ch] = acc[j];
-    }
-    if (blockIdx.x == 0 && threadIdx.x < nk) {
-        float s = 0.f;
-        for (int cl = 0; cl < clips; ++cl) s += dscores[(long)cl * classes + k0 + threadIdx.x];
-        db[k0 + threadIdx.x] = s;
-    }
-}
-
-// dfeat[frame][hw][ch] = (1/(T*hw)) * sum_k dscores[clip][k] * W[k][ch]
-__global__ void head_dpool_kernel(const float* dscores, const float* w, int classes, int c, float scale, float* dpool) {
-    const int cl = blockIdx.y, ch = blockIdx.x * blockDim.x + threadIdx.x;
-    if (ch >= c) return;
-    // eight independent accumulators: the class loop is a chain of L2 round trips otherwise (81 -> ~15 us)
-    float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    const float* ds = dscores + (long)cl * classes;
-    int k = 0;
-    for (; k + 8 <= classes; k += 8) {
-#pragma unroll
-        for (int u = 0; u < 8; ++u) a[u] += ds[k + u] * w[(long)(k + u) * c + ch];
-    }
-    for (; k < classes; ++k) a[0] += ds[k] * w[(long)k * c + ch];
-    dpool[(long)cl * c + ch] = (((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]))) * scale;
-}
-template <typename ET>
-__global__ void head_dfeat_kernel(const float* dpool, const float* drop_mask, int T, int hw, int c, long total, ET* dfeat) {
-    // blockIdx.y = frame, threads over (row, 4 channels): the frame's gradient row (dpool x mask) is the same for its hw pixels
-    const int frame = blockIdx.y, c4 = c >> 2;
-    const int per = hw * c4;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < per; i += gridDim.x * blockDim.x) {
-        const int q = i % c4;
-        float4 v = *reinterpret_cast<const float4*>(dpool + (long)(frame / T) * c + q * 4);
-        if (drop_mask) {
-            const float4 mk = *reinterpret_cast<const float4*>(drop_mask + (long)frame * c + q * 4);
-            v.x *= mk.x; v.y *= mk.y; v.z *= mk.z; v.w *= mk.w;
-        }
-        st4(dfeat + ((long)frame * hw * c + (long)i * 4), v);
-    }
-}
-
 inline int grid_for(long total, int cap) { return (int)std::min<long>((total + 255) / 256, cap); }      // (the max-pool launchers' grids)
 
 // Host-side record of the calling thread's last BatchNorm / max-pool call (mvf_bn_last_launch): plain host stores next to the launches, nothing on the device.
@@ -1863,203 +1695,6 @@ int mvf_maxpool_bn_relu_bwd_apply(const unsigned char* argmax, const void* g, in
 int mvf_bn_last_launch(mvf_bn_launch_info_t* out) {
     MVF_REQUIRE(out, MVF_EINVAL, "bn_last_launch: NULL argument");
     *out = t_last_bn;
-    return MVF_OK;
-}
-
-// head, training: feat (clips*T, hw, c) -> pooled (clips*T, c) fp32 [kept for backward] -> scores (clips, classes) -> loss
-int mvf_head_train_fwd(const void* feat, int clips, int t, int hw, int c, const float* fc_w, const float* fc_b, int classes,
-                       const long long* labels, const float* drop_mask, float* pooled, float* scores, float* dscores, float* loss_part, float* loss,
-                       int dtype, void* stream);
-int mvf_head_train_bwd(const float* dscores, const float* pooled, const float* fc_w, const float* drop_mask, int clips, int t, int hw, int c, int classes,
-                       float* dfc_w, float* dfc_b, float* dpool_ws, void* dfeat, int dtype, void* stream);
-
-}  // extern "C"
-
-// frame-level fc + segment mean (training keeps per-frame pooled features for the weight gradient)
-namespace {
-// fc per frame, then consensus mean over the clip's T frames (tsn_clshead.py:92-96) -- both linear, so the clip's mean feature is
-// formed once in LDS (fixed t order) and every class is one dot product with it: T x fewer multiply-adds and, with a workgroup per
-// (clip, class range) instead of a wave per (clip, class), 8 x less L2 traffic than re-reading the T frame rows for every class
-// (137 -> ~20 us at 32 clips x 400 classes x 2048 channels).
-constexpr int kHeadSplit = 25;      // class ranges per clip (16 classes per workgroup at 400 classes: 4 per wave, all in flight)
-__global__ __launch_bounds__(256) void head_fc_seg_kernel(const float* pooled, const float* w, const float* b, int clips, int T, int c, int classes, float* scores) {
-    extern __shared__ float pc[];                   // [c] the clip's mean pooled feature
-    const int clip = blockIdx.x, part = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float inv = 1.f / (float)T;
-    for (int i = tid; i < c; i += 256) {
-        float s = 0.f;
-        for (int t = 0; t < T; ++t) s += pooled[((long)clip * T + t) * c + i];
-        pc[i] = s * inv;
-    }
-    __syncthreads();
-    const int per = (classes + kHeadSplit - 1) / kHeadSplit;
-    const int k_end = min(classes, (part + 1) * per);
-    // a wave takes classes k, k+4, k+8, k+12 of the range together: four independent dot products keep four weight rows in flight
-    const int kb = part * per + wave;
-    float s[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int i = lane; i < c; i += 64) {
-        const float f = pc[i];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int k = kb + 4 * u;
-            s[u] += f * w[(long)(k < k_end ? k : kb < k_end ? kb : 0) * c + i];       // clamped row: unconditional load
-        }
-    }
-    for (int u0 = 0; u0 * 16 < per; ++u0) {            // ranges longer than 16 classes: further rounds of four
-        if (u0 > 0) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) s[u] = 0.f;
-            for (int i = lane; i < c; i += 64) {
-                const float f = pc[i];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int k = kb + 16 * u0 + 4 * u;
-                    s[u] += f * w[(long)(k < k_end ? k : 0) * c + i];
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            float v = s[u];
-            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-            const int k = kb + 16 * u0 + 4 * u;
-            if (lane == 0 && k < k_end) scores[(long)clip * classes + k] = v + (b ? b[k] : 0.f);
-        }
-    }
-}
-}  // namespace
-
-extern "C" {
-
-int mvf_head_train_fwd(const void* feat, int clips, int t, int hw, int c, const float* fc_w, const float* fc_b, int classes,
-                       const long long* labels, const float* drop_mask, float* pooled, float* scores, float* dscores, float* loss_part, float* loss,
-                       int dtype, void* stream) {
-    MVF_REQUIRE(feat && fc_w && labels && pooled && scores && dscores && loss_part && loss && clips > 0 && t > 0 && hw > 0 && c > 0 && classes > 0, MVF_EINVAL, "head_train_fwd: bad argument");
-    hipStream_t st = (hipStream_t)stream;
-    dim3 g((c + 255) / 256, clips * t);
-    if (dtype == MVF_F32) hipLaunchKernelGGL(frame_pool_kernel<float>, g, dim3(256), 0, st, (const float*)feat, hw, c, drop_mask, pooled);
-    else hipLaunchKernelGGL(frame_pool_kernel<bf16_t>, g, dim3(256), 0, st, (const bf16_t*)feat, hw, c, drop_mask, pooled);
-    MVF_LAUNCH_CHECK();
-    MVF_REQUIRE((size_t)c * sizeof(float) <= 160 * 1024, MVF_EUNSUPPORTED, "head_train_fwd: c=%d does not fit the LDS feature buffer", c);
-    hipLaunchKernelGGL(head_fc_seg_kernel, dim3(clips, kHeadSplit), dim3(256), (size_t)c * sizeof(float), st, pooled, fc_w, fc_b, clips, t, c, classes, scores);
-    MVF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ce_loss_kernel, dim3(clips), dim3(256), 0, st, scores, labels, clips, classes, loss_part, dscores);
-    MVF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(mean_reduce_kernel, dim3(1), dim3(64), 0, st, loss_part, clips, loss);
-    MVF_LAUNCH_CHECK();
-    return MVF_OK;
-}
-
-int mvf_ce_loss(const float* scores, const long long* labels, int clips, int classes, float* dscores, float* loss_part, float* loss, void* stream) {
-    MVF_REQUIRE(scores && labels && loss_part && loss && clips > 0 && classes > 0, MVF_EINVAL, "ce_loss: bad argument");
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(ce_loss_kernel, dim3(clips), dim3(256), 0, st, scores, labels, clips, classes, loss_part, dscores);
-    MVF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(mean_reduce_kernel, dim3(1), dim3(64), 0, st, loss_part, clips, loss);
-    MVF_LAUNCH_CHECK();
-    return MVF_OK;
-}
-
-// mvf_head_train_fwd against soft targets (clips, classes) instead of integer labels: the same frame_pool_kernel and head_fc_seg_kernel launches, then the
-// soft-target loss.  Every by-value argument is checked before the first launch.
-int mvf_head_train_fwd_soft(const void* feat, int clips, int t, int hw, int c, const float* fc_w, const float* fc_b, int classes,
-                            const float* targets, const float* drop_mask, float* pooled, float* scores, float* dscores, float* loss_part, float* loss,
-                            int dtype, void* stream) {
-    MVF_REQUIRE(clips > 0 && t > 0 && hw > 0 && c > 0 && classes > 0, MVF_EINVAL, "head_train_fwd_soft: bad argument (clips=%d t=%d hw=%d c=%d classes=%d)",
-                clips, t, hw, c, classes);
-    MVF_REQUIRE(dtype == MVF_F32 || dtype == MVF_BF16, MVF_EINVAL, "head_train_fwd_soft: dtype %d", dtype);
-    MVF_REQUIRE((size_t)c * sizeof(float) <= 160 * 1024, MVF_EUNSUPPORTED, "head_train_fwd_soft: c=%d does not fit the LDS feature buffer", c);
-    MVF_REQUIRE((long)clips * t <= 65535, MVF_ESHAPE, "head_train_fwd_soft: %d x %d frames exceed the grid", clips, t);
-    MVF_REQUIRE(feat && fc_w && targets && pooled && scores && dscores && loss_part && loss, MVF_EINVAL, "head_train_fwd_soft: NULL argument");
-    hipStream_t st = (hipStream_t)stream;
-    dim3 g((c + 255) / 256, clips * t);
-    if (dtype == MVF_F32) hipLaunchKernelGGL(frame_pool_kernel<float>, g, dim3(256), 0, st, (const float*)feat, hw, c, drop_mask, pooled);
-    else hipLaunchKernelGGL(frame_pool_kernel<bf16_t>, g, dim3(256), 0, st, (const bf16_t*)feat, hw, c, drop_mask, pooled);
-    MVF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(head_fc_seg_kernel, dim3(clips, kHeadSplit), dim3(256), (size_t)c * sizeof(float), st, pooled, fc_w, fc_b, clips, t, c, classes, scores);
-    MVF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ce_loss_soft_kernel, dim3(clips), dim3(256), 0, st, scores, targets, clips, classes, loss_part, dscores);
-    MVF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(mean_reduce_kernel, dim3(1), dim3(64), 0, st, loss_part, clips, loss);
-    MVF_LAUNCH_CHECK();
-    return MVF_OK;
-}
-
-// mvf_head_train_fwd_soft with the binary cross-entropy of mvf_bce_loss (bce.hip) in place of the soft-target cross-entropy: the same frame_pool_kernel and
-// head_fc_seg_kernel launches, so pooled and scores hold the same bits.  Every argument is checked before the first launch.
-int mvf_head_train_fwd_bce(const void* feat, int clips, int t, int hw, int c, const float* fc_w, const float* fc_b, int classes,
-                           const float* targets, const float* drop_mask, const float* pos_weight, float target_threshold, int sum_classes,
-                           float* pooled, float* scores, float* dscores, float* loss_part, float* loss, int dtype, void* stream) {
-    MVF_REQUIRE(clips > 0 && t > 0 && hw > 0 && c > 0 && classes > 0, MVF_EINVAL, "head_train_fwd_bce: bad argument (clips=%d t=%d hw=%d c=%d classes=%d)",
-                clips, t, hw, c, classes);
-    MVF_REQUIRE(dtype == MVF_F32 || dtype == MVF_BF16, MVF_EINVAL, "head_train_fwd_bce: dtype %d", dtype);
-    MVF_REQUIRE((size_t)c * sizeof(float) <= 160 * 1024, MVF_EUNSUPPORTED, "head_train_fwd_bce: c=%d does not fit the LDS feature buffer", c);
-    MVF_REQUIRE((long)clips * t <= 65535, MVF_ESHAPE, "head_train_fwd_bce: %d x %d frames exceed the grid", clips, t);
-    MVF_REQUIRE(feat && fc_w && pooled && dscores, MVF_EINVAL, "head_train_fwd_bce: NULL argument");
-    const int rc = mvf_internal::bce_check("head_train_fwd_bce", scores, targets, clips, classes, target_threshold, sum_classes, loss_part, loss);
-    if (rc != MVF_OK) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    dim3 g((c + 255) / 256, clips * t);
-    if (dtype == MVF_F32) hipLaunchKernelGGL(frame_pool_kernel<float>, g, dim3(256), 0, st, (const float*)feat, hw, c, drop_mask, pooled);
-    else hipLaunchKernelGGL(frame_pool_kernel<bf16_t>, g, dim3(256), 0, st, (const bf16_t*)feat, hw, c, drop_mask, pooled);
-    MVF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(head_fc_seg_kernel, dim3(clips, kHeadSplit), dim3(256), (size_t)c * sizeof(float), st, pooled, fc_w, fc_b, clips, t, c, classes, scores);
-    MVF_LAUNCH_CHECK();
-    return mvf_internal::bce_launch(scores, targets, clips, classes, pos_weight, target_threshold, sum_classes, dscores, loss_part, loss, st);
-}
-
-// mvf_head_train_fwd_bce with the focal / asymmetric loss of mvf_focal_loss (focal.hip) in place of the binary cross-entropy: the same frame_pool_kernel and
-// head_fc_seg_kernel launches, so pooled and scores hold the same bits.  Every argument is checked before the first launch; prm is read here, on the host.
-int mvf_head_train_fwd_focal(const void* feat, int clips, int t, int hw, int c, const float* fc_w, const float* fc_b, int classes,
-                             const float* targets, const float* drop_mask, const float* class_weight, const mvf_focal_params_t* prm,
-                             float* pooled, float* scores, float* dscores, float* loss_part, float* loss, int dtype, void* stream) {
-    MVF_REQUIRE(clips > 0 && t > 0 && hw > 0 && c > 0 && classes > 0, MVF_EINVAL, "head_train_fwd_focal: bad argument (clips=%d t=%d hw=%d c=%d classes=%d)",
-                clips, t, hw, c, classes);
-    MVF_REQUIRE(dtype == MVF_F32 || dtype == MVF_BF16, MVF_EINVAL, "head_train_fwd_focal: dtype %d", dtype);
-    MVF_REQUIRE((size_t)c * sizeof(float) <= 160 * 1024, MVF_EUNSUPPORTED, "head_train_fwd_focal: c=%d does not fit the LDS feature buffer", c);
-    MVF_REQUIRE((long)clips * t <= 65535, MVF_ESHAPE, "head_train_fwd_focal: %d x %d frames exceed the grid", clips, t);
-    MVF_REQUIRE(feat && fc_w && pooled && dscores, MVF_EINVAL, "head_train_fwd_focal: NULL argument");
-    const int rc = mvf_internal::focal_check("head_train_fwd_focal", scores, targets, clips, classes, prm, loss_part, loss);
-    if (rc != MVF_OK) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    dim3 g((c + 255) / 256, clips * t);
-    if (dtype == MVF_F32) hipLaunchKernelGGL(frame_pool_kernel<float>, g, dim3(256), 0, st, (const float*)feat, hw, c, drop_mask, pooled);
-    else hipLaunchKernelGGL(frame_pool_kernel<bf16_t>, g, dim3(256), 0, st, (const bf16_t*)feat, hw, c, drop_mask, pooled);
-    MVF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(head_fc_seg_kernel, dim3(clips, kHeadSplit), dim3(256), (size_t)c * sizeof(float), st, pooled, fc_w, fc_b, clips, t, c, classes, scores);
-    MVF_LAUNCH_CHECK();
-    return mvf_internal::focal_launch(scores, targets, clips, classes, class_weight, *prm, dscores, loss_part, loss, st);
-}
-
-int mvf_ce_loss_soft(const float* scores, const float* targets, int clips, int classes, float* dscores, float* loss_part, float* loss, void* stream) {
-    MVF_REQUIRE(clips > 0 && classes > 0, MVF_EINVAL, "ce_loss_soft: bad argument (clips=%d classes=%d)", clips, classes);
-    MVF_REQUIRE(scores && targets && loss_part && loss, MVF_EINVAL, "ce_loss_soft: NULL argument");
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(ce_loss_soft_kernel, dim3(clips), dim3(256), 0, st, scores, targets, clips, classes, loss_part, dscores);
-    MVF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(mean_reduce_kernel, dim3(1), dim3(64), 0, st, loss_part, clips, loss);
-    MVF_LAUNCH_CHECK();
-    return MVF_OK;
-}
-
-int mvf_head_train_bwd(const float* dscores, const float* pooled, const float* fc_w, const float* drop_mask, int clips, int t, int hw, int c, int classes,
-                       float* dfc_w, float* dfc_b, float* dpool_ws, void* dfeat, int dtype, void* stream) {
-    MVF_REQUIRE(dscores && pooled && fc_w && dfc_w && dfc_b && dpool_ws && dfeat, MVF_EINVAL, "head_train_bwd: NULL argument");
-    hipStream_t st = (hipStream_t)stream;
-    MVF_REQUIRE(c % 4 == 0, MVF_ESHAPE, "head_train_bwd: c=%d must be a multiple of 4", c);
-    // the clips' mean features borrow dpool_ws ([clips][c] floats), which the NEXT kernel of this call overwrites with its real content
-    float* pcm = dpool_ws;
-    hipLaunchKernelGGL(head_clipmean_kernel, dim3((c + 255) / 256, clips), dim3(256), 0, st, pooled, t, c, pcm);
-    MVF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(head_fc_bwd_w_kernel, dim3((c + 255) / 256, (classes + kHeadKc - 1) / kHeadKc), dim3(256), 0, st, dscores, pcm, clips, t, c, classes, dfc_w, dfc_b);
-    MVF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(head_dpool_kernel, dim3((c + 255) / 256, clips), dim3(256), 0, st, dscores, fc_w, classes, c, 1.0f / ((float)t * hw), dpool_ws);
-    MVF_LAUNCH_CHECK();
-    const long total = (long)clips * t * hw * c;
-    const dim3 gdf((unsigned)std::min<long>(((long)hw * (c / 4) + 255) / 256, 64), (unsigned)(clips * t));
-    if (dtype == MVF_F32) hipLaunchKernelGGL(head_dfeat_kernel<float>, gdf, dim3(256), 0, st, dpool_ws, drop_mask, t, hw, c, total, (float*)dfeat);
-    else hipLaunchKernelGGL(head_dfeat_kernel<bf16_t>, gdf, dim3(256), 0, st, dpool_ws, drop_mask, t, hw, c, total, (bf16_t*)dfeat);
-    MVF_LAUNCH_CHECK();
     return MVF_OK;
 }
 

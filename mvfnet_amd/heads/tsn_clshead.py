@@ -295,7 +295,7 @@ class TSNClsHead(nn.Module):
 
     def loss(self, cls_score, labels):
         """reference heads/base.py:40-45: {'loss_cls': F.cross_entropy(cls_score, labels)} (mean over the clips), computed by the
-        HIP cross-entropy kernel of the train head (mvf_ce_loss); no autograd through it -- Recognizer2D.forward_train is the
+        HIP cross-entropy kernel of the train head (mvf_ce_loss, csrc/head.hip); no autograd through it -- Recognizer2D.forward_train is the
         path that trains (scores, loss and their gradients in one fused head).
         labels: integers (B,) / (B, 1), or a floating-point (B, num_classes) matrix of soft labels (mvf_ce_loss_soft).  In training mode integer labels are
         smoothed with label_smooth_eps (mvf_soft_targets) as mmaction's head does.
@@ -303,7 +303,8 @@ class TSNClsHead(nn.Module):
         is (multi-hot labels), integer labels through mvf_soft_targets.  With one of the focal family (SigmoidFocalLoss, CBFocalLoss,
         AsymmetricLossMultiLabel) the same, through mvf_focal_loss."""
         import ctypes as C
-        from .._lib import check, lib
+        from .._lib import lib
+        from . import loss_calls
         if not cls_score.is_cuda:
             raise RuntimeError("TSNClsHead.loss: mvfnet_amd runs on MI355X tensors only; no CPU fallback (tests use oracle/)")
         s = cls_score.detach().to(torch.float32).contiguous()
@@ -315,46 +316,16 @@ class TSNClsHead(nn.Module):
         eps = self.label_smooth_eps if self.training else 0.0
         if soft and eps > 0.0:
             raise ValueError("TSNClsHead.loss: soft (B, num_classes) labels are taken as they are; label_smooth_eps needs integer labels")
-        if bce is not None or focal is not None:
-            # loss_cls = BCELossWithLogits or one of the focal family: always against a target matrix -- the caller's (multi-hot or soft), or mvf_soft_targets' one-hot / smoothed one
-            P = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-            if soft:
-                tgt = labels.detach().to(device=s.device, dtype=torch.float32).contiguous()
-            else:
-                lab = labels.reshape(-1).to(device=s.device, dtype=torch.int64).contiguous()
-                if lab.numel() != s.shape[0]:
-                    raise ValueError("TSNClsHead.loss: %d labels for %d score rows" % (lab.numel(), s.shape[0]))
-                tgt = torch.empty_like(s)
-                check(lib.mvf_soft_targets(P(lab), None, None, s.shape[0], s.shape[1], C.c_float(eps), P(tgt), stream), "mvf_soft_targets")
-            part = torch.empty(s.shape[0], dtype=torch.float32, device=s.device)
-            out = torch.empty(1, dtype=torch.float32, device=s.device)
-            if focal is not None:
-                cw, prm = focal
-                check(lib.mvf_focal_loss(P(s), P(tgt), s.shape[0], s.shape[1], P(cw), prm, None, P(part), P(out), stream), "mvf_focal_loss")
-                return dict(loss_cls=out.reshape(()))
-            pw, thr, sum_classes = bce
-            check(lib.mvf_bce_loss(P(s), P(tgt), s.shape[0], s.shape[1], P(pw), C.c_float(thr), sum_classes, None, P(part), P(out), stream), "mvf_bce_loss")
-            return dict(loss_cls=out.reshape(()))
-        if soft or eps > 0.0:
-            P = lambda t: C.c_void_p(t.data_ptr())
-            if soft:
-                tgt = labels.detach().to(device=s.device, dtype=torch.float32).contiguous()
-            else:
-                lab = labels.reshape(-1).to(device=s.device, dtype=torch.int64).contiguous()
-                if lab.numel() != s.shape[0]:
-                    raise ValueError("TSNClsHead.loss: %d labels for %d score rows" % (lab.numel(), s.shape[0]))
-                tgt = torch.empty_like(s)
-                check(lib.mvf_soft_targets(P(lab), None, None, s.shape[0], s.shape[1], C.c_float(eps), P(tgt), stream), "mvf_soft_targets")
-            part = torch.empty(s.shape[0], dtype=torch.float32, device=s.device)
-            out = torch.empty(1, dtype=torch.float32, device=s.device)
-            check(lib.mvf_ce_loss_soft(P(s), P(tgt), s.shape[0], s.shape[1], None, P(part), P(out), stream), "mvf_ce_loss_soft")
-            return dict(loss_cls=out.reshape(()))
-        lab = labels.reshape(-1).to(device=s.device, dtype=torch.int64).contiguous()
-        if lab.numel() != s.shape[0]:
-            raise ValueError("TSNClsHead.loss: %d labels for %d score rows" % (lab.numel(), s.shape[0]))
+        if soft:
+            tgt = labels.detach().to(device=s.device, dtype=torch.float32).contiguous()
+        else:
+            tgt = labels.reshape(-1).to(device=s.device, dtype=torch.int64).contiguous()
+            if tgt.numel() != s.shape[0]:
+                raise ValueError("TSNClsHead.loss: %d labels for %d score rows" % (tgt.numel(), s.shape[0]))
+            # loss_cls = BCELossWithLogits or one of the focal family always runs against a target matrix: mvf_soft_targets' one-hot / smoothed one
+            if bce is not None or focal is not None or eps > 0.0:
+                tgt, soft = loss_calls.targets_for(lib, tgt, None, None, s.shape[0], s.shape[1], eps, torch.empty_like(s), stream), True
         part = torch.empty(s.shape[0], dtype=torch.float32, device=s.device)
         out = torch.empty(1, dtype=torch.float32, device=s.device)
-        P = lambda t: C.c_void_p(t.data_ptr())
-        check(lib.mvf_ce_loss(P(s), P(lab), s.shape[0], s.shape[1], None, P(part), P(out), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-              "mvf_ce_loss")
+        loss_calls.stand_alone_loss(lib, loss_calls.loss_kind(bce, focal, soft), s, tgt, s.shape[0], s.shape[1], None, part, out, stream)
         return dict(loss_cls=out.reshape(()))

@@ -22,6 +22,7 @@ import torch
 
 from . import _lib
 from ._lib import ConvDesc, MvfDesc, check, lib
+from .heads import loss_calls
 
 F32 = _lib.MVF_F32
 
@@ -2163,7 +2164,7 @@ class TrainEngine(_ParamStore):
         return scale_operands(self.trn["module"], lambda p: p, self.grad_of)[0]
 
     def _trn_head_forward(self, feat, b, t, hw, c, lab, mask, pooled, scores, dscores, loss_part, loss):
-        """Scores from mvf_trn_head_fwd, then the loss and dscores from the stand-alone entry point of the step's label kind."""
+        """Scores from mvf_trn_head_fwd, then the loss and dscores from the stand-alone entry point of the step's label kind (heads/loss_calls.py)."""
         f32, trn = torch.float32, self.trn
         table_d, rows = self._relation_table
         fbuf = self.buf("trn_f", (b * t, trn["fdim"]), f32)
@@ -2172,26 +2173,8 @@ class TrainEngine(_ParamStore):
         arr = self._trn_operands()
         check(lib.mvf_trn_head_fwd(_p(feat), b, t, hw, c, _p(self.fc_w), _p(self.fc_b), trn["fdim"], arr, len(arr), trn["hidden"], self.num_classes, _p(table_d), rows,
                                    _p(mask), _p(pooled), _p(fbuf), _p(hbuf), _p(hpart), _p(scores), self.dt, _st()), "trn head fwd")
-        if self._uses_soft_head(lab):
-            if lab.is_floating_point():
-                targets = lab
-            else:
-                rows_d, wts_d = self._blend_table if self.blending is not None else (None, None)
-                targets = self.buf("soft_targets", (b, self.num_classes), f32)
-                check(lib.mvf_soft_targets(_p(lab), _p(rows_d), _p(wts_d), b, self.num_classes, C.c_float(self.label_smooth_eps), _p(targets), _st()),
-                      "soft_targets")
-            if self.focal is not None:
-                class_weight, prm = self.focal
-                check(lib.mvf_focal_loss(_p(scores), _p(targets), b, self.num_classes, _p(class_weight), prm, _p(dscores), _p(loss_part), _p(loss), _st()),
-                      "focal loss")
-            elif self.bce is not None:
-                pos_weight, thr, sum_classes = self.bce
-                check(lib.mvf_bce_loss(_p(scores), _p(targets), b, self.num_classes, _p(pos_weight), C.c_float(thr), sum_classes, _p(dscores), _p(loss_part),
-                                       _p(loss), _st()), "bce loss")
-            else:
-                check(lib.mvf_ce_loss_soft(_p(scores), _p(targets), b, self.num_classes, _p(dscores), _p(loss_part), _p(loss), _st()), "ce loss (soft targets)")
-        else:
-            check(lib.mvf_ce_loss(_p(scores), _p(lab), b, self.num_classes, _p(dscores), _p(loss_part), _p(loss), _st()), "ce loss")
+        kind, tgt = self._loss_operands(lab, b)
+        loss_calls.stand_alone_loss(lib, kind, scores, tgt, b, self.num_classes, dscores, loss_part, loss, _st())
         self.saved.update(trn_f=fbuf, trn_h=hbuf, trn_table=(table_d, rows))
 
     def _trn_head_backward(self, s, g):
@@ -2261,6 +2244,16 @@ class TrainEngine(_ParamStore):
 
     def _uses_soft_head(self, lab):
         return self.blending is not None or self.label_smooth_eps > 0.0 or lab.is_floating_point() or self.bce is not None or self.focal is not None
+
+    def _loss_operands(self, lab, b):
+        """(heads.loss_calls.loss_kind of the step, its labels or target matrix).  A target matrix is the caller's own soft labels -- their address is the
+        plan's `labels` slot -- or mvf_soft_targets' (a library call, not torch scatter ops: a replayed plan skips torch calls made inside the recorded region)."""
+        soft = self._uses_soft_head(lab)
+        if soft and not lab.is_floating_point():
+            rows_d, wts_d = self._blend_table if self.blending is not None else (None, None)
+            lab = loss_calls.targets_for(lib, lab, rows_d, wts_d, b, self.num_classes, self.label_smooth_eps,
+                                         self.buf("soft_targets", (b, self.num_classes), torch.float32), _st())
+        return loss_calls.loss_kind(self.bce, self.focal, soft), lab
 
     def set_options(self, lr=None, momentum=None, weight_decay=None, max_norm=None, dtype=None, optimizer=None, betas=None, eps=None, trust_clip=None,
                     always_adapt=None):
@@ -2344,31 +2337,10 @@ class TrainEngine(_ParamStore):
         loss_part = self.buf("loss_part", (b,), f32)
         if self.trn is not None:
             self._trn_head_forward(xcur, b, t, hc * wc, cc, lab, mask, pooled, scores, dscores, loss_part, loss)
-        elif self._uses_soft_head(lab):
-            if lab.is_floating_point():
-                targets = lab                            # the caller's soft labels: their address is the plan's `labels` slot
-            else:
-                # a library call, not torch scatter ops: a replayed plan skips torch calls made inside the recorded region
-                rows_d, wts_d = self._blend_table if self.blending is not None else (None, None)
-                targets = self.buf("soft_targets", (b, self.num_classes), f32)
-                check(lib.mvf_soft_targets(_p(lab), _p(rows_d), _p(wts_d), b, self.num_classes, C.c_float(self.label_smooth_eps), _p(targets), _st()),
-                      "soft_targets")
-            if self.focal is not None:
-                class_weight, prm = self.focal
-                check(lib.mvf_head_train_fwd_focal(_p(xcur), b, t, hc * wc, cc, _p(self.fc_w), _p(self.fc_b), self.num_classes, _p(targets), _p(mask),
-                                                   _p(class_weight), prm, _p(pooled), _p(scores), _p(dscores), _p(loss_part), _p(loss), self.dt, _st()),
-                      "head fwd (focal)")
-            elif self.bce is not None:
-                pos_weight, thr, sum_classes = self.bce
-                check(lib.mvf_head_train_fwd_bce(_p(xcur), b, t, hc * wc, cc, _p(self.fc_w), _p(self.fc_b), self.num_classes, _p(targets), _p(mask),
-                                                 _p(pos_weight), C.c_float(thr), sum_classes, _p(pooled), _p(scores), _p(dscores), _p(loss_part), _p(loss),
-                                                 self.dt, _st()), "head fwd (bce)")
-            else:
-                check(lib.mvf_head_train_fwd_soft(_p(xcur), b, t, hc * wc, cc, _p(self.fc_w), _p(self.fc_b), self.num_classes, _p(targets), _p(mask), _p(pooled),
-                                                  _p(scores), _p(dscores), _p(loss_part), _p(loss), self.dt, _st()), "head fwd (soft targets)")
         else:
-            check(lib.mvf_head_train_fwd(_p(xcur), b, t, hc * wc, cc, _p(self.fc_w), _p(self.fc_b), self.num_classes, _p(lab), _p(mask), _p(pooled),
-                                         _p(scores), _p(dscores), _p(loss_part), _p(loss), self.dt, _st()), "head fwd")
+            kind, tgt = self._loss_operands(lab, b)
+            loss_calls.fused_head_loss(lib, kind, xcur, b, t, hc * wc, cc, self.fc_w, self.fc_b, self.num_classes, tgt, mask, pooled, scores, dscores, loss_part,
+                                       loss, self.dt, _st())
         if teacher_scores is not None:
             # the head left the cross-entropy's dscores / loss_part / loss: they become the combined loss's in place, whatever kind of labels made them
             terms = self._distill_terms = self.buf("distill_terms", (2,), f32)

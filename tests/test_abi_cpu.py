@@ -94,7 +94,7 @@ def test_plan_run_generic_call_marshals_integers_and_floats_in_order():
 
 
 def test_head_and_optimizer_argument_failures_return_before_any_launch():
-    """The head's and the optimizer's entry points check their arguments before the first launch (csrc/train_ops.hip, csrc/optim.hip, csrc/net_ops.hip): the codes come back on
+    """The head's and the optimizer's entry points check their arguments before the first launch (csrc/head.hip, csrc/optim.hip): the codes come back on
     a machine without a GPU, from host addresses that are never read."""
     import ctypes as C
     from mvfnet_amd import _lib
@@ -116,6 +116,34 @@ def test_head_and_optimizer_argument_failures_return_before_any_launch():
     assert b"multiple of 4" in lib.mvf_last_error()
     assert lib.mvf_head_pool_fc(a, 1, 1, 1, 6, a, a, 1, a, a, 0, None) == ESHAPE
     assert b"multiple of 4" in lib.mvf_last_error()
+
+
+def test_every_head_form_refuses_bad_score_arguments_before_any_launch():
+    """The four fused forward forms of csrc/head.hip share one argument check, mvf_head_train_bwd has its counterpart: a storage type that is neither fp32 nor
+    bf16, more frames than a grid holds, more channels than the LDS feature buffer and a NULL pooled come back with the same code from every form.  The addresses
+    are host memory that is never read, and this machine has no GPU: a call that reached a launch would return MVF_EHIP, so each code shows the refusal came first."""
+    import ctypes as C
+    from mvfnet_amd import _lib
+    lib = _lib.lib
+    host = (C.c_float * 64)()
+    a = C.cast(host, C.c_void_p)
+    EINVAL, ESHAPE, EUNSUPPORTED = -1, -2, -5
+    prm = _lib.FocalParams(gamma_pos=2.0, gamma_neg=2.0, margin=0.0, alpha=0.25, target_threshold=float("nan"), sum_classes=0)
+    forms = {"head_train_fwd": (lib.mvf_head_train_fwd, ()), "head_train_fwd_soft": (lib.mvf_head_train_fwd_soft, ()),
+             "head_train_fwd_bce": (lib.mvf_head_train_fwd_bce, (None, C.c_float(float("nan")), 0)), "head_train_fwd_focal": (lib.mvf_head_train_fwd_focal, (None, prm))}
+    for who, (fn, mid) in forms.items():
+        def call(clips=2, t=4, c=8, pooled=a, dtype=0):
+            return fn(a, clips, t, 9, c, a, a, 10, a, None, *mid, pooled, a, a, a, a, dtype, None)
+        for rc_want, word, kw in ((EINVAL, b"dtype 2", dict(dtype=2)), (ESHAPE, b"exceed the grid", dict(clips=65536, t=1)),
+                                  (EUNSUPPORTED, b"c=40961 does not fit", dict(c=40961)), (EINVAL, b"NULL", dict(pooled=None))):
+            assert call(**kw) == rc_want, (who, kw, lib.mvf_last_error())
+            err = lib.mvf_last_error()
+            assert err.startswith(who.encode() + b":") and word in err, (who, kw, err)
+        assert call(clips=0) == EINVAL and b"bad argument" in lib.mvf_last_error()
+    bwd = lambda clips=2, t=4, dtype=0: lib.mvf_head_train_bwd(a, a, a, None, clips, t, 9, 8, 10, a, a, a, a, dtype, None)  # noqa: E731
+    assert bwd(dtype=2) == EINVAL and b"head_train_bwd: dtype 2" in lib.mvf_last_error()
+    assert bwd(clips=16384, t=4) == ESHAPE and b"exceed the grid" in lib.mvf_last_error()
+    assert bwd(clips=65536, t=1) == ESHAPE
 
 
 def test_refused_weight_gradient_calls_leave_an_empty_launch_record():

@@ -1,5 +1,5 @@
-"""GPU: the binary cross-entropy head -- mvf_bce_loss / mvf_head_train_fwd_bce (csrc/bce.hip, csrc/train_ops.hip) and mvf_average_clip_sigmoid
-(csrc/net_ops.hip) against the fp64 restatement in bce_numpy.py, and the train engine with a BCE head: multi-hot labels, integer labels through
+"""GPU: the binary cross-entropy head -- mvf_bce_loss / mvf_head_train_fwd_bce (csrc/bce.hip, csrc/head.hip) and mvf_average_clip_sigmoid
+(csrc/head.hip) against the fp64 restatement in bce_numpy.py, and the train engine with a BCE head: multi-hot labels, integer labels through
 mvf_soft_targets (smoothing, Mixup), launch plans, distillation behind it, and the default head's plan.
 
 Bounds are the suite's own for the head's loss and gradient (test_head_optimizer_gpu.py: LOSS_BOUND for loss_part / loss, HEAD_BOUND for dscores,

@@ -1,4 +1,4 @@
-"""GPU: batch blending and soft labels -- mvf_stem_blend / mvf_soft_targets (csrc/blend.hip), mvf_ce_loss_soft / mvf_head_train_fwd_soft (csrc/train_ops.hip)
+"""GPU: batch blending and soft labels -- mvf_stem_blend / mvf_soft_targets (csrc/blend.hip), mvf_ce_loss_soft / mvf_head_train_fwd_soft (csrc/head.hip)
 against the fp64 restatement in blend_numpy.py, and the train engine with them: a device-blended step equals the host-blended step bit for bit, a replayed
 launch plan equals the eager steps bit for bit while lambda changes from step to step, the uint8 input path is blended behind the frame kernel, and eval is
 untouched.  The reference project has neither feature: the semantics are those of include/mvfnet_hip.h.

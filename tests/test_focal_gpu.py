@@ -1,4 +1,4 @@
-"""GPU: the focal / asymmetric sigmoid losses -- mvf_focal_loss / mvf_head_train_fwd_focal (csrc/focal.hip, csrc/train_ops.hip) against the fp64 restatement in
+"""GPU: the focal / asymmetric sigmoid losses -- mvf_focal_loss / mvf_head_train_fwd_focal (csrc/focal.hip, csrc/head.hip) against the fp64 restatement in
 focal_numpy.py, and the train engine with a focal head: multi-hot labels, integer labels through mvf_soft_targets (smoothing, Mixup), launch plans,
 distillation behind it, and the plans of the default and the BCE head.
 

@@ -1,6 +1,6 @@
 """The last two stages of a training step through the C ABI, each against an fp64 restatement written here: the TSN head (tsn_clshead.py: per-frame
-average pool -> dropout -> fc -> consensus mean over the segments -> cross-entropy; csrc/train_ops.hip frame_pool / head_fc_seg / ce_loss / head_fc_bwd_w /
-head_dpool / head_dfeat and csrc/net_ops.hip head_pool / head_fc / average_clip) and the fused clip_grad_norm_ + SGD step (dist_utils.py:61-67 +
+average pool -> dropout -> fc -> consensus mean over the segments -> cross-entropy; csrc/head.hip frame_pool / head_fc_seg / ce_loss / head_fc_bwd_w /
+head_dpool / head_dfeat and its inference kernels head_pool / head_fc / average_clip) and the fused clip_grad_norm_ + SGD step (dist_utils.py:61-67 +
 torch.optim.SGD; csrc/optim.hip sqsum_* / norm_finalize / sgd_kernel).  The references take the same explicit dropout mask, labels and segment table as
 the kernels; inputs come from seeded generators.
 
@@ -136,6 +136,35 @@ def test_head_train_vs_fp64(name, dtype, p):
         assert not np.array_equal(free["pooled"], got["pooled"]) and not np.array_equal(free["scores"], got["scores"])
         if HEAD_CASES[name][4] > 1:          # one class: dscores = 0 and every gradient with it, mask or not
             assert not np.array_equal(free["dfeat"], got["dfeat"]) and not np.array_equal(free["dfc_w"], got["dfc_w"])
+
+
+@pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("name", ["c36_k10_empty_class_ranges", "k401_per17_second_round_clips33"])
+def test_fused_forms_equal_the_stand_alone_losses_on_their_own_scores(name, dtype):
+    """mvf_head_train_fwd against mvf_ce_loss and mvf_head_train_fwd_soft against mvf_ce_loss_soft, with the p = 0.5 mask: dscores, loss_part and loss of the
+    fused form are, bit for bit, the stand-alone loss run on the fused form's own scores, and pooled and scores hold the same bits in the hard and the soft
+    form (one pair of score launches, one loss launcher behind both; the BCE and focal forms have this test in test_bce_gpu.py / test_focal_gpu.py)."""
+    lib, check = _lib()
+    inp = head_inputs(HEAD_CASES[name], dtype, 0.5)
+    clips, T, hw, c, classes = inp["case"]
+    dev, dt, nan = "cuda", 0 if dtype == F32 else 1, float("nan")
+    fg, wg, bg, lab, mg = inp["feat"].to(dev, dtype).contiguous(), inp["w"].to(dev), inp["b"].to(dev), inp["labels"].to(dev), inp["mask"].to(dev)
+    gen = torch.Generator().manual_seed(clips * 7 + classes)
+    targets = (torch.rand(clips, classes, generator=gen) ** 3).to(dev)
+    full = lambda *s: torch.full(s, nan, device=dev)  # noqa: E731
+    got = {}
+    for form, fused, alone, tg in (("hard", lib.mvf_head_train_fwd, lib.mvf_ce_loss, lab), ("soft", lib.mvf_head_train_fwd_soft, lib.mvf_ce_loss_soft, targets)):
+        pooled, scores, dsc, lp, lo = full(clips * T, c), full(clips, classes), full(clips, classes), full(clips), full(1)
+        check(fused(P(fg), clips, T, hw, c, P(wg), P(bg), classes, P(tg), P(mg), P(pooled), P(scores), P(dsc), P(lp), P(lo), dt, None), form)
+        dsc2, lp2, lo2 = full(clips, classes), full(clips), full(1)
+        check(alone(P(scores), P(tg), clips, classes, P(dsc2), P(lp2), P(lo2), None), form)
+        torch.cuda.synchronize()
+        assert torch.isfinite(dsc).all() and torch.isfinite(lp).all() and torch.isfinite(lo).all() and torch.isfinite(scores).all()
+        for a, b_, what in ((dsc, dsc2, "dscores"), (lp, lp2, "loss_part"), (lo, lo2, "loss")):
+            assert torch.equal(a.view(torch.int32), b_.view(torch.int32)), (form, what)
+        got[form] = (pooled, scores)
+    for a, b_, what in zip(got["hard"], got["soft"], ("pooled", "scores")):
+        assert torch.equal(a.view(torch.int32), b_.view(torch.int32)), what
 
 
 # ------------------------------------------------------------------------------------------------ 2. cross-entropy
