@@ -393,7 +393,8 @@ int mvf_bn_train_finalize(const float* part, int nblk, long m, int c, const floa
 /* [r5] The same outputs for z = a W^T, the output of a POINTWISE conv (Bottleneck.conv3 -> norm3, resnet.py:236-237), WITHOUT computing z: mean_c = W[c].abar,
  * var_c = W[c] (A2 / m - abar abar^T) W[c]^T from the Gram matrix gram [k][k] = a^T a of the conv's input (mvf_conv2d_nhwc_wgrad with dz = x = a), its
  * column means a_mean [k] (mvf_bn_train_stats on a) and the forward pack w_packed [c][k].  Replaces the statistics pass of a block that applies this
- * BatchNorm in a second conv pass (mvf_conv2d_nhwc_fwd_bnapply); the dz3-free backward reuses gram / a_mean.  bf16 storage, c and k multiples of 32. */
+ * BatchNorm in a second conv pass (mvf_conv2d_nhwc_fwd_bnapply); the dz3-free backward reuses gram / a_mean.  bf16 storage, c and k multiples of 32.
+ * Up to 16 rows (m <= 16: a variance of at most 15 squares, which some channels take 1e6 times below its terms) the sums are taken in fp64. */
 int mvf_bn_train_stats_gram(const float* gram, const float* a_mean, const void* w_packed, long m, int c, int k, const float* gamma, const float* beta,
                             float eps, float momentum, float* running_mean, float* running_var, float* save_mean, float* save_invstd, float* scale,
                             float* shift, int dtype, void* stream);

@@ -310,6 +310,43 @@ __global__ __launch_bounds__(256) void gram_stats_kernel(GramStatsArgs p) {
     }
 }
 
+// The same outputs for FEW ROWS (m <= GRAM_F64_MAX_ROWS), in fp64.  Gc = A2 / m - abar abar^T has rank m - 1 at most, so over the channels var_c = W[c] Gc W[c]^T is
+// a sum of m - 1 squares: with a handful of rows some channels land 1e5 .. 1e7 times below the sum of the absolute values of their terms (two rows: one square,
+// var_c = (W[c] . (a_1 - a_2))^2 / 4), and invstd = (var + eps)^-1/2 multiplies the fp32 error of the sum by that ratio -- any fp32 evaluation of the expression
+// leaves invstd 1e-4 .. 1e-3 off there (tests/test_dzfree_kernels_gpu.py found it at m = 2; from 17 degrees of freedom on the lower tail is empty and the matrix
+// form above is within 1.1e-6).  Such a call is never on the training step's critical path (m = n h w >= 1568 there): one wave per channel, plain loops.
+constexpr long GRAM_F64_MAX_ROWS = 16;
+__global__ __launch_bounds__(256) void gram_stats_f64_kernel(GramStatsArgs p, double inv_m, double unbias) {
+    const int lane = threadIdx.x & 63, c = blockIdx.x * 4 + (threadIdx.x >> 6), K = p.K;
+    if (c >= p.C) return;
+    const uint16_t* pw = p.w + (long)c * K;
+    double q = 0.0, mu = 0.0;
+    for (int k = lane; k < K; k += 64) {
+        const double wk = (double)__uint_as_float((unsigned)pw[k] << 16), ak = (double)p.a_mean[k];
+        const float* pg = p.gram + (long)k * K;
+        double t = 0.0;
+        for (int j = 0; j < K; ++j) t += (double)__uint_as_float((unsigned)pw[j] << 16) * ((double)pg[j] * inv_m - ak * (double)p.a_mean[j]);
+        q += wk * t;
+        mu += wk * ak;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {          // fixed order
+        q += __shfl_xor(q, o, 64);
+        mu += __shfl_xor(mu, o, 64);
+    }
+    if (lane == 0) {
+        const double var = q > 0.0 ? q : 0.0;
+        const float mean = (float)mu, invstd = (float)(1.0 / sqrt(var + (double)p.eps));
+        p.save_mean[c] = mean;
+        p.save_invstd[c] = invstd;
+        const float s = p.gamma[c] * invstd;
+        p.scale[c] = s;
+        p.shift[c] = p.beta[c] - mean * s;
+        if (p.running_mean) p.running_mean[c] = (1.f - p.momentum) * p.running_mean[c] + p.momentum * mean;
+        if (p.running_var) p.running_var[c] = (1.f - p.momentum) * p.running_var[c] + p.momentum * (float)(var * unbias);
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -323,7 +360,10 @@ int mvf_bn_train_stats_gram(const float* gram, const float* a_mean, const void* 
     MVF_REQUIRE(((uintptr_t)gram | (uintptr_t)a_mean | (uintptr_t)w_packed) % 16 == 0, MVF_EINVAL, "bn_train_stats_gram: operands must be 16-byte aligned");
     GramStatsArgs p = {gram, a_mean, (const uint16_t*)w_packed, gamma, beta, running_mean, running_var, save_mean, save_invstd, scale, shift,
                        c, k, 1.0f / (float)m, eps, momentum, (float)((double)m / (double)(m > 1 ? m - 1 : 1))};
-    hipLaunchKernelGGL(gram_stats_kernel, dim3((c / 32 + 3) / 4), dim3(256), 0, (hipStream_t)stream, p);
+    if (m <= GRAM_F64_MAX_ROWS)
+        hipLaunchKernelGGL(gram_stats_f64_kernel, dim3((c + 3) / 4), dim3(256), 0, (hipStream_t)stream, p, 1.0 / (double)m, (double)m / (double)(m > 1 ? m - 1 : 1));
+    else
+        hipLaunchKernelGGL(gram_stats_kernel, dim3((c / 32 + 3) / 4), dim3(256), 0, (hipStream_t)stream, p);
     MVF_LAUNCH_CHECK();
     return MVF_OK;
 }

@@ -271,3 +271,64 @@ def test_refused_batchnorm_and_pool_calls_leave_a_record_that_says_so():
     assert lib.mvf_bn_workspace_bytes(8, 8) == nb and lib.mvf_maxpool_bwd_sums_rows(2, 9) == 3           # plan queries leave the record alone
     assert lib.mvf_bn_last_launch(C.byref(info)) == 0 and info.entry == E["pool_bwd_apply"]
     assert lib.mvf_bn_last_launch(None) == -1
+
+
+@pytest.mark.cpu
+def test_dzfree_and_gram_glue_entry_points_refuse_before_any_launch():
+    """The four entry points of csrc/bn_dzfree.hip check their arguments before the launch: every code below comes back on a machine without a GPU (a call that
+    reached the launch would return MVF_EHIP), from host addresses that are never read.  `a` is 64-byte aligned; the misaligned rows move one operand off it."""
+    import ctypes as C
+    from mvfnet_amd import _lib
+    lib = _lib.lib
+    host = (C.c_char * 4096)()
+    base = (C.addressof(host) + 63) // 64 * 64
+    a = C.c_void_p(base)
+    off = lambda n: C.c_void_p(base + n)  # noqa: E731
+    EINVAL, ESHAPE, EUNSUPPORTED = -1, -2, -5
+    BF16, F32 = _lib.MVF_BF16, _lib.MVF_F32
+
+    def prep(c=256, k=32, m=37, dtype=BF16, ptrs=None, w_out=a):
+        p = [a] * 7 if ptrs is None else ptrs                        # w_packed_dgrad, gamma, mean, invstd, dgamma, dbeta, bias_out
+        return lib.mvf_bn_bwd_dzfree_prep(p[0], c, k, p[1], p[2], p[3], p[4], p[5], m, w_out, p[6], dtype, None)
+
+    def wgrad(c=32, k=64, m=37, dtype=BF16, gram=a):
+        return lib.mvf_bn_bwd_dzfree_wgrad(a, a, gram, a, a, a, a, a, a, m, c, k, dtype, None)
+
+    def sums(c=8, k=4, q=a, w=a, part_lo=a, rows_lo=2, c_split=4, part_hi=a, rows_hi=2):
+        return lib.mvf_bn_bwd_dzfree_sums(q, w, c, k, a, a, part_lo, rows_lo, c_split, part_hi, rows_hi, a, a, BF16, None)
+
+    def gram(c=32, k=32, m=37, dtype=BF16, a_mean=a):
+        return lib.mvf_bn_train_stats_gram(a, a_mean, a, m, c, k, a, a, C.c_float(1e-5), C.c_float(0.1), a, a, a, a, a, a, dtype, None)
+
+    rows = [("prep", EINVAL, lambda i=i: prep(ptrs=[None if j == i else a for j in range(7)])) for i in range(7)]        # a NULL among the nine pointers ...
+    rows += [
+        ("prep", EINVAL, lambda: prep(w_out=None)),                                                                      # ... (w_out; bias_out is ptrs[6])
+        ("prep", EINVAL, lambda: prep(m=0)),
+        ("prep", EUNSUPPORTED, lambda: prep(dtype=F32)),
+        ("prep", ESHAPE, lambda: prep(c=96)),
+        ("prep", ESHAPE, lambda: prep(c=192)),                                                                           # a multiple of 64, not of 256
+        ("prep", ESHAPE, lambda: prep(c=4352)),                                                                          # 17 x 256: past the 64 KiB of LDS
+        ("prep", ESHAPE, lambda: prep(k=48)),
+        ("prep", EINVAL, lambda: prep(w_out=off(8))),
+        ("wgrad", ESHAPE, lambda: wgrad(k=32)),
+        ("wgrad", ESHAPE, lambda: wgrad(c=48)),
+        ("wgrad", EINVAL, lambda: wgrad(gram=off(4))),
+        ("wgrad", EUNSUPPORTED, lambda: wgrad(dtype=F32)),
+        ("sums", ESHAPE, lambda: sums(k=6)),
+        ("sums", ESHAPE, lambda: sums(c_split=-1)),
+        ("sums", ESHAPE, lambda: sums(c_split=9)),
+        ("sums", EINVAL, lambda: sums(part_lo=None)),
+        ("sums", EINVAL, lambda: sums(rows_lo=0)),
+        ("sums", EINVAL, lambda: sums(part_hi=None)),
+        ("sums", EINVAL, lambda: sums(q=off(4))),
+        ("sums", EINVAL, lambda: sums(w=off(2))),
+        ("stats_gram", ESHAPE, lambda: gram(c=48)),
+        ("stats_gram", ESHAPE, lambda: gram(k=48)),
+        ("stats_gram", EINVAL, lambda: gram(a_mean=off(4))),
+        ("stats_gram", EUNSUPPORTED, lambda: gram(dtype=F32)),
+    ]
+    for who, rc_want, call in rows:
+        rc = call()
+        err = lib.mvf_last_error()
+        assert rc == rc_want, (who, rc, rc_want, err)
+        assert who.encode() in err, (who, err)
