@@ -140,6 +140,21 @@ class StatSegment(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("first", C.c_long)]
 
 
+# Every entry point that launches nothing: sizes, row / split counts, tile and split plans, the host-side launch records, the ABI version and the error
+# text.  Their return value is an answer, not a status, so a launch plan never holds them (launch_plan.RecordingLib calls them and records nothing); every
+# declared function that does not return a status must be named here (tests/test_abi_cpu.py).
+QUERIES = frozenset((
+    "mvf_abi_version", "mvf_last_error",
+    "mvf_fwd_train_workspace_bytes", "mvf_bwd_workspace_bytes", "mvf_conv2d_workspace_bytes", "mvf_conv2d_wgrad_workspace_bytes", "mvf_bn_workspace_bytes",
+    "mvf_bn_bwd_wgrad_slab_bytes", "mvf_nhwc_tapgrad_workspace_bytes", "mvf_sgd_workspace_bytes", "mvf_adamw_workspace_bytes", "mvf_lamb_workspace_bytes",
+    "mvf_flat_stats_workspace_bytes", "mvf_metrics_state_words",
+    "mvf_conv2d_stats_rows", "mvf_nhwc_stencil_stats_rows", "mvf_maxpool_bwd_sums_rows",
+    "mvf_bn_bwd_wgrad_splits", "mvf_conv1x1_bwd_fused_splits", "mvf_nhwc_stencil_tile_plan",
+    "mvf_conv2d_last_launch", "mvf_conv2d_wgrad_last_launch", "mvf_bn_last_launch", "mvf_nhwc_stencil_last_launch", "mvf_nhwc_tapgrad_last_launch",
+    "mvf_trn_head_last_launch",
+))
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(

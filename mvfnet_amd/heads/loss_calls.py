@@ -1,8 +1,9 @@
 """Which loss entry point of the train head a step calls, and with which arguments: one place for TrainEngine._forward (the fused forms),
 TrainEngine._trn_head_forward and TSNClsHead.loss (the stand-alone forms).
 
-Every function takes the library object from its caller and looks the entry point up on it at call time: the train engine swaps its `lib` for
-launch_plan.RecordingLib while a step is recorded, and tests replace it.  This module therefore imports no library of its own.
+Every function takes the library handle from its caller and looks the entry point up on it at call time.  The train engine passes its own handle
+(`self.lib`: the loaded library, or for the one engine inside launch_plan.recording() the RecordingLib that also records the call; tests install a
+stand-in the same way), TSNClsHead.loss the loaded library.  This module therefore imports no library of its own.
 """
 import ctypes as C
 

@@ -3,12 +3,14 @@
 The train engine issues ~650 library calls per step from Python, always the same ones with the same arguments (persistent buffers, memoised descriptors): ~4 ms
 of host time per step, half of a 9 ms step at the reference's own batch size (12 clips per GPU: configs/MVFNet/K400/mvf_kinetics400_2d_rgb_r50_dense.py:121-123;
 one step = batch_processor + DistOptimizerHook.after_train_iter, codes/core/train.py:45-60, codes/core/dist_utils.py:61-67).  A plan is built by running ONE
-eager step with every library call routed through `RecordingLib` (the call is made as usual AND appended to the plan) and every cross-stream ordering made through
-`Recorder.wait` / `mark` / `wait_mark`; it is accepted once a second recording of the next step is identical to it (same calls, same arguments).  A replay patches
+eager step inside `recording(eng)`: that engine's library handle (`eng.lib`, which every launch made on its behalf goes through) is a `RecordingLib` for the
+duration (the call is made as usual AND appended to the plan) and its cross-stream orderings go through `Recorder.wait` / `mark` / `wait_mark`; no other engine
+of the process is touched.  The plan is accepted once a second recording of the next step is identical to it (same calls, same arguments).  A replay patches
 the few arguments that legitimately change -- input batch, labels, dropout mask, loss tensor -- and hands the table to C.  Work that must stay in Python (a
 collective in the middle of backward) cuts the plan into segments with a callback in between.  No kernel, argument or stream order differs from the eager step:
 results are bit-identical (tests/test_launch_plan_gpu.py).
 """
+import contextlib
 import ctypes as C
 
 import torch
@@ -16,13 +18,6 @@ import torch
 from . import _lib
 
 CALL, RECORD, WAIT = 0, 1, 2
-# entry points that launch nothing (sizes, plans): called as usual while recording, never part of a plan
-_PURE_SUFFIXES = ("_bytes", "_rows", "_splits", "_plan")
-_PURE = {"mvf_last_error", "mvf_abi_version"}
-
-
-def _is_pure(name):
-    return name in _PURE or name.endswith(_PURE_SUFFIXES)
 
 
 class Recorder(object):
@@ -94,26 +89,47 @@ class Recorder(object):
 
 
 class RecordingLib(object):
-    """Stands in for _lib.lib while a step is recorded: every call is made AND recorded."""
+    """Stands in for one engine's library handle `lib` while a step is recorded: every call is made AND recorded, except the entry points that launch nothing
+    (_lib.QUERIES), which are only made.  Anything else must return a status (mvf_plan_run reads every callee's return value as one): a function that does
+    not makes the step unsupported."""
 
-    def __init__(self, rec):
+    def __init__(self, rec, lib):
         self._rec = rec
+        self._lib = lib
         self._fns = {}
 
     def __getattr__(self, name):
         w = self._fns.get(name)
         if w is None:
-            fn = getattr(_lib.lib, name)
-            if _is_pure(name):
+            fn = getattr(self._lib, name)
+            if name in _lib.QUERIES:
                 w = fn
             else:
                 rec = self._rec
+                if fn.restype is not C.c_int:
+                    rec.unsupported = "%s does not return a status and is not declared in _lib.QUERIES" % name
 
                 def w(*args, _fn=fn, _name=name):
                     rec.call(_name, _fn, args)
                     return _fn(*args)
             self._fns[name] = w
         return w
+
+
+@contextlib.contextmanager
+def recording(eng):
+    """with recording(eng) as rec: every library call and stream ordering `eng` makes inside is also appended to rec.  The stand-in and the recorder are
+    INSTANCE attributes of that one engine; on exit (an exception included) they are removed and the class defaults (the loaded library, no recorder) show
+    through again.  (A stand-in a test had installed on the instance is bypassed for the block, as the recorded calls go to the class's library, and put back.)"""
+    rec = Recorder()
+    shadowed = vars(eng).get("lib")
+    eng.lib, eng._rec = RecordingLib(rec, type(eng).lib), rec
+    try:
+        yield rec
+    finally:
+        del eng.lib, eng._rec
+        if shadowed is not None:
+            eng.lib = shadowed
 
 
 class Plan(object):

@@ -21,7 +21,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import ConvDesc, MvfDesc, check, lib
+from ._lib import ConvDesc, MvfDesc, check      # (no `lib` here: every launch goes through its engine's handle, _ParamStore.lib)
 from .heads import loss_calls
 
 F32 = _lib.MVF_F32
@@ -47,12 +47,16 @@ def MvfDesc(*a):       # noqa: F811
     return d
 
 
+# _stats_rows and _conv_ws below only ask the library for sizes (_lib.QUERIES: nothing is launched, nothing would be recorded), and what they cache is shared
+# by every engine of the process: they stay on the package's library instead of taking an engine's handle.
+
+
 def _stats_rows(d):
     # kept ON the descriptor object (not in a table keyed by id(d): a descriptor built outside the memo and collected would hand its id -- and a stale row
     # count, i.e. an undersized partial-sum buffer -- to the next object allocated there)
     r = d.__dict__.get("_rows")
     if r is None:
-        r = d._rows = lib.mvf_conv2d_stats_rows(C.byref(d))
+        r = d._rows = _lib.lib.mvf_conv2d_stats_rows(C.byref(d))
     return r
 
 
@@ -106,7 +110,7 @@ def _conv_ws(device):
     key = (str(device), h.value)
     ws = _SIDE_WS.get(key)
     if ws is None:
-        ws = torch.empty(lib.mvf_conv2d_workspace_bytes(None), dtype=torch.uint8, device=device)
+        ws = torch.empty(_lib.lib.mvf_conv2d_workspace_bytes(None), dtype=torch.uint8, device=device)
         _SIDE_WS[key] = ws
     return ws
 
@@ -138,7 +142,7 @@ class _BN(object):
 
     def use_running_stats(self):
         """Coefficients of a frozen-statistics BN for this step: mean / invstd from the running buffers, folded scale / shift."""
-        check(lib.mvf_bn_fold(_p(self.gamma), _p(self.beta), _p(self.mod.running_mean), _p(self.mod.running_var), C.c_float(self.eps), self.c,
+        check(self.eng.lib.mvf_bn_fold(_p(self.gamma), _p(self.beta), _p(self.mod.running_mean), _p(self.mod.running_var), C.c_float(self.eps), self.c,
                               _p(self.scale), _p(self.shift), _st()), "mvf_bn_fold")
         self.mean.copy_(self.mod.running_mean)
         torch.rsqrt(self.mod.running_var + self.eps, out=self.invstd)
@@ -148,15 +152,15 @@ class _BN(object):
     def stats(self, z, m, eng):
         if self.frozen:
             return self.use_running_stats()
-        ws = eng.workspace(lib.mvf_bn_workspace_bytes(m, self.c))
-        check(lib.mvf_bn_train_stats(_p(z), m, self.c, _p(self.gamma), _p(self.beta), C.c_float(self.eps), C.c_float(self.momentum),
+        ws = eng.workspace(self.eng.lib.mvf_bn_workspace_bytes(m, self.c))
+        check(self.eng.lib.mvf_bn_train_stats(_p(z), m, self.c, _p(self.gamma), _p(self.beta), C.c_float(self.eps), C.c_float(self.momentum),
                                      _p(self.mod.running_mean), _p(self.mod.running_var), _p(self.mean), _p(self.invstd), _p(self.scale),
                                      _p(self.shift), _p(ws), ws.numel(), eng.dt, _st()), "mvf_bn_train_stats")
         self._count()
 
     def finalize(self, part, nblk, m):
         """Batch statistics from the per-tile partial sums the conv epilogue produced (same K = old running mean)."""
-        check(lib.mvf_bn_train_finalize(_p(part), nblk, m, self.c, _p(self.gamma), _p(self.beta), C.c_float(self.eps), C.c_float(self.momentum),
+        check(self.eng.lib.mvf_bn_train_finalize(_p(part), nblk, m, self.c, _p(self.gamma), _p(self.beta), C.c_float(self.eps), C.c_float(self.momentum),
                                         _p(self.mod.running_mean), _p(self.mod.running_var), _p(self.mean), _p(self.invstd), _p(self.scale),
                                         _p(self.shift), _st()), "mvf_bn_train_finalize")
         self._count()
@@ -173,7 +177,7 @@ class _BN(object):
         """out = act(bn(z) [+ residual]); bits=True also keeps the sign bits of out ([m][c/4] bytes) for the backward masks."""
         out = self.eng.buf((id(self), "apply"), z.shape, z.dtype)
         sb = self.eng.buf((id(self), "bits"), (m, self.c // 4), torch.uint8) if bits else None
-        check(lib.mvf_bn_apply_bits(_p(z), m, self.c, _p(self.scale), _p(self.shift), _p(residual), _p(rbn.scale if rbn else None),
+        check(self.eng.lib.mvf_bn_apply_bits(_p(z), m, self.c, _p(self.scale), _p(self.shift), _p(residual), _p(rbn.scale if rbn else None),
                                     _p(rbn.shift if rbn else None), act, _p(out), _p(sb), self.eng.dt, _st()), "mvf_bn_apply")
         return (out, sb) if bits else out
 
@@ -181,8 +185,8 @@ class _BN(object):
         """[r5] out = act(bn(z)) + the column means of what is stored into mean_out -- conv3's a_mean for the Gram form of bn3's statistics
         (_TConv.gram_stats) without a pass over a2."""
         out = self.eng.buf((id(self), "apply"), z.shape, z.dtype)
-        ws = self.eng.workspace(max(lib.mvf_bn_workspace_bytes(m, self.c), 4608 * self.c * 8))        # (the apply plan aims at 4096 workgroups: one partial row each)
-        check(lib.mvf_bn_apply_colmeans(_p(z), m, self.c, _p(self.scale), _p(self.shift), act, _p(out), _p(mean_out), _p(ws), ws.numel(), self.eng.dt, _st()),
+        ws = self.eng.workspace(max(self.eng.lib.mvf_bn_workspace_bytes(m, self.c), 4608 * self.c * 8))        # (the apply plan aims at 4096 workgroups: one partial row each)
+        check(self.eng.lib.mvf_bn_apply_colmeans(_p(z), m, self.c, _p(self.scale), _p(self.shift), act, _p(out), _p(mean_out), _p(ws), ws.numel(), self.eng.dt, _st()),
               "mvf_bn_apply_colmeans")
         return out
 
@@ -197,10 +201,10 @@ class _BN(object):
     def backward_pair(a, b, g, g_pitch, za, zb, m, eng, bits):
         """Backward of both BatchNorms of a downsample block, out = relu(a(za) + b(zb)): the shared g and sign bits are read once
         (mvf_bn_bwd_pair).  Returns (dza, dzb); results equal a.backward(...), b.backward(...) bit for bit."""
-        nb = lib.mvf_bn_workspace_bytes(m, a.c)
+        nb = eng.lib.mvf_bn_workspace_bytes(m, a.c)
         ws = eng.workspace(2 * nb)
         dza, dzb = eng.buf((id(a), "dz"), za.shape, za.dtype), eng.buf((id(b), "dz"), zb.shape, zb.dtype)
-        check(lib.mvf_bn_bwd_pair(_p(g), g_pitch, _p(za), _p(zb), _p(bits), m, a.c, _p(a.gamma), _p(a.mean), _p(a.invstd), _p(a.dgamma), _p(a.dbeta),
+        check(eng.lib.mvf_bn_bwd_pair(_p(g), g_pitch, _p(za), _p(zb), _p(bits), m, a.c, _p(a.gamma), _p(a.mean), _p(a.invstd), _p(a.dgamma), _p(a.dbeta),
                                   _p(b.gamma), _p(b.mean), _p(b.invstd), _p(b.dgamma), _p(b.dbeta), _p(dza), _p(dzb), _p(ws), ws.numel(), eng.dt, _st()),
               "mvf_bn_bwd_pair")
         return dza, dzb
@@ -215,11 +219,11 @@ class _BN(object):
     def _apply_bwd_wgrad(self, g, g_pitch, z, m, eng, mask_mode, ymask, conv, x, x_pitch):
         """Exactly one fused launch (bench.py brackets this call with HIP events) + the slab reduce handed to the side stream."""
         dz = eng.buf((id(self), "dz"), z.shape, z.dtype)
-        ns = lib.mvf_bn_bwd_wgrad_splits(m, self.c, conv.cin, 1, mask_mode)
-        nb = lib.mvf_bn_bwd_wgrad_slab_bytes(m, self.c, conv.cin, 1, mask_mode)
+        ns = self.eng.lib.mvf_bn_bwd_wgrad_splits(m, self.c, conv.cin, 1, mask_mode)
+        nb = self.eng.lib.mvf_bn_bwd_wgrad_slab_bytes(m, self.c, conv.cin, 1, mask_mode)
         slabs = eng.buf((id(conv), "wslab"), (nb // 4,), torch.float32)
         sg, sb = (self._zero, self._zero) if self.frozen else (self.dgamma, self.dbeta)
-        check(lib.mvf_bn_bwd_apply_wgrad(_p(g), g_pitch, _p(z), _p(ymask) if mask_mode == 4 else None, m, self.c, _p(self.gamma), _p(self.mean), _p(self.invstd),
+        check(self.eng.lib.mvf_bn_bwd_apply_wgrad(_p(g), g_pitch, _p(z), _p(ymask) if mask_mode == 4 else None, m, self.c, _p(self.gamma), _p(self.mean), _p(self.invstd),
                                          _p(self.scale), _p(self.shift), _p(sg), _p(sb), mask_mode, _p(dz), _p(x), x_pitch, conv.cin, _p(slabs), nb,
                                          eng.dt, _st()), "mvf_bn_bwd_apply_wgrad")
         conv.slab_reduce(slabs, ns, eng)
@@ -228,15 +232,15 @@ class _BN(object):
     @staticmethod
     def backward_pair_wgrad(a, b, g, g_pitch, za, zb, m, eng, bits, conv_a, xa, xa_pitch, conv_b, xb, xb_pitch):
         """[r4] backward_pair with conv_a's (and, when xb is given, conv_b's) weight gradient inside the apply pass (mvf_bn_bwd_pair_wgrad)."""
-        nbw = lib.mvf_bn_workspace_bytes(m, a.c)
+        nbw = eng.lib.mvf_bn_workspace_bytes(m, a.c)
         ws = eng.workspace(2 * nbw)
         dza, dzb = eng.buf((id(a), "dz"), za.shape, za.dtype), eng.buf((id(b), "dz"), zb.shape, zb.dtype)
         k = conv_a.cin
-        ns = lib.mvf_bn_bwd_wgrad_splits(m, a.c, k, 2, 4)
-        nb = lib.mvf_bn_bwd_wgrad_slab_bytes(m, a.c, k, 2, 4)
+        ns = eng.lib.mvf_bn_bwd_wgrad_splits(m, a.c, k, 2, 4)
+        nb = eng.lib.mvf_bn_bwd_wgrad_slab_bytes(m, a.c, k, 2, 4)
         sa = eng.buf((id(conv_a), "wslab"), (nb // 4,), torch.float32)
         sb = eng.buf((id(conv_b), "wslab"), (nb // 4,), torch.float32) if xb is not None else None
-        check(lib.mvf_bn_bwd_pair_wgrad(_p(g), g_pitch, _p(za), _p(zb), _p(bits), m, a.c, _p(a.gamma), _p(a.mean), _p(a.invstd), _p(a.dgamma), _p(a.dbeta),
+        check(eng.lib.mvf_bn_bwd_pair_wgrad(_p(g), g_pitch, _p(za), _p(zb), _p(bits), m, a.c, _p(a.gamma), _p(a.mean), _p(a.invstd), _p(a.dgamma), _p(a.dbeta),
                                         _p(b.gamma), _p(b.mean), _p(b.invstd), _p(b.dgamma), _p(b.dbeta), _p(dza), _p(dzb), _p(xa), xa_pitch,
                                         _p(xb), xb_pitch, k, _p(sa), _p(sb), nb, _p(ws), ws.numel(), eng.dt, _st()), "mvf_bn_bwd_pair_wgrad")
         conv_a.slab_reduce(sa, ns, eng)
@@ -245,8 +249,8 @@ class _BN(object):
         return dza, dzb
 
     def _reduce(self, g, g_pitch, z, m, eng, mask_mode, ymask, gm_out):
-        ws = eng.workspace(lib.mvf_bn_workspace_bytes(m, self.c))
-        check(lib.mvf_bn_bwd_reduce(_p(g), g_pitch, _p(z), _p(ymask), m, self.c, _p(self.mean), _p(self.invstd), _p(self.scale),
+        ws = eng.workspace(self.eng.lib.mvf_bn_workspace_bytes(m, self.c))
+        check(self.eng.lib.mvf_bn_bwd_reduce(_p(g), g_pitch, _p(z), _p(ymask), m, self.c, _p(self.mean), _p(self.invstd), _p(self.scale),
                                     _p(self.shift), mask_mode, _p(gm_out), _p(self.dgamma), _p(self.dbeta), _p(ws), ws.numel(), eng.dt, _st()),
               "mvf_bn_bwd_reduce")
 
@@ -256,7 +260,7 @@ class _BN(object):
         # frozen statistics: mean and variance do not depend on z, so dz = gamma * invstd * (masked g) -- the batch-statistics
         # formula with its two correction sums set to zero (dgamma / dbeta themselves are still the real sums)
         sg, sb = (self._zero, self._zero) if self.frozen else (self.dgamma, self.dbeta)
-        check(lib.mvf_bn_bwd_apply_masked(_p(src), pitch, _p(z), _p(ymask) if mode in (1, 4) else None, m, self.c, _p(self.gamma), _p(self.mean),
+        check(self.eng.lib.mvf_bn_bwd_apply_masked(_p(src), pitch, _p(z), _p(ymask) if mode in (1, 4) else None, m, self.c, _p(self.gamma), _p(self.mean),
                                           _p(self.invstd), _p(self.scale), _p(self.shift), _p(sg), _p(sb), mode, _p(dz), eng.dt,
                                           _st()), "mvf_bn_bwd_apply")
         return dz
@@ -285,10 +289,10 @@ class _TConv(object):
 
     def pack(self, need_dgrad=True):
         if self.stem:
-            check(lib.mvf_pack_conv_weight(_p(self.w), self.cout, self.cin, self.kh, self.kw, 8, 4, None, _p(self.wp), self.eng.dt, _st()), "pack")
+            check(self.eng.lib.mvf_pack_conv_weight(_p(self.w), self.cout, self.cin, self.kh, self.kw, 8, 4, None, _p(self.wp), self.eng.dt, _st()), "pack")
             return
         if self.wp is not self.w:
-            check(lib.mvf_pack_conv_weight(_p(self.w), self.cout, self.cin, self.kh, self.kw, self.kw, self.cin, None, _p(self.wp), self.eng.dt, _st()), "pack")
+            check(self.eng.lib.mvf_pack_conv_weight(_p(self.w), self.cout, self.cin, self.kh, self.kw, self.kw, self.cin, None, _p(self.wp), self.eng.dt, _st()), "pack")
         if need_dgrad:
             self.pack_dgrad()
 
@@ -302,7 +306,7 @@ class _TConv(object):
 
     def pack_dgrad(self):
         if not self.stem:
-            check(lib.mvf_pack_conv_weight_dgrad(_p(self.w), self.cout, self.cin, self.kh, self.kw, _p(self.wd), self.eng.dt, _st()), "pack_dgrad")
+            check(self.eng.lib.mvf_pack_conv_weight_dgrad(_p(self.w), self.cout, self.cin, self.kh, self.kw, _p(self.wd), self.eng.dt, _st()), "pack_dgrad")
 
     def desc(self, n, h, w, ho, wo, x_pitch, split_c=0):
         if self.stem:
@@ -356,7 +360,7 @@ class _TConv(object):
         rows = _stats_rows(d)
         part = self.eng.buf((id(self), "bwpart"), (rows, self.cout, 2), torch.float32)
         self.launch_bwd_sums(d, a_in, g, bits, bn, part, ws)
-        check(lib.mvf_bn_bwd_finalize(_p(part), rows, self.cout, _p(bn.dgamma), _p(bn.dbeta), _st()), "mvf_bn_bwd_finalize")
+        check(self.eng.lib.mvf_bn_bwd_finalize(_p(part), rows, self.cout, _p(bn.dgamma), _p(bn.dbeta), _st()), "mvf_bn_bwd_finalize")
         dz = self.eng.buf((id(bn), "dz"), (m, self.cout))
         self.launch_bwd_apply(d, a_in, g, bits, bn, dz, ws)
         return dz
@@ -364,7 +368,7 @@ class _TConv(object):
     def bwd_fused_ok(self, m):
         """[r4] The one-pass backward of a z3-free block's last conv is built for this shape (bf16, 64 -> 256 channels, pointwise, stride 1)."""
         return (self.eng.tdtype == torch.bfloat16 and self.kh == 1 and self.kw == 1 and self.stride == 1 and not self.stem and
-                lib.mvf_conv1x1_bwd_fused_splits(m, self.cout, self.cin) > 0)
+                self.eng.lib.mvf_conv1x1_bwd_fused_splits(m, self.cout, self.cin) > 0)
 
     def bwd_fused(self, a_in, g, bits, n, h, w, bn, bn_in=None, z_in=None, a_pitch=None, sums_done=False):
         """[r4] bwd_recompute + dgrad_bnsums + wgrad of a z3-free block's last conv with dz3 kept on chip (mvf_conv1x1_bwd_fused): bn's dgamma / dbeta
@@ -376,57 +380,57 @@ class _TConv(object):
         m = n * h * w
         ws = _conv_ws(a_in.device)
         rows = _stats_rows(d)
-        ns = lib.mvf_conv1x1_bwd_fused_splits(m, self.cout, self.cin)
+        ns = self.eng.lib.mvf_conv1x1_bwd_fused_splits(m, self.cout, self.cin)
         if not sums_done and self.eng.pair_ds_sums & 2:          # [r4] the one-branch form of csrc/pw_sums_pair.hip instead of pw_sums.hip
             part = self.eng.buf((id(self), "bwpart_pair"), (self.cout, 2 * ns, 2), torch.float32)
             self.launch_bwd_sums1(m, a_in, pitch, g, bits, bn, part, ns)
-            check(lib.mvf_bn_bwd_finalize(_p(part), 2 * ns, self.cout, _p(bn.dgamma), _p(bn.dbeta), _st()), "mvf_bn_bwd_finalize")
+            check(self.eng.lib.mvf_bn_bwd_finalize(_p(part), 2 * ns, self.cout, _p(bn.dgamma), _p(bn.dbeta), _st()), "mvf_bn_bwd_finalize")
         elif not sums_done:        # (a downsample block takes both branches' sums in one pass over g: _TBlock.backward)
             part = self.eng.buf((id(self), "bwpart"), (rows, self.cout, 2), torch.float32)
             self.launch_bwd_sums(d, a_in, g, bits, bn, part, ws)
-            check(lib.mvf_bn_bwd_finalize(_p(part), rows, self.cout, _p(bn.dgamma), _p(bn.dbeta), _st()), "mvf_bn_bwd_finalize")
+            check(self.eng.lib.mvf_bn_bwd_finalize(_p(part), rows, self.cout, _p(bn.dgamma), _p(bn.dbeta), _st()), "mvf_bn_bwd_finalize")
         dx = self.eng.buf((id(self), "dx"), (m, self.cin))
         spart = self.eng.buf((id(self), "bnsums_fused"), (self.cin, 2 * ns, 2), torch.float32) if bn_in is not None else None
         slabs = self.eng.buf((id(self), "wslab"), (ns * self.cout * self.cin,), torch.float32)
         self.launch_bwd_fused(m, a_in, g, bits, bn, bn_in, z_in, dx, spart, ns, slabs, pitch)
         if bn_in is not None:
-            check(lib.mvf_bn_bwd_finalize(_p(spart), 2 * ns, self.cin, _p(bn_in.dgamma), _p(bn_in.dbeta), _st()), "bn bwd finalize")
+            check(self.eng.lib.mvf_bn_bwd_finalize(_p(spart), 2 * ns, self.cin, _p(bn_in.dgamma), _p(bn_in.dbeta), _st()), "bn bwd finalize")
         self.slab_reduce(slabs, ns, self.eng)
         return dx
 
     def launch_bwd_sums1(self, m, a_in, a_pitch, g, bits, bn, part, ns):
         """Exactly one launch (bench.py brackets this call with HIP events)."""
-        check(lib.mvf_conv1x1_bnbwd_sums_pair(_p(a_in), a_pitch, _p(self.wp), None, 0, None, _p(g), self.cout, _p(bits), m, self.cout, self.cin, _p(bn.mean),
+        check(self.eng.lib.mvf_conv1x1_bnbwd_sums_pair(_p(a_in), a_pitch, _p(self.wp), None, 0, None, _p(g), self.cout, _p(bits), m, self.cout, self.cin, _p(bn.mean),
                                               _p(bn.invstd), None, None, _p(part), None, 2 * ns, self.eng.dt, _st()), "bn backward sums (one branch)")
 
     def launch_bwd_fused(self, m, a_in, g, bits, bn, bn_in, z_in, dx, spart, ns, slabs, a_pitch=None):
         """Exactly one launch (bench.py brackets this call with HIP events)."""
         i = bn_in
-        check(lib.mvf_conv1x1_bwd_fused(_p(a_in), a_pitch or self.cin, _p(self.wp), _p(g), self.cout, _p(bits), m, self.cout, self.cin, _p(bn.gamma), _p(bn.mean),
+        check(self.eng.lib.mvf_conv1x1_bwd_fused(_p(a_in), a_pitch or self.cin, _p(self.wp), _p(g), self.cout, _p(bits), m, self.cout, self.cin, _p(bn.gamma), _p(bn.mean),
                                         _p(bn.invstd), _p(bn.dgamma), _p(bn.dbeta), _p(z_in) if i is not None else None, _p(i.mean) if i else None,
                                         _p(i.invstd) if i else None, _p(i.scale) if i else None, _p(i.shift) if i else None,
                                         _p(dx), _p(spart), 2 * ns, _p(slabs), slabs.numel() * 4, self.eng.dt, _st()), "conv1x1 backward fused")
 
     def launch_bwd_sums(self, d, a_in, g, bits, bn, part, ws):
-        check(lib.mvf_conv2d_nhwc_fwd_bnbwd_sums(C.byref(d), _p(a_in), None, _p(self.wp), _p(g), _p(bits), _p(bn.mean), _p(bn.invstd), _p(part),
+        check(self.eng.lib.mvf_conv2d_nhwc_fwd_bnbwd_sums(C.byref(d), _p(a_in), None, _p(self.wp), _p(g), _p(bits), _p(bn.mean), _p(bn.invstd), _p(part),
                                                  _p(ws), ws.numel(), _st()), "conv + bn backward sums")
 
     def launch_bwd_apply(self, d, a_in, g, bits, bn, dz, ws):
-        check(lib.mvf_conv2d_nhwc_fwd_bnbwd_apply(C.byref(d), _p(a_in), None, _p(self.wp), _p(g), _p(bits), _p(bn.gamma), _p(bn.mean), _p(bn.invstd),
+        check(self.eng.lib.mvf_conv2d_nhwc_fwd_bnbwd_apply(C.byref(d), _p(a_in), None, _p(self.wp), _p(g), _p(bits), _p(bn.gamma), _p(bn.mean), _p(bn.invstd),
                                                   _p(bn.dgamma), _p(bn.dbeta), _p(dz), _p(ws), ws.numel(), _st()), "conv + bn backward apply")
 
     def launch_fwd_apply(self, d, x, bn, residual, rbn, out, bits, ws):
         """Exactly one implicit-GEMM launch (bench.py brackets this call with HIP events)."""
-        check(lib.mvf_conv2d_nhwc_fwd_bnapply(C.byref(d), _p(x), None, _p(self.wp), _p(bn.scale), _p(bn.shift), _p(residual),
+        check(self.eng.lib.mvf_conv2d_nhwc_fwd_bnapply(C.byref(d), _p(x), None, _p(self.wp), _p(bn.scale), _p(bn.shift), _p(residual),
                                               _p(rbn.scale if rbn else None), _p(rbn.shift if rbn else None), _p(out), _p(bits),
                                               _p(ws), ws.numel(), _st()), "conv fwd + bn apply")
 
     def launch_fwd(self, d, x, x2, z, ws, part, shift):
         """Exactly one implicit-GEMM launch (bench.py brackets this call with HIP events)."""
         if part is None:
-            check(lib.mvf_conv2d_nhwc_fwd_ws(C.byref(d), _p(x), _p(x2), _p(self.wp), None, None, _p(z), _p(ws), ws.numel(), _st()), "conv fwd")
+            check(self.eng.lib.mvf_conv2d_nhwc_fwd_ws(C.byref(d), _p(x), _p(x2), _p(self.wp), None, None, _p(z), _p(ws), ws.numel(), _st()), "conv fwd")
         else:
-            check(lib.mvf_conv2d_nhwc_fwd_stats(C.byref(d), _p(x), _p(x2), _p(self.wp), _p(z), _p(part), _p(shift), _p(ws), ws.numel(), _st()),
+            check(self.eng.lib.mvf_conv2d_nhwc_fwd_stats(C.byref(d), _p(x), _p(x2), _p(self.wp), _p(z), _p(part), _p(shift), _p(ws), ws.numel(), _st()),
                   "conv fwd+stats")
 
     def wgrad(self, dz, x, n, h, w, ho, wo, eng, x_pitch=None, x2=None, split_c=0, on_main=False):
@@ -434,16 +438,16 @@ class _TConv(object):
         independent given dz) and fills the CUs the other chain's partial tile waves leave idle."""
         d = self.desc(n, h, w, ho, wo, x_pitch or self.cin, split_c)
         kwr, cinr, kwp, cinp = (self.kw, self.cin, 8, 4) if self.stem else (self.kw, self.cin, self.kw, self.cin)
-        nbytes = lib.mvf_conv2d_wgrad_workspace_bytes(C.byref(d))
+        nbytes = self.eng.lib.mvf_conv2d_wgrad_workspace_bytes(C.byref(d))
         side = None if on_main else eng.side_stream()
         if side is None:
             ws = eng.workspace(nbytes)
-            check(lib.mvf_conv2d_nhwc_wgrad(C.byref(d), _p(dz), _p(x), _p(x2), kwr, cinr, kwp, cinp, _p(self.dw), _p(ws), ws.numel(), _st()), "conv wgrad")
+            check(self.eng.lib.mvf_conv2d_nhwc_wgrad(C.byref(d), _p(dz), _p(x), _p(x2), kwr, cinr, kwp, cinp, _p(self.dw), _p(ws), ws.numel(), _st()), "conv wgrad")
             return
         ws = eng.workspace(nbytes, side=True)
 
         def launch():
-            check(lib.mvf_conv2d_nhwc_wgrad(C.byref(d), _p(dz), _p(x), _p(x2), kwr, cinr, kwp, cinp, _p(self.dw), _p(ws), ws.numel(), _st()), "conv wgrad")
+            check(self.eng.lib.mvf_conv2d_nhwc_wgrad(C.byref(d), _p(dz), _p(x), _p(x2), kwr, cinr, kwp, cinp, _p(self.dw), _p(ws), ws.numel(), _st()), "conv wgrad")
         eng.on_side(launch)
         # dz / x / x2 are persistent engine buffers (eng.buf) or tensors the caller keeps alive until join_side()
 
@@ -451,12 +455,12 @@ class _TConv(object):
         """[r4] This conv's weight gradient can ride in the BatchNorm-backward apply pass that forms its dz (bf16 storage, pointwise,
         stride 1, a c x cin accumulator that fits one workgroup: csrc/bnbwd_wgrad.hip)."""
         return (eng.tdtype == torch.bfloat16 and self.kh == 1 and self.kw == 1 and self.stride == 1 and not self.stem and c == self.cout and
-                lib.mvf_bn_bwd_wgrad_splits(m, c, self.cin, nbn, mask_mode) > 0)
+                self.eng.lib.mvf_bn_bwd_wgrad_splits(m, c, self.cin, nbn, mask_mode) > 0)
 
     def slab_reduce(self, slabs, ns, eng):
         """dw <- fixed-order sum of the fused pass's partial slabs: only feeds the optimizer, so it goes to the side stream."""
         def launch():
-            check(lib.mvf_wgrad_slab_reduce(_p(slabs), ns, self.cout, self.cin, _p(self.dw), _st()), "wgrad slab reduce")
+            check(self.eng.lib.mvf_wgrad_slab_reduce(_p(slabs), ns, self.cout, self.cin, _p(self.dw), _st()), "wgrad slab reduce")
         if eng.side_stream() is None:
             launch()
         else:
@@ -473,12 +477,12 @@ class _TConv(object):
         rows = _stats_rows(d)
         part = self.eng.buf((id(self), "bnsums"), (rows, self.cin, 2), torch.float32)
         self.launch_dgrad_bnsums(d, dz, dx, z, bn, part, ws)
-        check(lib.mvf_bn_bwd_finalize(_p(part), rows, self.cin, _p(bn.dgamma), _p(bn.dbeta), _st()), "bn bwd finalize")
+        check(self.eng.lib.mvf_bn_bwd_finalize(_p(part), rows, self.cin, _p(bn.dgamma), _p(bn.dbeta), _st()), "bn bwd finalize")
         return dx
 
     def launch_dgrad_bnsums(self, d, dz, dx, z, bn, part, ws):
         """Exactly one implicit-GEMM launch (bench.py brackets this call with HIP events)."""
-        check(lib.mvf_conv2d_nhwc_dgrad_bnsums(C.byref(d), _p(dz), _p(self.wd), _p(dx), _p(z), _p(bn.mean), _p(bn.invstd), _p(bn.scale), _p(bn.shift),
+        check(self.eng.lib.mvf_conv2d_nhwc_dgrad_bnsums(C.byref(d), _p(dz), _p(self.wd), _p(dx), _p(z), _p(bn.mean), _p(bn.invstd), _p(bn.scale), _p(bn.shift),
                                                _p(part), _p(ws), ws.numel(), _st()), "conv dgrad+bn sums")
 
     def dgrad(self, dz, n, ho, wo, h, w, residual=None, res_c0=0, res_bits=None, out_gate=None, gsum=None):
@@ -496,14 +500,14 @@ class _TConv(object):
             bn = gsum["bn"]
             rows = _stats_rows(d)
             part = self.eng.buf((id(bn), "gsum_conv"), (self.cin, rows, 2), torch.float32)
-            check(lib.mvf_conv2d_nhwc_fwd_resmask_gate_colsums(C.byref(d), _p(dz), None, _p(self.wd), _p(residual), _p(res_bits), _p(out_gate), _p(dx), _p(part), _p(ws),
+            check(self.eng.lib.mvf_conv2d_nhwc_fwd_resmask_gate_colsums(C.byref(d), _p(dz), None, _p(self.wd), _p(residual), _p(res_bits), _p(out_gate), _p(dx), _p(part), _p(ws),
                                                                ws.numel(), _st()), "conv dgrad (gated output + column sums)")
             bn._s1 = [None, 0, res_c0, part, rows]
         elif out_gate is not None:
-            check(lib.mvf_conv2d_nhwc_fwd_resmask_gate(C.byref(d), _p(dz), None, _p(self.wd), None, _p(residual), _p(res_bits), _p(out_gate), _p(dx), _p(ws),
+            check(self.eng.lib.mvf_conv2d_nhwc_fwd_resmask_gate(C.byref(d), _p(dz), None, _p(self.wd), None, _p(residual), _p(res_bits), _p(out_gate), _p(dx), _p(ws),
                                                        ws.numel(), _st()), "conv dgrad (gated output)")
         else:
-            check(lib.mvf_conv2d_nhwc_fwd_resmask(C.byref(d), _p(dz), None, _p(self.wd), None, _p(residual), _p(res_bits), _p(dx), _p(ws), ws.numel(),
+            check(self.eng.lib.mvf_conv2d_nhwc_fwd_resmask(C.byref(d), _p(dz), None, _p(self.wd), None, _p(residual), _p(res_bits), _p(dx), _p(ws), ws.numel(),
                                                   _st()), "conv dgrad")
         return dx
 
@@ -521,7 +525,7 @@ class _TConv(object):
         bd = eng.buf((id(self), "dzfree_w"), (k, c + k))
         bias = eng.buf((id(self), "dzfree_b"), (k,), torch.float32)
         sg, sb = (frozen_zero, frozen_zero) if frozen_zero is not None else (bn.dgamma, bn.dbeta)
-        check(lib.mvf_bn_bwd_dzfree_prep(_p(self.wd), c, k, _p(bn.gamma), _p(bn.mean), _p(bn.invstd), _p(sg), _p(sb), m, _p(bd), _p(bias), eng.dt, _st()),
+        check(self.eng.lib.mvf_bn_bwd_dzfree_prep(_p(self.wd), c, k, _p(bn.gamma), _p(bn.mean), _p(bn.invstd), _p(sg), _p(sb), m, _p(bd), _p(bias), eng.dt, _st()),
               "bn backward without dz: operands")
         d = ConvDesc(n, h, w, c + k, k, 1, 1, 1, 0, h, w, k, eng.dt, 0, c, c, 0, 0, c)        # x = a_in (pitch k, columns c .. c + k), x2 = gm (pitch c)
         dx = eng.buf((id(self), "dx"), (m, k))
@@ -529,12 +533,12 @@ class _TConv(object):
         rows = _stats_rows(d)
         part = eng.buf((id(self), "bnsums"), (rows, k, 2), torch.float32)
         self.launch_dzfree_dgrad(d, a_in, gm, bd, bias, dx, z_in, bn_in, part, ws)
-        check(lib.mvf_bn_bwd_finalize(_p(part), rows, k, _p(bn_in.dgamma), _p(bn_in.dbeta), _st()), "bn bwd finalize")
+        check(self.eng.lib.mvf_bn_bwd_finalize(_p(part), rows, k, _p(bn_in.dgamma), _p(bn_in.dbeta), _st()), "bn bwd finalize")
         return dx
 
     def launch_dzfree_dgrad(self, d, a_in, gm, bd, bias, dx, z_in, bn_in, part, ws):
         """Exactly one implicit-GEMM launch (bench.py brackets this call with HIP events)."""
-        check(lib.mvf_conv2d_nhwc_dgrad_bnsums_split(C.byref(d), _p(a_in), _p(gm), _p(bd), _p(bias), _p(dx), _p(z_in), _p(bn_in.mean), _p(bn_in.invstd),
+        check(self.eng.lib.mvf_conv2d_nhwc_dgrad_bnsums_split(C.byref(d), _p(a_in), _p(gm), _p(bd), _p(bias), _p(dx), _p(z_in), _p(bn_in.mean), _p(bn_in.invstd),
                                                      _p(bn_in.scale), _p(bn_in.shift), _p(part), _p(ws), ws.numel(), _st()), "conv dgrad on [gm | a] + bn sums")
 
     def dzfree_q_sums(self, gm, a_in, bn, n, h, w, eng):
@@ -543,17 +547,17 @@ class _TConv(object):
         gradient for the channels >= its MVF slice, its transposed stencil for the slice)."""
         c, k = self.cout, self.cin
         d = self.desc(n, h, w, h, w, k, 0)
-        ws = eng.workspace(lib.mvf_conv2d_wgrad_workspace_bytes(C.byref(d)))
+        ws = eng.workspace(self.eng.lib.mvf_conv2d_wgrad_workspace_bytes(C.byref(d)))
         self.launch_q(d, gm, a_in, ws, eng.dzfree_q_wgs)
         lo, rows_lo, c_split, hi, rows_hi = bn._s1
         assert c_split == 0 or lo is not None, "the MVF slice's column sums are missing"
-        check(lib.mvf_bn_bwd_dzfree_sums(_p(self.dw), _p(self.wp), c, k, _p(bn.mean), _p(bn.invstd), _p(lo), rows_lo, c_split, _p(hi), rows_hi, _p(bn.dgamma),
+        check(self.eng.lib.mvf_bn_bwd_dzfree_sums(_p(self.dw), _p(self.wp), c, k, _p(bn.mean), _p(bn.invstd), _p(lo), rows_lo, c_split, _p(hi), rows_hi, _p(bn.dgamma),
                                          _p(bn.dbeta), eng.dt, _st()), "bn backward sums from the weight-gradient GEMM")
         bn._s1 = None
 
     def launch_q(self, d, gm, a_in, ws, wgs):
         """One weight-gradient GEMM + its slab reduce on the launch stream (bench.py brackets this call with HIP events)."""
-        check(lib.mvf_conv2d_nhwc_wgrad_wgs(C.byref(d), _p(gm), _p(a_in), None, self.kw, self.cin, self.kw, self.cin, _p(self.dw), _p(ws), ws.numel(), wgs, _st()),
+        check(self.eng.lib.mvf_conv2d_nhwc_wgrad_wgs(C.byref(d), _p(gm), _p(a_in), None, self.kw, self.cin, self.kw, self.cin, _p(self.dw), _p(ws), ws.numel(), wgs, _st()),
               "conv wgrad (launch stream)")
 
     def gram_ok(self):
@@ -569,15 +573,15 @@ class _TConv(object):
         gram = eng.buf((id(self), "gram"), (k, k), torch.float32)
         amean = eng.buf((id(self), "amean"), (4, k), torch.float32)            # rows: mean, and three outputs of the statistics call nobody reads
         d = ConvDesc(n, h, w, k, k, 1, 1, 1, 0, h, w, k, eng.dt, 0, 0, 0, 0)
-        ws = eng.workspace(max(lib.mvf_conv2d_wgrad_workspace_bytes(C.byref(d)), lib.mvf_bn_workspace_bytes(m, k), (eng.gram_stats_wgs + 8) * k * k * 4))
+        ws = eng.workspace(max(self.eng.lib.mvf_conv2d_wgrad_workspace_bytes(C.byref(d)), self.eng.lib.mvf_bn_workspace_bytes(m, k), (eng.gram_stats_wgs + 8) * k * k * 4))
         if k not in eng._ones:
             eng._ones[k] = (torch.ones(k, device=a_in.device), torch.zeros(k, device=a_in.device))
         one, zero = eng._ones[k]
         self.launch_gram(d, a_in, gram, ws, eng.gram_stats_wgs)
         if not means_done:     # (means_done: the kernel that wrote a_in left its column means in amean[0] -- _BN.apply_colmeans)
-            check(lib.mvf_bn_train_stats(_p(a_in), m, k, _p(one), _p(zero), C.c_float(1e-5), C.c_float(0.1), None, None, _p(amean[0]), _p(amean[1]),
+            check(self.eng.lib.mvf_bn_train_stats(_p(a_in), m, k, _p(one), _p(zero), C.c_float(1e-5), C.c_float(0.1), None, None, _p(amean[0]), _p(amean[1]),
                                          _p(amean[2]), _p(amean[3]), _p(ws), ws.numel(), eng.dt, _st()), "column means")
-        check(lib.mvf_bn_train_stats_gram(_p(gram), _p(amean[0]), _p(self.wp), m, c, k, _p(bn.gamma), _p(bn.beta), C.c_float(bn.eps), C.c_float(bn.momentum),
+        check(self.eng.lib.mvf_bn_train_stats_gram(_p(gram), _p(amean[0]), _p(self.wp), m, c, k, _p(bn.gamma), _p(bn.beta), C.c_float(bn.eps), C.c_float(bn.momentum),
                                           _p(bn.mod.running_mean), _p(bn.mod.running_var), _p(bn.mean), _p(bn.invstd), _p(bn.scale), _p(bn.shift), eng.dt,
                                           _st()), "bn statistics from the Gram matrix")
         bn._count()
@@ -585,7 +589,7 @@ class _TConv(object):
     def launch_gram(self, d, a_in, gram, ws, wgs):
         """One k x k GEMM a^T a (+ its slab reduce) on the launch stream (bench.py brackets this call with HIP events)."""
         k = self.cin
-        check(lib.mvf_conv2d_nhwc_wgrad_wgs(C.byref(d), _p(a_in), _p(a_in), None, 1, k, 1, k, _p(gram), _p(ws), ws.numel(), wgs, _st()), "gram (launch stream)")
+        check(self.eng.lib.mvf_conv2d_nhwc_wgrad_wgs(C.byref(d), _p(a_in), _p(a_in), None, 1, k, 1, k, _p(gram), _p(ws), ws.numel(), wgs, _st()), "gram (launch stream)")
 
     def dzfree_wgrad(self, gm, a_in, bn, n, h, w, eng, frozen_zero=None, q_done=False, gram_done=False):
         """dW = dz^T a_in without dz: Q = gm^T a_in (the usual weight-gradient GEMM, into dw), A2 = a_in^T a_in and the column means of a_in, then the
@@ -596,7 +600,7 @@ class _TConv(object):
         gram = eng.buf((id(self), "gram"), (k, k), torch.float32)
         amean = eng.buf((id(self), "amean"), (4, k), torch.float32)            # rows: mean, and three outputs of the statistics call nobody reads
         d = ConvDesc(n, h, w, k, k, 1, 1, 1, 0, h, w, k, eng.dt, 0, 0, 0, 0)
-        nbytes = max(lib.mvf_conv2d_wgrad_workspace_bytes(C.byref(d)), lib.mvf_bn_workspace_bytes(m, k))
+        nbytes = max(self.eng.lib.mvf_conv2d_wgrad_workspace_bytes(C.byref(d)), self.eng.lib.mvf_bn_workspace_bytes(m, k))
         if k not in eng._ones:
             eng._ones[k] = (torch.ones(k, device=gm.device), torch.zeros(k, device=gm.device))
         one, zero = eng._ones[k]
@@ -606,10 +610,10 @@ class _TConv(object):
 
         def launch():
             if not gram_done:      # (the forward's statistics already left both in place: gram_stats)
-                check(lib.mvf_conv2d_nhwc_wgrad(C.byref(d), _p(a_in), _p(a_in), None, 1, k, 1, k, _p(gram), _p(ws), ws.numel(), _st()), "gram")
-                check(lib.mvf_bn_train_stats(_p(a_in), m, k, _p(one), _p(zero), C.c_float(1e-5), C.c_float(0.1), None, None, _p(amean[0]), _p(amean[1]),
+                check(self.eng.lib.mvf_conv2d_nhwc_wgrad(C.byref(d), _p(a_in), _p(a_in), None, 1, k, 1, k, _p(gram), _p(ws), ws.numel(), _st()), "gram")
+                check(self.eng.lib.mvf_bn_train_stats(_p(a_in), m, k, _p(one), _p(zero), C.c_float(1e-5), C.c_float(0.1), None, None, _p(amean[0]), _p(amean[1]),
                                              _p(amean[2]), _p(amean[3]), _p(ws), ws.numel(), eng.dt, _st()), "column means")
-            check(lib.mvf_bn_bwd_dzfree_wgrad(_p(self.dw), _p(self.wp), _p(gram), _p(amean[0]), _p(bn.gamma), _p(bn.mean), _p(bn.invstd), _p(sg), _p(sb),
+            check(self.eng.lib.mvf_bn_bwd_dzfree_wgrad(_p(self.dw), _p(self.wp), _p(gram), _p(amean[0]), _p(bn.gamma), _p(bn.mean), _p(bn.invstd), _p(sg), _p(sb),
                                               m, c, k, eng.dt, _st()), "weight gradient without dz: correction")
         if side is None:
             launch()
@@ -644,7 +648,7 @@ class _TMvf(object):
         y = self.eng.buf((id(self), "y"), (m, self.cs))
         if self.use_hs and eng.fuse_mvf_stats and eng.fuse_stats and not self.bn.frozen and self.cs % 4 == 0:
             # [r5] the stencil accumulates the BatchNorm's batch statistics over what it stores: no separate pass over y
-            rows = lib.mvf_nhwc_stencil_stats_rows(C.byref(d), c, self.cs)
+            rows = self.eng.lib.mvf_nhwc_stencil_stats_rows(C.byref(d), c, self.cs)
             part = self.eng.buf((id(self), "part"), (self.cs, rows, 2), torch.float32)
             self.launch_stencil_stats(d, x, c, y, part)
             self.bn.finalize(part, rows, m)
@@ -657,7 +661,7 @@ class _TMvf(object):
 
     def launch_stencil_stats(self, d, x, c, y, part):
         """Exactly one MVF stencil launch (bench.py brackets this call with HIP events)."""
-        check(lib.mvf_nhwc_stencil_stats(C.byref(d), _p(x), c, _p(y), self.cs, _p(self.wt), _p(self.wh), _p(self.ww), _p(part), _p(self.bn.mod.running_mean),
+        check(self.eng.lib.mvf_nhwc_stencil_stats(C.byref(d), _p(x), c, _p(y), self.cs, _p(self.wt), _p(self.wh), _p(self.ww), _p(part), _p(self.bn.mod.running_mean),
                                          _st()), "mvf stencil + statistics")
 
     def backward(self, dxp, x, y, nt, h, w, c, eng, addend=None, addend_bits=None, out_gate=None, gsum=None):
@@ -669,13 +673,13 @@ class _TMvf(object):
             dy = self.bn.backward(dxp, c, y, m, eng, 3)
         else:
             dy = dxp[:, : self.cs].contiguous()
-        nbytes = lib.mvf_nhwc_tapgrad_workspace_bytes(C.byref(d))
+        nbytes = self.eng.lib.mvf_nhwc_tapgrad_workspace_bytes(C.byref(d))
         dwh = self.dwh if self.dwh is not None else self.tmp_h
         dww = self.dww if self.dww is not None else self.tmp_w
         side = eng.side_stream() if (self.use_hs and not self.share) else None
         if side is None:
             ws = eng.workspace(nbytes)
-            check(lib.mvf_nhwc_tapgrad(C.byref(d), _p(x), c, _p(dy), self.cs, _p(self.dwt), _p(dwh), _p(dww), _p(ws), ws.numel(), _st()), "mvf tapgrad")
+            check(self.eng.lib.mvf_nhwc_tapgrad(C.byref(d), _p(x), c, _p(dy), self.cs, _p(self.dwt), _p(dwh), _p(dww), _p(ws), ws.numel(), _st()), "mvf tapgrad")
             if self.share:   # one weight tensor serves every view (MVF.py:114-116): gradients add up
                 self.dwt.view(self.cs, 3).add_(dwh.view(self.cs, 3) if self.mode & 2 else 0).add_(dww.view(self.cs, 3) if self.mode & 4 else 0)
         else:
@@ -684,7 +688,7 @@ class _TMvf(object):
             ws = eng.workspace(nbytes, side=True)
 
             def launch():
-                check(lib.mvf_nhwc_tapgrad(C.byref(d), _p(x), c, _p(dy), self.cs, _p(self.dwt), _p(dwh), _p(dww), _p(ws), ws.numel(), _st()), "mvf tapgrad")
+                check(self.eng.lib.mvf_nhwc_tapgrad(C.byref(d), _p(x), c, _p(dy), self.cs, _p(self.dwt), _p(dwh), _p(dww), _p(ws), ws.numel(), _st()), "mvf tapgrad")
             eng.on_side(launch)
         self.launch_stencil(d, dy, self.cs, dxp, c, 1, addend, c if addend is not None else 0, addend_bits, out_gate, gsum)
 
@@ -693,17 +697,17 @@ class _TMvf(object):
         [, the result gated by out_gate: the block below then receives the slice of gm = g * [out > 0]]); bench.py brackets this call with HIP events."""
         if out_gate is not None and gsum is not None:        # [r5] ... + the slice's column sums (the block below's dzfree_q_sums)
             bn = gsum["bn"]
-            rows = lib.mvf_nhwc_stencil_stats_rows(C.byref(d), src_c, dst_c)
+            rows = self.eng.lib.mvf_nhwc_stencil_stats_rows(C.byref(d), src_c, dst_c)
             part = self.eng.buf((id(bn), "gsum_mvf"), (self.cs, rows, 2), torch.float32)
-            check(lib.mvf_nhwc_stencil_gate_colsums(C.byref(d), _p(src), src_c, _p(dst), dst_c, _p(self.wt), _p(self.wh), _p(self.ww), flip, _p(addend), addend_c,
+            check(self.eng.lib.mvf_nhwc_stencil_gate_colsums(C.byref(d), _p(src), src_c, _p(dst), dst_c, _p(self.wt), _p(self.wh), _p(self.ww), flip, _p(addend), addend_c,
                                                     _p(addend_bits), _p(out_gate), _p(part), _st()), "mvf stencil (gated output + column sums)")
             bn._s1[0], bn._s1[1] = part, rows
             return
         if out_gate is not None:
-            check(lib.mvf_nhwc_stencil_gate(C.byref(d), _p(src), src_c, _p(dst), dst_c, _p(self.wt), _p(self.wh), _p(self.ww), None, None, flip,
+            check(self.eng.lib.mvf_nhwc_stencil_gate(C.byref(d), _p(src), src_c, _p(dst), dst_c, _p(self.wt), _p(self.wh), _p(self.ww), None, None, flip,
                                             _p(addend), addend_c, _p(addend_bits), _p(out_gate), _st()), "mvf stencil (gated output)")
             return
-        check(lib.mvf_nhwc_stencil(C.byref(d), _p(src), src_c, _p(dst), dst_c, _p(self.wt), _p(self.wh), _p(self.ww), None, None, flip,
+        check(self.eng.lib.mvf_nhwc_stencil(C.byref(d), _p(src), src_c, _p(dst), dst_c, _p(self.wt), _p(self.wh), _p(self.ww), None, None, flip,
                                    _p(addend), addend_c, _p(addend_bits), _st()), "mvf stencil")
 
 
@@ -748,7 +752,7 @@ class _TBlock(object):
             return False
         if self.q_z3_free(eng, m2):
             return True            # [r5] its backward reads no z3 at all (dzfree_q): the first conv3 pass only takes the statistics
-        if (eng.fuse_bnwg & 8) and eng.tdtype == torch.bfloat16 and lib.mvf_bn_bwd_wgrad_splits(m2, self.c3.cout, self.c3.cin, 1, 4) > 0:
+        if (eng.fuse_bnwg & 8) and eng.tdtype == torch.bfloat16 and eng.lib.mvf_bn_bwd_wgrad_splits(m2, self.c3.cout, self.c3.cin, 1, 4) > 0:
             return False           # A/B: stored z3 + conv3's weight gradient in bn3's backward apply instead
         # measured per block in the bf16 step (us; stored-z3 path -> recompute path): statistics-only pass 148 -> 79 (layer1) / 75 -> 52 (layer2),
         # backward sums 168 -> 205 / 102 -> 119 (the conv kernel's sum epilogue streams g at 2.7 TB/s, the BatchNorm kernel at 5.2), backward apply
@@ -767,7 +771,7 @@ class _TBlock(object):
             return False
         # [r5] asked with the block's REAL pixel count: the backward of this form has no fallback, so the forward must not choose it where the one-pass
         # kernel (stride 1: the downsample branch sees the same m2 pixels) refuses the shape
-        return lib.mvf_conv1x1_bwd_fused_splits(m2, self.c3.cout, self.c3.cin) > 0
+        return eng.lib.mvf_conv1x1_bwd_fused_splits(m2, self.c3.cout, self.c3.cin) > 0
 
     above = None       # the block whose backward produces this block's output gradient (set by the engine / BlockTrainer over a chain)
 
@@ -821,13 +825,13 @@ class _TBlock(object):
     def launch_sums_pair(self, a2, x, x_pitch, g, bits, m, eng):
         """Exactly one launch (bench.py brackets this call with HIP events) + the two finalizes."""
         c3, cd = self.c3, self.cd
-        ns = lib.mvf_conv1x1_bwd_fused_splits(m, c3.cout, c3.cin)
+        ns = eng.lib.mvf_conv1x1_bwd_fused_splits(m, c3.cout, c3.cin)
         pa = eng.buf((id(c3), "bwpart_pair"), (c3.cout, 2 * ns, 2), torch.float32)
         pb = eng.buf((id(cd), "bwpart_pair"), (c3.cout, 2 * ns, 2), torch.float32)
-        check(lib.mvf_conv1x1_bnbwd_sums_pair(_p(a2), c3.cin, _p(c3.wp), _p(x), x_pitch, _p(cd.wp), _p(g), c3.cout, _p(bits), m, c3.cout, c3.cin, _p(self.b3.mean),
+        check(eng.lib.mvf_conv1x1_bnbwd_sums_pair(_p(a2), c3.cin, _p(c3.wp), _p(x), x_pitch, _p(cd.wp), _p(g), c3.cout, _p(bits), m, c3.cout, c3.cin, _p(self.b3.mean),
                                               _p(self.b3.invstd), _p(self.bd.mean), _p(self.bd.invstd), _p(pa), _p(pb), 2 * ns, eng.dt, _st()), "bn backward sums (pair)")
-        check(lib.mvf_bn_bwd_finalize(_p(pa), 2 * ns, c3.cout, _p(self.b3.dgamma), _p(self.b3.dbeta), _st()), "mvf_bn_bwd_finalize")
-        check(lib.mvf_bn_bwd_finalize(_p(pb), 2 * ns, c3.cout, _p(self.bd.dgamma), _p(self.bd.dbeta), _st()), "mvf_bn_bwd_finalize")
+        check(eng.lib.mvf_bn_bwd_finalize(_p(pa), 2 * ns, c3.cout, _p(self.b3.dgamma), _p(self.b3.dbeta), _st()), "mvf_bn_bwd_finalize")
+        check(eng.lib.mvf_bn_bwd_finalize(_p(pb), 2 * ns, c3.cout, _p(self.bd.dgamma), _p(self.bd.dbeta), _st()), "mvf_bn_bwd_finalize")
 
     def forward(self, x, nt, h, w, c, eng):
         m = nt * h * w
@@ -1025,6 +1029,7 @@ class _StatTable(object):
     offset, length and shape of every segment.  acc (fp64) and shadow (fp32) are the two flat work arrays of TrainEngine.precise_bn."""
 
     def __init__(self, eng, bns):
+        self.eng = eng
         names = {id(m_): n_ for n_, m_ in eng.model.named_modules()}
         segs, self.keys, self.slices, first = [], [], [], 0
         for bn in bns:
@@ -1041,18 +1046,23 @@ class _StatTable(object):
         self.shadow = torch.empty(first, dtype=torch.float32, device=eng.device)
 
     def accumulate(self):
-        check(lib.mvf_bn_stats_accumulate(_p(self.dev), self.nseg, self.n, _p(self.acc), _st()), "bn stats accumulate")
+        check(self.eng.lib.mvf_bn_stats_accumulate(_p(self.dev), self.nseg, self.n, _p(self.acc), _st()), "bn stats accumulate")
 
     def finalize(self, count, dst=None):
-        check(lib.mvf_bn_stats_finalize(_p(self.dev), self.nseg, self.n, _p(self.acc), count, _p(dst), _st()), "bn stats finalize")
+        check(self.eng.lib.mvf_bn_stats_finalize(_p(self.dev), self.nseg, self.n, _p(self.acc), count, _p(dst), _st()), "bn stats finalize")
 
     def exchange(self, flat, mode):
         """mode 0: flat <- the modules' buffers, 1: the modules' buffers <- flat, 2: swap."""
-        check(lib.mvf_bn_stats_exchange(_p(self.dev), self.nseg, self.n, _p(flat), mode, _st()), "bn stats exchange")
+        check(self.eng.lib.mvf_bn_stats_exchange(_p(self.dev), self.nseg, self.n, _p(flat), mode, _st()), "bn stats exchange")
 
 
 class _ParamStore(object):
     """Flat fp32 parameter / gradient / momentum buffers for a module; its nn.Parameters become views."""
+
+    # The library handle: every entry point launched on behalf of an engine (by the engine itself, its _BN / _TConv / _TMvf / _TBlock / _StatTable objects and
+    # the closures it hands to on_side) is looked up on the engine's `lib` at call time.  The class attribute is the loaded library; launch_plan.recording(eng)
+    # shadows it with a RecordingLib on that ONE instance while a step is recorded.
+    lib = _lib.lib
 
     def _init_store(self, model, dtype=torch.float32, rehome=True):
         """rehome=True: the parameters become views of this store's flat buffer (the optimizer kernel and the gradient exchange work on
@@ -1296,7 +1306,7 @@ class _ParamStore(object):
             self._ones[c] = (torch.ones(c, device=a.device), torch.zeros(c, device=a.device))
         one, zero = self._ones[c]
         out = self.buf((key or id(a), "add"), a.shape, a.dtype) if key is not None else torch.empty_like(a)
-        check(lib.mvf_bn_apply(_p(a), m, c, _p(one), _p(zero), _p(b), None, None, 0, _p(out), self.dt, _st()), "add")
+        check(self.lib.mvf_bn_apply(_p(a), m, c, _p(one), _p(zero), _p(b), None, None, 0, _p(out), self.dt, _st()), "add")
         return out
 
     lr, momentum, weight_decay, max_norm = 0.015, 0.9, 1e-4, 40.0
@@ -1379,7 +1389,7 @@ class _ParamStore(object):
 
     def _flat_stats(self, x, y, out, guard=None, step_out=None):
         ls = self._lstats
-        check(lib.mvf_flat_segment_stats(_p(x), _p(y), x.numel(), _p(ls["first"]), ls["nseg"], _p(out), _p(guard), _p(step_out), _p(ls["ws"]), ls["ws"].numel(),
+        check(self.lib.mvf_flat_segment_stats(_p(x), _p(y), x.numel(), _p(ls["first"]), ls["nseg"], _p(out), _p(guard), _p(step_out), _p(ls["ws"]), ls["ws"].numel(),
                                          _st()), "flat segment stats")
 
     def _layer_stats_before(self, grads):
@@ -1416,7 +1426,7 @@ class _ParamStore(object):
         ent = ls["bn"].get(id(tab))
         if ent is None:
             ent = ls["bn"][id(tab)] = (tab, torch.zeros(tab.nseg, dtype=torch.int64, device=self.device))
-        check(lib.mvf_bn_stats_nonfinite(_p(tab.dev), tab.nseg, tab.n, _p(ent[1]), _p(self._guard["buf"]), _st()), "bn stats nonfinite")
+        check(self.lib.mvf_bn_stats_nonfinite(_p(tab.dev), tab.nseg, tab.n, _p(ent[1]), _p(self._guard["buf"]), _st()), "bn stats nonfinite")
 
     def _optimizer_operands(self):
         """What every _apply_* opens with: (off, n, ema, ema_m, guard) -- the trainable range [off, off + n) of the flat buffers, the averaged copy's pointer
@@ -1453,7 +1463,7 @@ class _ParamStore(object):
         if ops is None:
             return None
         off, n, ema, ema_m, guard = ops
-        ws = self.workspace(lib.mvf_sgd_workspace_bytes(n))
+        ws = self.workspace(self.lib.mvf_sgd_workspace_bytes(n))
         args = (_p(self.flat_params[off:]), _p(grads[off:]), _p(self.flat_mom[off:]), n, C.c_float(grad_scale),
                 C.c_float(self.max_norm or 0.0), C.c_float(self.lr if lr is None else lr), C.c_float(self.momentum),
                 C.c_float(self.weight_decay), int(self.steps == 0))
@@ -1464,11 +1474,11 @@ class _ParamStore(object):
             tab, nseg = self._segments(off)
             seg = (int(self.nesterov), _p(tab), nseg)
         if guard is not None:
-            check(lib.mvf_sgd_step_guarded(*(args + (seg or (0, None, 0)) + (ema, C.c_float(ema_m), guard) + tail)), "sgd step (guarded)")
+            check(self.lib.mvf_sgd_step_guarded(*(args + (seg or (0, None, 0)) + (ema, C.c_float(ema_m), guard) + tail)), "sgd step (guarded)")
         elif ema is None:
-            check((lib.mvf_sgd_nesterov_step if flat else lib.mvf_sgd_step_segments)(*(args + seg + tail)), "sgd step")
+            check((self.lib.mvf_sgd_nesterov_step if flat else self.lib.mvf_sgd_step_segments)(*(args + seg + tail)), "sgd step")
         else:
-            check((lib.mvf_sgd_nesterov_step_ema if flat else lib.mvf_sgd_step_segments_ema)(*(args + seg + (ema, C.c_float(ema_m)) + tail)), "sgd step (ema)")
+            check((self.lib.mvf_sgd_nesterov_step_ema if flat else self.lib.mvf_sgd_step_segments_ema)(*(args + seg + (ema, C.c_float(ema_m)) + tail)), "sgd step (ema)")
         return self._optimizer_done()
 
     _guard = None      # non-finite step guard (TrainEngine.enable_step_guard): None = off, the launches above are all there is
@@ -1481,7 +1491,7 @@ class _ParamStore(object):
             self._layer_stats_on_skip(snap[0] if snap is not None else None)      # the NaN statistics are evidence: scanned before they are put back
         if snap is not None:
             tab, flat_stats = snap
-            check(lib.mvf_bn_stats_restore(_p(tab.dev), tab.nseg, tab.n, _p(flat_stats), _p(self._nbt_flat), self._nbt_flat.numel(), _p(g["nbt"]), _p(g["buf"]),
+            check(self.lib.mvf_bn_stats_restore(_p(tab.dev), tab.nseg, tab.n, _p(flat_stats), _p(self._nbt_flat), self._nbt_flat.numel(), _p(g["nbt"]), _p(g["buf"]),
                                            _st()), "bn stats restore")
 
     # ---- Adam / AdamW: the fused step of mvf_adamw_step in place of the SGD sequence -----------------------------------------------------------------------
@@ -1565,14 +1575,14 @@ class _ParamStore(object):
             return None
         off, n, ema, ema_m, guard = ops
         a = self._adam
-        ws = self.workspace(lib.mvf_adamw_workspace_bytes(n))
+        ws = self.workspace(self.lib.mvf_adamw_workspace_bytes(n))
         h = a["hyper"]
         h.lr, h.weight_decay = float(self.lr if lr is None else lr), float(self.weight_decay or 0.0)
         h.beta1, h.beta2, h.eps, h.decoupled = a["betas"][0], a["betas"][1], a["eps"], a["decoupled"]
         tab, nseg = (None, 0)
         if self.param_options or self._scattered_frozen:
             tab, nseg = self._segments(off)
-        check(lib.mvf_adamw_step(_p(self.flat_params[off:]), _p(grads[off:]), _p(self.flat_mom[off:]), _p(self.flat_var[off:]), n, C.c_float(grad_scale),
+        check(self.lib.mvf_adamw_step(_p(self.flat_params[off:]), _p(grads[off:]), _p(self.flat_mom[off:]), _p(self.flat_var[off:]), n, C.c_float(grad_scale),
                                  C.c_float(self.max_norm or 0.0), C.byref(h), _p(tab), nseg, ema, C.c_float(ema_m), guard,
                                  _p(a["count"]), _p(self.norm_out), _p(ws), ws.numel(), _st()), "adamw step")
         return self._optimizer_done()
@@ -1602,11 +1612,11 @@ class _ParamStore(object):
         a = self._adam
         lamb = a["lamb"]
         tab, nseg, names, ratios = self._lamb_segments(off)
-        ws = self.workspace(lib.mvf_lamb_workspace_bytes(n, nseg))
+        ws = self.workspace(self.lib.mvf_lamb_workspace_bytes(n, nseg))
         h = lamb["hyper"]
         h.lr, h.weight_decay = float(self.lr if lr is None else lr), float(self.weight_decay or 0.0)
         h.beta1, h.beta2, h.eps, h.trust_clip, h.always_adapt = a["betas"][0], a["betas"][1], a["eps"], lamb["trust_clip"], lamb["always_adapt"]
-        check(lib.mvf_lamb_step(_p(self.flat_params[off:]), _p(grads[off:]), _p(self.flat_mom[off:]), _p(self.flat_var[off:]), n, C.c_float(grad_scale),
+        check(self.lib.mvf_lamb_step(_p(self.flat_params[off:]), _p(grads[off:]), _p(self.flat_mom[off:]), _p(self.flat_var[off:]), n, C.c_float(grad_scale),
                                 C.c_float(self.max_norm or 0.0), C.byref(h), _p(tab), nseg, ema, C.c_float(ema_m), guard, _p(a["count"]), _p(self.norm_out),
                                 _p(ratios), _p(ws), ws.numel(), _st()), "lamb step")
         lamb["last"] = (names, ratios)
@@ -1666,7 +1676,7 @@ class _ParamStore(object):
         self._ema_live("update_ema")
         off = self.trainable_offset()
         m = _ema_momentum_at(self.ema_momentum, self.ema_warmup_steps, self.ema_updates)
-        check(lib.mvf_ema_update(_p(self.flat_ema[off:]), _p(self.flat_params[off:]), self.flat_params.numel() - off, C.c_float(m), _st()), "ema update")
+        check(self.lib.mvf_ema_update(_p(self.flat_ema[off:]), _p(self.flat_params[off:]), self.flat_params.numel() - off, C.c_float(m), _st()), "ema update")
         self.ema_updates += 1
 
     def ema_of(self, p):
@@ -1913,6 +1923,7 @@ class TrainEngine(_ParamStore):
         self.blocks = [_TBlock(blk, self) for name in bb.res_layers for blk in getattr(bb, name)]
         for lo, hi in zip(self.blocks[:-1], self.blocks[1:]):
             lo.above = hi
+        self._shared_taps = any(blk.mvf is not None and blk.mvf.share for blk in self.blocks)      # (read by _plan_key)
         head = model.cls_head
         self.fc_w, self.fc_b = head.new_fc.weight, head.new_fc.bias
         self.dfc_w, self.dfc_b = self.grad_of(head.new_fc.weight), self.grad_of(head.new_fc.bias)
@@ -2009,7 +2020,7 @@ class TrainEngine(_ParamStore):
                 self._pack_tables[k] = (host.to(self.device), len(jobs), first)
         t = self._pack_tables[kind]
         if t is not None:
-            check(lib.mvf_pack_conv_weights_batched(_p(t[0]), t[1], t[2], self.dt, _st()), "pack_conv_weights_batched")
+            check(self.lib.mvf_pack_conv_weights_batched(_p(t[0]), t[1], t[2], self.dt, _st()), "pack_conv_weights_batched")
 
     # ---- one step -----------------------------------------------------------------------------------------------
     def forward(self, imgs, labels, stages=None, _prepared=None):
@@ -2171,10 +2182,10 @@ class TrainEngine(_ParamStore):
         hbuf = self.buf("trn_h", (rows, b, trn["hidden"]), f32)
         hpart = self.buf("trn_hpart", (_lib.TRN_KSPLIT_MAX, rows, b, trn["hidden"]), f32)
         arr = self._trn_operands()
-        check(lib.mvf_trn_head_fwd(_p(feat), b, t, hw, c, _p(self.fc_w), _p(self.fc_b), trn["fdim"], arr, len(arr), trn["hidden"], self.num_classes, _p(table_d), rows,
+        check(self.lib.mvf_trn_head_fwd(_p(feat), b, t, hw, c, _p(self.fc_w), _p(self.fc_b), trn["fdim"], arr, len(arr), trn["hidden"], self.num_classes, _p(table_d), rows,
                                    _p(mask), _p(pooled), _p(fbuf), _p(hbuf), _p(hpart), _p(scores), self.dt, _st()), "trn head fwd")
         kind, tgt = self._loss_operands(lab, b)
-        loss_calls.stand_alone_loss(lib, kind, scores, tgt, b, self.num_classes, dscores, loss_part, loss, _st())
+        loss_calls.stand_alone_loss(self.lib, kind, scores, tgt, b, self.num_classes, dscores, loss_part, loss, _st())
         self.saved.update(trn_f=fbuf, trn_h=hbuf, trn_table=(table_d, rows))
 
     def _trn_head_backward(self, s, g):
@@ -2186,7 +2197,7 @@ class TrainEngine(_ParamStore):
         df = self.buf("trn_df", (b * t, trn["fdim"]), f32)
         dpool = self.buf("trn_dpool", (b * t, s["c"]), f32)
         arr = self._trn_operands()
-        check(lib.mvf_trn_head_bwd(_p(s["dscores"]), _p(s["pooled"]), _p(s["trn_f"]), _p(s["trn_h"]), _p(self.fc_w), arr, len(arr), trn["hidden"], self.num_classes,
+        check(self.lib.mvf_trn_head_bwd(_p(s["dscores"]), _p(s["pooled"]), _p(s["trn_f"]), _p(s["trn_h"]), _p(self.fc_w), arr, len(arr), trn["hidden"], self.num_classes,
                                    _p(table_d), rows, _p(s["mask"]), b, t, s["hw"], s["c"], trn["fdim"], _p(self.dfc_w), _p(self.dfc_b), _p(dh), _p(df), _p(dpool),
                                    _p(g), self.dt, _st()), "trn head bwd")
 
@@ -2231,7 +2242,7 @@ class TrainEngine(_ParamStore):
         n, hs, ws = (int(v) for v in f.shape[:3])
         out, tmp = self.buf("randaug_out", tuple(f.shape), torch.uint8), self.buf("randaug_tmp", tuple(f.shape), torch.uint8)
         wsb = self.buf("randaug_ws", (n * WS_PER_FRAME,), torch.uint8)
-        check(lib.mvf_frames_randaug_u8(_p(f), n, hs, ws, int(imgs.shape[1]), order, _p(sizes_d), _p(table_d), layers, mask, _p(out), _p(tmp), _p(wsb),
+        check(self.lib.mvf_frames_randaug_u8(_p(f), n, hs, ws, int(imgs.shape[1]), order, _p(sizes_d), _p(table_d), layers, mask, _p(out), _p(tmp), _p(wsb),
                                         wsb.numel(), _st()), "frames_randaug")
         return out.view(imgs.shape)
 
@@ -2251,7 +2262,7 @@ class TrainEngine(_ParamStore):
         soft = self._uses_soft_head(lab)
         if soft and not lab.is_floating_point():
             rows_d, wts_d = self._blend_table if self.blending is not None else (None, None)
-            lab = loss_calls.targets_for(lib, lab, rows_d, wts_d, b, self.num_classes, self.label_smooth_eps,
+            lab = loss_calls.targets_for(self.lib, lab, rows_d, wts_d, b, self.num_classes, self.label_smooth_eps,
                                          self.buf("soft_targets", (b, self.num_classes), torch.float32), _st())
         return loss_calls.loss_kind(self.bce, self.focal, soft), lab
 
@@ -2293,16 +2304,16 @@ class TrainEngine(_ParamStore):
                 imgs = self._randaug_frames(imgs)          # RandAugment, then erasing, then blending
             self.input_pipeline.to_stem(imgs, self.input_window, 3, wp, self.tdtype, out=xp)
         else:
-            check(lib.mvf_stem_prep(_p(x), nt, 3, h, w, 3, wp, _p(xp), self.dt, _st()), "stem_prep")
+            check(self.lib.mvf_stem_prep(_p(x), nt, 3, h, w, 3, wp, _p(xp), self.dt, _st()), "stem_prep")
         if self.erasing is not None:
             # in place, per sample, BEFORE the batch blend (as in timm and mmaction2): saved['xp'] is the erased, then blended, operand
             boxes_d, fill_d, key_d, max_boxes = self._erase_table
-            check(lib.mvf_stem_erase(_p(xp), nt, hp, wp, 3, _p(boxes_d), max_boxes, _p(fill_d), _p(key_d), self.dt, _st()), "stem_erase")
+            check(self.lib.mvf_stem_erase(_p(xp), nt, hp, wp, 3, _p(boxes_d), max_boxes, _p(fill_d), _p(key_d), self.dt, _st()), "stem_erase")
         if self.blending is not None:
             # out of place (clip i reads its partner clip); xp_blend is what the stem reads AND what backward's stem weight gradient sees (saved['xp'])
             rows_d, wts_d = self._blend_table
             xb = self.buf("xp_blend", (nt, hp, wp, 4))
-            check(lib.mvf_stem_blend(_p(xp), b, t, hp, wp, 3, _p(rows_d), _p(wts_d), _p(xb), self.dt, _st()), "stem_blend")
+            check(self.lib.mvf_stem_blend(_p(xp), b, t, hp, wp, 3, _p(rows_d), _p(wts_d), _p(xb), self.dt, _st()), "stem_blend")
             xp = xb
         teacher_scores = None
         if self.distill is not None:
@@ -2315,7 +2326,7 @@ class TrainEngine(_ParamStore):
         h2, w2 = (ho - 1) // 2 + 1, (wo - 1) // 2 + 1
         p0 = self.buf("p0", (nt * h2 * w2, 64))
         amax = self.buf("amax", (nt * h2 * w2, 64), torch.uint8)
-        check(lib.mvf_maxpool_bn_relu_fwd(_p(z0), nt, ho, wo, 64, _p(self.stem_bn.scale), _p(self.stem_bn.shift), _p(p0), _p(amax), self.dt, _st()), "maxpool fwd")
+        check(self.lib.mvf_maxpool_bn_relu_fwd(_p(z0), nt, ho, wo, 64, _p(self.stem_bn.scale), _p(self.stem_bn.shift), _p(p0), _p(amax), self.dt, _st()), "maxpool fwd")
         self.saved = dict(xp=xp, z0=z0, amax=amax, nt=nt, hp=hp, wp=wp, ho=ho, wo=wo, t=t, b=b)
         if stages is not None:
             stages["maxpool"] = p0.view(nt, h2, w2, 64)
@@ -2339,12 +2350,12 @@ class TrainEngine(_ParamStore):
             self._trn_head_forward(xcur, b, t, hc * wc, cc, lab, mask, pooled, scores, dscores, loss_part, loss)
         else:
             kind, tgt = self._loss_operands(lab, b)
-            loss_calls.fused_head_loss(lib, kind, xcur, b, t, hc * wc, cc, self.fc_w, self.fc_b, self.num_classes, tgt, mask, pooled, scores, dscores, loss_part,
+            loss_calls.fused_head_loss(self.lib, kind, xcur, b, t, hc * wc, cc, self.fc_w, self.fc_b, self.num_classes, tgt, mask, pooled, scores, dscores, loss_part,
                                        loss, self.dt, _st())
         if teacher_scores is not None:
             # the head left the cross-entropy's dscores / loss_part / loss: they become the combined loss's in place, whatever kind of labels made them
             terms = self._distill_terms = self.buf("distill_terms", (2,), f32)
-            check(lib.mvf_distill_loss(_p(scores), _p(teacher_scores), b, self.num_classes, C.c_float(self.distill.temperature), C.c_float(self.distill.alpha),
+            check(self.lib.mvf_distill_loss(_p(scores), _p(teacher_scores), b, self.num_classes, C.c_float(self.distill.temperature), C.c_float(self.distill.alpha),
                                        _p(dscores), _p(loss_part), _p(loss), _p(terms), _st()), "distill loss")
             self.saved.update(teacher_scores=teacher_scores)
         self.saved.update(pooled=pooled, dscores=dscores, mask=mask, hw=hc * wc, c=cc, feat_shape=xcur.shape, scores=scores)
@@ -2389,7 +2400,7 @@ class TrainEngine(_ParamStore):
         if self.trn is not None:
             self._trn_head_backward(s, g)
         else:
-            check(lib.mvf_head_train_bwd(_p(s["dscores"]), _p(s["pooled"]), _p(self.fc_w), _p(s["mask"]), b, t, s["hw"], s["c"], self.num_classes,
+            check(self.lib.mvf_head_train_bwd(_p(s["dscores"]), _p(s["pooled"]), _p(self.fc_w), _p(s["mask"]), b, t, s["hw"], s["c"], self.num_classes,
                                          _p(self.dfc_w), _p(self.dfc_b), _p(dpool), _p(g), self.dt, _st()), "head bwd")
         gated = sums = False
         for i in range(len(self.blocks) - 1, -1, -1):
@@ -2402,14 +2413,14 @@ class TrainEngine(_ParamStore):
         # the stem's max-pool + ReLU + BatchNorm backward: a sums pass that gathers the pooled gradient through the argmax bytes (no scattered gradient tensor) and
         # produces the BatchNorm's backward sums, then an apply pass that gathers again and writes dz0 ([r3]: against scatter + reduce + apply: 515 -> 301 us)
         bn = self.stem_bn
-        rows = lib.mvf_maxpool_bwd_sums_rows(nt, ho)
+        rows = self.lib.mvf_maxpool_bwd_sums_rows(nt, ho)
         part = self.buf("stem_bnsums", (64, rows, 2), torch.float32)
-        check(lib.mvf_maxpool_bn_relu_bwd_sums(_p(s["amax"]), _p(g), nt, ho, wo, 64, None, _p(s["z0"]), _p(bn.mean), _p(bn.invstd),
+        check(self.lib.mvf_maxpool_bn_relu_bwd_sums(_p(s["amax"]), _p(g), nt, ho, wo, 64, None, _p(s["z0"]), _p(bn.mean), _p(bn.invstd),
                                                _p(bn.scale), _p(bn.shift), _p(part), self.dt, _st()), "maxpool bwd + bn sums")
-        check(lib.mvf_bn_bwd_finalize(_p(part), rows, 64, _p(bn.dgamma), _p(bn.dbeta), _st()), "bn bwd finalize")
+        check(self.lib.mvf_bn_bwd_finalize(_p(part), rows, 64, _p(bn.dgamma), _p(bn.dbeta), _st()), "bn bwd finalize")
         dz0 = self.buf((id(bn), "dz"), s["z0"].shape, s["z0"].dtype)
         sg, sb = (bn._zero, bn._zero) if bn.frozen else (bn.dgamma, bn.dbeta)
-        check(lib.mvf_maxpool_bn_relu_bwd_apply(_p(s["amax"]), _p(g), nt, ho, wo, 64, _p(s["z0"]), _p(bn.gamma), _p(bn.mean), _p(bn.invstd), _p(bn.scale),
+        check(self.lib.mvf_maxpool_bn_relu_bwd_apply(_p(s["amax"]), _p(g), nt, ho, wo, 64, _p(s["z0"]), _p(bn.gamma), _p(bn.mean), _p(bn.invstd), _p(bn.scale),
                                                 _p(bn.shift), _p(sg), _p(sb), _p(dz0), self.dt, _st()), "maxpool bwd + bn apply")
         # the step's last weight gradient runs on the LAUNCH stream: nothing is left there to overlap it with, and the side stream
         # still has layer1's weight gradients queued -- the two tails now run side by side
@@ -2499,6 +2510,7 @@ class TrainEngine(_ParamStore):
     plan_warmup = 2          # eager steps before the first recording (buffers and workspaces reach their final sizes in the first two)
     focal = None             # (the class default of the instance attribute __init__ sets: None is no plan-key switch, see _switch_names)
     trn = relations = None   # (likewise: the relation head's settings and the explicit relation table)
+    _shared_taps = False     # (likewise: __init__ sets it when an MVF block of the model has share=True)
 
     def _plan_key(self, imgs, labels):
         """None = this step cannot run from a plan; else what a plan is valid for."""
@@ -2512,6 +2524,8 @@ class TrainEngine(_ParamStore):
             return None                  # the teacher's calls go through engine.py, which a plan does not record; back at None the recorded plans are replayed
         if self.trn is not None:
             return None                  # the relation head's per-scale operands are a host array built per call; the average head's key is what it was
+        if self._shared_taps:
+            return None                  # an MVF block with share=True: the three views' tap gradients are summed by torch add_ calls (_TMvf.backward), which a plan does not record
         sw = self.__dict__.get("_switch_names")
         if sw is None:
             sw = self._switch_names = sorted(k for c_ in type(self).__mro__ for k, v in vars(c_).items()
@@ -2532,17 +2546,10 @@ class TrainEngine(_ParamStore):
     def _record_step(self, imgs, labels, prepared):
         """One eager step with every library call and stream ordering recorded; returns (loss, Plan | None)."""
         from . import launch_plan
-        import sys
-        mod = sys.modules[__name__]
-        rec = launch_plan.Recorder()
         allocs0 = torch.cuda.memory_stats(imgs.device).get("allocation.all.allocated", 0)
-        real_lib, self._rec = mod.lib, rec
-        mod.lib = launch_plan.RecordingLib(rec)
-        try:
+        with launch_plan.recording(self) as rec:
             loss = self.forward(imgs, labels, _prepared=prepared)
             self.backward(exchange=True)
-        finally:
-            mod.lib, self._rec = real_lib, None
         # a tensor allocated INSIDE the step would be freed after it, and a replay would launch on memory the allocator has handed to somebody else
         if torch.cuda.memory_stats(imgs.device).get("allocation.all.allocated", 0) != allocs0:
             rec.unsupported = "the step allocates device memory"
@@ -2671,7 +2678,7 @@ class TrainEngine(_ParamStore):
         if not ent:
             return
         tab, flat = ent
-        check(lib.mvf_bn_stats_snapshot(_p(tab.dev), tab.nseg, tab.n, _p(flat), _p(self._nbt_flat), self._nbt_flat.numel(), _p(g["nbt"]),
+        check(self.lib.mvf_bn_stats_snapshot(_p(tab.dev), tab.nseg, tab.n, _p(flat), _p(self._nbt_flat), self._nbt_flat.numel(), _p(g["nbt"]),
                                         C.c_void_p(torch.cuda.current_stream().cuda_stream)), "bn stats snapshot")
         g["snap"] = ent
 
@@ -2719,7 +2726,7 @@ class TrainEngine(_ParamStore):
                 raise RuntimeError("enable_layer_stats: the flat parameter layout is not ascending from 0")
             ls = dict(names=names, nseg=len(names), first=torch.tensor(first, dtype=torch.int64).to(self.device), armed=False, out=None, copy=None, pending=None,
                       grads=None, scale=1.0, on_skip=False,
-                      ws=torch.empty(lib.mvf_flat_stats_workspace_bytes(n, len(names)), dtype=torch.uint8, device=self.device))
+                      ws=torch.empty(self.lib.mvf_flat_stats_workspace_bytes(n, len(names)), dtype=torch.uint8, device=self.device))
             self._lstats = ls
         if on_skip and (not ls["on_skip"] or ls.get("guard_buf") is not self._guard["buf"]):
             ls.update(skip_out=torch.zeros(ls["nseg"], 4, dtype=torch.int64, device=self.device), skip_step=torch.zeros(1, dtype=torch.int64, device=self.device),
@@ -2852,7 +2859,7 @@ class TrainEngine(_ParamStore):
         first = self.accumulated_count == 0
         # backward ended with join_side(): the launch stream is ordered behind the side stream's weight gradients
         with _on_stream(torch.cuda.current_stream(), main=True):
-            check(lib.mvf_grad_accumulate(_p(self.flat_acc), _p(self.flat_grads), self.flat_grads.numel(), int(first), _st()), "grad accumulate")
+            check(self.lib.mvf_grad_accumulate(_p(self.flat_acc), _p(self.flat_grads), self.flat_grads.numel(), int(first), _st()), "grad accumulate")
         if first:
             torch.mul(loss, 1.0, out=self._acc_loss_sum)      # (an elementwise launch on this stream: copy_ would be a blit on another queue)
         else:
@@ -2897,7 +2904,7 @@ class TrainEngine(_ParamStore):
         """Exchange the live and the averaged model in place: the parameters, and (stats=True) the calibrated running statistics where flat_ema_stats exists."""
         if stats and self.flat_ema_stats is not None:
             self._ema_stats_table.exchange(self.flat_ema_stats, 2)
-        check(lib.mvf_ema_swap(_p(self.flat_params), _p(self.flat_ema), self.flat_params.numel(), _st()), "ema swap")
+        check(self.lib.mvf_ema_swap(_p(self.flat_params), _p(self.flat_ema), self.flat_params.numel(), _st()), "ema swap")
         self._invalidate_inference()
 
     def _invalidate_inference(self):

@@ -53,6 +53,38 @@ class policy_set(object):
             os.environ["MVF_POLICY"] = self.old
 
 
+class NamesOf(object):
+    """Stands in for a library object (as launch_plan.RecordingLib does) and notes every entry point that is looked up."""
+
+    def __init__(self, real, names):
+        self.__dict__.update(_real=real, _names=names)
+
+    def __getattr__(self, name):
+        self._names.append(name)
+        return getattr(self._real, name)
+
+
+class library_names(object):
+    """with library_names(eng) as names: ... -- the engine's library handle (eng.lib, which every launch made on its behalf is looked up on at call time) is
+    a NamesOf for the block, `names` the list of the entry points looked up; `lib=` installs another stand-in (a launch_plan.RecordingLib) the same way.
+    On exit the engine's handle is what it was (an instance attribute that was there before comes back, else the class's library shows through again)."""
+
+    def __init__(self, eng, lib=None):
+        self.eng, self.names = eng, []
+        self.lib = lib if lib is not None else NamesOf(eng.lib, self.names)
+
+    def __enter__(self):
+        self.old = vars(self.eng).get("lib")
+        self.eng.lib = self.lib
+        return self.names
+
+    def __exit__(self, *a):
+        if self.old is None:
+            vars(self.eng).pop("lib", None)
+        else:
+            self.eng.lib = self.old
+
+
 def rel_err(a, ref):
     """max|a-ref| / max|ref| -- tolerances are relative to each tensor's scale."""
     a = np.asarray(a, dtype=np.float64)

@@ -13,6 +13,38 @@ def test_library_loads_and_exports_declared_symbols():
     assert _lib.lib.mvf_abi_version() == 2        # [r5] 2: mvf_conv_desc_t.x_c0
 
 
+def test_queries_names_every_entry_point_that_launches_nothing():
+    """_lib.QUERIES is what a launch plan never holds (launch_plan.RecordingLib): mvf_plan_run reads every callee's return value as a status, so every declared
+    function that returns anything else must be in it; it is no weaker than the name rule it replaces (four suffixes, two names), it holds the host-side launch
+    records that rule missed, and it names nothing the header does not declare."""
+    from mvfnet_amd import _lib
+    names = _lib.declared_symbols()
+    no_status = [n for n in names if getattr(_lib.lib, n).restype is not ctypes.c_int]
+    assert no_status and not [n for n in no_status if n not in _lib.QUERIES], [n for n in no_status if n not in _lib.QUERIES]
+    old_rule = [n for n in names if n.endswith(("_bytes", "_rows", "_splits", "_plan")) or n in ("mvf_last_error", "mvf_abi_version")]
+    assert len(old_rule) >= 18 and not [n for n in old_rule if n not in _lib.QUERIES], [n for n in old_rule if n not in _lib.QUERIES]
+    assert "mvf_conv2d_last_launch" in _lib.QUERIES and "mvf_bn_last_launch" in _lib.QUERIES
+    assert isinstance(_lib.QUERIES, frozenset) and not sorted(_lib.QUERIES - set(names)), sorted(_lib.QUERIES - set(names))
+
+
+def test_recording_lib_passes_queries_through_and_refuses_what_returns_no_status():
+    """launch_plan.RecordingLib without a GPU: a query is handed out as the library's own function and leaves the recorder alone; an entry point outside
+    _lib.QUERIES is wrapped, and one that does not return a status marks the step as unsupported (no plan is built from it)."""
+    from mvfnet_amd import _lib, launch_plan
+
+    class FakeLib(object):
+        mvf_bn_workspace_bytes = _lib.lib.mvf_bn_workspace_bytes
+        mvf_bn_bwd_finalize = _lib.lib.mvf_bn_bwd_finalize
+        mvf_new_count = ctypes.CFUNCTYPE(ctypes.c_size_t)(lambda: 3)
+
+    rec = launch_plan.Recorder()
+    lib = launch_plan.RecordingLib(rec, FakeLib)
+    assert lib.mvf_bn_workspace_bytes is FakeLib.mvf_bn_workspace_bytes and lib.mvf_bn_workspace_bytes(8, 8) > 0
+    assert lib.mvf_bn_bwd_finalize is not FakeLib.mvf_bn_bwd_finalize and rec.unsupported is None and rec.ops == []
+    assert lib.mvf_bn_bwd_finalize(None, 0, 8, None, None, None) == -1 and [op[2] for op in rec.ops] == ["mvf_bn_bwd_finalize"] and rec.unsupported is None
+    assert lib.mvf_new_count is not FakeLib.mvf_new_count and "mvf_new_count" in rec.unsupported
+
+
 def test_argument_validation_needs_no_gpu():
     from mvfnet_amd import _lib
     d = _lib.MvfDesc(10, 16, 4, 4, 4, 4, 7, 0, 0)

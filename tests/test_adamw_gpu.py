@@ -18,6 +18,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import adamw_numpy as A  # noqa: E402
+from helpers import library_names  # noqa: E402
 from mvfnet_amd import synth  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -446,30 +447,13 @@ def test_checkpoint_resume_takes_the_next_adamw_step_bit_identically(tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------ 12. plain SGD engine is unchanged
-class _NamesOf(object):
-    """Stands in for the library object and notes every entry point that is looked up."""
-
-    def __init__(self, real, names):
-        self.__dict__.update(_real=real, _names=names)
-
-    def __getattr__(self, name):
-        self._names.append(name)
-        return getattr(self._real, name)
-
-
 def test_a_plain_sgd_engine_makes_no_adamw_call_and_allocates_no_second_moment():
-    import mvfnet_amd.train_engine as te
     m = _model()
     eng = m.train_engine()
-    names = []
-    real = te.lib
-    te.lib = _NamesOf(real, names)
-    try:
+    with library_names(eng) as names:
         eng.train_step(*_batch(250))
         eng.accumulate_step(*_batch(251))
         eng.apply_accumulated()
-    finally:
-        te.lib = real
     torch.cuda.synchronize()
     assert eng.optimizer == "sgd" and eng.flat_var is None and eng._adam is None
     assert not [n for n in names if "adamw" in n]
@@ -481,12 +465,8 @@ def test_a_plain_sgd_engine_makes_no_adamw_call_and_allocates_no_second_moment()
     m2 = _model()
     eng2 = m2.train_engine()
     eng2.optimizer = "adam"
-    names = []
-    te.lib = _NamesOf(real, names)
-    try:
+    with library_names(eng2) as names:
         eng2.train_step(*_batch(250))
-    finally:
-        te.lib = real
     torch.cuda.synchronize()
     assert [n for n in names if ("sgd" in n or "adamw" in n) and "workspace" not in n] == ["mvf_adamw_step"]
     assert eng2.optimizer == "adam" and eng2.flat_var is not None and eng2.applied_steps() == 1

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import library_names
 from mvfnet_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -420,22 +421,10 @@ def test_average_of_untrained_parameters_stays_bit_equal_to_them(backbone):
 
 
 # ------------------------------------------------------------------------------------------------ 10. never enabled
-class _NamesOf(object):
-    """Stands in for the library object (as launch_plan.RecordingLib does) and notes every entry point that is looked up."""
-
-    def __init__(self, real, names):
-        self.__dict__.update(_real=real, _names=names)
-
-    def __getattr__(self, name):
-        self._names.append(name)
-        return getattr(self._real, name)
-
-
 NEW_ENTRY_POINTS = {"mvf_sgd_nesterov_step_ema", "mvf_sgd_step_segments_ema", "mvf_ema_update", "mvf_ema_swap"}
 
 
 def test_an_engine_that_never_enables_the_average_calls_only_the_plain_entry_points():
-    import mvfnet_amd.train_engine as te
     m = _model()
     eng = m.train_engine()
     imgs, labels = _batch(70)
@@ -444,13 +433,8 @@ def test_an_engine_that_never_enables_the_average_calls_only_the_plain_entry_poi
         eng.nesterov = nesterov
         eng.forward(imgs, labels)
         eng.backward()
-        names = []
-        real = te.lib
-        te.lib = _NamesOf(real, names)
-        try:
+        with library_names(eng) as names:
             eng.step()
-        finally:
-            te.lib = real
         seen[form] = names
     torch.cuda.synchronize()
     assert eng.flat_ema is None and eng.ema_updates == 0
@@ -463,13 +447,8 @@ def test_an_engine_that_never_enables_the_average_calls_only_the_plain_entry_poi
         eng.nesterov = nesterov
         eng.forward(imgs, labels)
         eng.backward()
-        names = []
-        real = te.lib
-        te.lib = _NamesOf(real, names)
-        try:
+        with library_names(eng) as names:
             eng.step()
-        finally:
-            te.lib = real
         assert [n for n in names if "sgd" in n and "workspace" not in n] == [want]
     assert eng.ema_updates == 2
 

@@ -19,6 +19,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import lamb_numpy as A  # noqa: E402
+from helpers import library_names  # noqa: E402
 from mvfnet_amd import synth  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -444,28 +445,11 @@ def test_engine_trains_under_lamb_and_resumes_bit_identically():
         opt2.load_state_dict(adamw_state_dict(2, [None] * len(names), [None] * len(names), A.LR))
 
 
-class _NamesOf(object):
-    """Stands in for the library object and notes every entry point that is looked up."""
-
-    def __init__(self, real, names):
-        self.__dict__.update(_real=real, _names=names)
-
-    def __getattr__(self, name):
-        self._names.append(name)
-        return getattr(self._real, name)
-
-
 def test_an_engine_left_on_sgd_has_no_lamb_buffers_and_makes_no_lamb_call():
-    import mvfnet_amd.train_engine as te
     m = _model()
     eng = m.train_engine()
-    names = []
-    real = te.lib
-    te.lib = _NamesOf(real, names)
-    try:
+    with library_names(eng) as names:
         eng.train_step(*_batch(310))
-    finally:
-        te.lib = real
     torch.cuda.synchronize()
     assert eng.optimizer == "sgd" and eng.flat_var is None and eng._adam is None and eng.trust_clip is None
     assert not [n for n in names if "lamb" in n]
@@ -477,12 +461,8 @@ def test_an_engine_left_on_sgd_has_no_lamb_buffers_and_makes_no_lamb_call():
     m2 = _model()
     eng2 = m2.train_engine()
     eng2.set_optimizer("lamb", trust_clip=True)
-    names = []
-    te.lib = _NamesOf(real, names)
-    try:
+    with library_names(eng2) as names:
         eng2.train_step(*_batch(310))
-    finally:
-        te.lib = real
     torch.cuda.synchronize()
     assert [n for n in names if ("sgd" in n or "adamw" in n or "lamb" in n) and "workspace" not in n] == ["mvf_lamb_step"]
     assert eng2.optimizer == "lamb" and eng2.eps == 1e-6 and eng2.trust_clip is True and eng2.applied_steps() == 1

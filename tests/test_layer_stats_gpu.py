@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import layer_stats_numpy as ln
+from helpers import library_names
 from mvfnet_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -357,15 +358,6 @@ def test_last_skip_names_where_the_step_went_wrong():
 
 
 def test_an_engine_that_never_enables_the_option_calls_none_of_the_new_entry_points():
-    import mvfnet_amd.train_engine as te
-
-    class NamesOf(object):
-        def __init__(self, real, names):
-            self.__dict__.update(_real=real, _names=names)
-
-        def __getattr__(self, name):
-            self._names.append(name)
-            return getattr(self._real, name)
     new = {"mvf_flat_segment_stats", "mvf_flat_stats_workspace_bytes", "mvf_bn_stats_nonfinite"}
     m = _model()
     eng = m.train_engine(lr=LR)
@@ -373,12 +365,8 @@ def test_an_engine_that_never_enables_the_option_calls_none_of_the_new_entry_poi
     imgs, labels = _batch(240)
 
     def one_step():
-        names, real = [], te.lib
-        te.lib = NamesOf(real, names)
-        try:
+        with library_names(eng) as names:
             eng.train_step(imgs.clone(), labels.clone(), lr=LR)
-        finally:
-            te.lib = real
         return names
     assert not new & set(one_step()) and eng._lstats is None
     eng.enable_layer_stats(on_skip=True)

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import metrics_numpy as mn
+from helpers import NamesOf, library_names
 from mvfnet_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -419,21 +420,9 @@ def test_micro_steps_count_their_rows_and_blended_steps_count_none():
     torch.cuda.synchronize()
 
 
-class _NamesOf(object):
-    """Stands in for a library object and notes every entry point that is looked up."""
-
-    def __init__(self, real, names):
-        self.__dict__.update(_real=real, _names=names)
-
-    def __getattr__(self, name):
-        self._names.append(name)
-        return getattr(self._real, name)
-
-
 def _calls_of_one_step(eng, imgs, labels):
     """(library calls the engine made, entry points looked up on the package's library object) during one eager train_step."""
     import mvfnet_amd._lib as L
-    import mvfnet_amd.train_engine as te
     from mvfnet_amd import launch_plan
 
     class _Names(launch_plan.Recorder):
@@ -442,13 +431,13 @@ def _calls_of_one_step(eng, imgs, labels):
         def call(self, name, fn, args):
             self.ops.append(name)
     rec, names = _Names(), []
-    recording = launch_plan.RecordingLib(rec)
-    real_te, real_l = te.lib, L.lib
-    te.lib, L.lib = recording, _NamesOf(real_l, names)
+    real_l = L.lib
+    L.lib = NamesOf(real_l, names)
     try:
-        eng.train_step(imgs, labels, lr=LR)
+        with library_names(eng, lib=launch_plan.RecordingLib(rec, type(eng).lib)):
+            eng.train_step(imgs, labels, lr=LR)
     finally:
-        te.lib, L.lib = real_te, real_l
+        L.lib = real_l
     return list(rec.ops), names
 
 

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import library_names
 from mvfnet_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -278,27 +279,12 @@ def _same_bits(a, b):
     return a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.reshape(-1).view(torch.uint8), b.reshape(-1).view(torch.uint8))
 
 
-class _NamesOf(object):
-    """Stands in for the library object (as launch_plan.RecordingLib does) and notes every entry point that is looked up."""
-
-    def __init__(self, real, names):
-        self.__dict__.update(_real=real, _names=names)
-
-    def __getattr__(self, name):
-        self._names.append(name)
-        return getattr(self._real, name)
-
-
-def _names_during(call):
-    import mvfnet_amd.train_engine as te
-    names, real = [], te.lib
-    te.lib = _NamesOf(real, names)
-    try:
-        out = call()
-    except Exception as e:          # noqa: BLE001 -- handed back to the caller beside the names
-        out = e
-    finally:
-        te.lib = real
+def _names_during(eng, call):
+    with library_names(eng) as names:
+        try:
+            out = call()
+        except Exception as e:          # noqa: BLE001 -- handed back to the caller beside the names
+            out = e
     return names, out
 
 
@@ -323,7 +309,7 @@ def _live_run(dtype):
     ma = _model(momentum=1.0)
     ea = ma.train_engine(dtype=dtype)
     snaps = _twin_snapshots(ma, ea, CALIB)
-    r["forward_names"], _ = _names_during(lambda: ea.forward(*_batch(CALIB[0])))
+    r["forward_names"], _ = _names_during(ea, lambda: ea.forward(*_batch(CALIB[0])))
     del ma, ea
     mb = _model()
     eb = mb.train_engine(dtype=dtype)
@@ -336,7 +322,7 @@ def _live_run(dtype):
             pulled.append(s)
             yield _batch(s)
     rng0 = torch.cuda.get_rng_state()
-    r["names"], r["used"] = _names_during(lambda: eb.precise_bn(feed(CALIB), num_iters=3))
+    r["names"], r["used"] = _names_during(eb, lambda: eb.precise_bn(feed(CALIB), num_iters=3))
     torch.cuda.synchronize()
     r["rng_untouched"] = torch.equal(rng0, torch.cuda.get_rng_state())
     want = _mean_of(snaps)
@@ -417,7 +403,7 @@ def test_refusals_leave_everything_as_it_was():
     def unchanged():
         torch.cuda.synchronize()
         return all(_same_bits(v, before[k]) for k, v in m.state_dict().items()) and all(b.momentum == 0.1 for b in eng._all_bns())
-    names, out = _names_during(lambda: eng.precise_bn(iter(()), num_iters=3))
+    names, out = _names_during(eng, lambda: eng.precise_bn(iter(()), num_iters=3))
     assert isinstance(out, ValueError) and "no batch" in str(out) and unchanged()
     assert _new(names) == ["mvf_bn_stats_exchange"] * 2          # the pre-call copy, and its way back
     for bad in (0, -1, 2.5, True):
@@ -428,14 +414,14 @@ def test_refusals_leave_everything_as_it_was():
     with pytest.raises(RuntimeError, match="enable_ema"):
         eng.precise_bn(good, weights="ema")
     # a batch that raises midway (a host tensor: the forward refuses it) after one good batch has overwritten the statistics
-    names, out = _names_during(lambda: eng.precise_bn([good[0], (good[1][0].cpu(), good[1][1]), good[2]], num_iters=3))
+    names, out = _names_during(eng, lambda: eng.precise_bn([good[0], (good[1][0].cpu(), good[1][1]), good[2]], num_iters=3))
     assert isinstance(out, RuntimeError) and "GPU input" in str(out)
     assert _new(names) == ["mvf_bn_stats_exchange", "mvf_bn_stats_accumulate", "mvf_bn_stats_exchange"]
     assert unchanged()
     # non-finite statistics on entry
     with torch.no_grad():
         m.backbone.layer2[1].bn2.running_var[5] = float("inf")
-    names, out = _names_during(lambda: eng.precise_bn(good, num_iters=3))
+    names, out = _names_during(eng, lambda: eng.precise_bn(good, num_iters=3))
     assert isinstance(out, RuntimeError) and "non-finite" in str(out) and "layer2.1.bn2.running_var" in str(out)
     assert _new(names) == ["mvf_bn_stats_exchange"] and not any("conv" in n for n in names)
     with torch.no_grad():
@@ -444,7 +430,7 @@ def test_refusals_leave_everything_as_it_was():
     # micro-steps pending in the accumulator
     eng.accumulate_step(*good[0])
     pending = {k: v.clone() for k, v in m.state_dict().items()}
-    names, out = _names_during(lambda: eng.precise_bn(good, num_iters=3))
+    names, out = _names_during(eng, lambda: eng.precise_bn(good, num_iters=3))
     assert isinstance(out, RuntimeError) and "pending" in str(out) and not names
     assert all(_same_bits(v, pending[k]) for k, v in m.state_dict().items())
     eng.apply_accumulated(lr=0.01)
@@ -478,7 +464,7 @@ def test_norm_eval_backbone_has_nothing_to_calibrate():
     eng = m.train_engine()
     before = {k: v.clone() for k, v in m.state_dict().items()}
     assert not _stats(m)                             # every BatchNorm is in eval mode
-    names, used = _names_during(lambda: eng.precise_bn([_batch(CALIB[0])], num_iters=5))
+    names, used = _names_during(eng, lambda: eng.precise_bn([_batch(CALIB[0])], num_iters=5))
     torch.cuda.synchronize()
     assert used == 0 and not names
     assert all(_same_bits(v, before[k]) for k, v in m.state_dict().items())
@@ -505,7 +491,7 @@ def _ema_run(dtype):
     def block():
         with eng.averaged_weights():
             return {k: v.clone() for k, v in _stats(m).items()}
-    names, inside = _names_during(block)
+    names, inside = _names_during(eng, block)
     r["uncalibrated_block"] = (not _new(names) and names.count("mvf_ema_swap") == 2 and eng.flat_ema_stats is None
                                and all(_same_bits(v, live[k]) for k, v in inside.items()) and "bn_stats" not in eng.ema_state_dict())
     # the twin: the averaged parameters and the live statistics in a model whose BatchNorm modules carry momentum 1.0
@@ -515,7 +501,7 @@ def _ema_run(dtype):
     et.flat_params.copy_(e0)
     want = _mean_of(_twin_snapshots(mt, et, CALIB))
     del mt, et
-    r["names"], r["used"] = _names_during(lambda: eng.precise_bn([_batch(s) for s in CALIB], num_iters=3, weights="ema"))
+    r["names"], r["used"] = _names_during(eng, lambda: eng.precise_bn([_batch(s) for s in CALIB], num_iters=3, weights="ema"))
     torch.cuda.synchronize()
 
     def live_again():
@@ -523,7 +509,7 @@ def _ema_run(dtype):
                 and all(_same_bits(v, live[k]) for k, v in m.state_dict().items()))
     r["live_untouched"] = live_again()
     stats0 = eng.flat_ema_stats.clone()
-    names, inside = _names_during(block)
+    names, inside = _names_during(eng, block)
     torch.cuda.synchronize()
     r["block_names"] = _new(names)
     r["inside_is_twin"] = _equal_bits(inside, want)
@@ -609,6 +595,6 @@ def test_an_engine_that_never_calibrates_calls_none_of_the_entry_points():
         with eng.averaged_weights():
             m.state_dict()
         eng.ema_state_dict()
-    names, out = _names_during(work)
+    names, out = _names_during(eng, work)
     torch.cuda.synchronize()
     assert out is None and not _new(names) and eng.flat_ema_stats is None and not getattr(eng, "_stat_tables", None)

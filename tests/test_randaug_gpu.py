@@ -5,6 +5,7 @@ import pytest
 import torch
 
 import randaug_numpy as RN
+from helpers import library_names
 from test_launch_plan_gpu import _engine
 
 pytestmark = pytest.mark.gpu
@@ -165,7 +166,7 @@ B, T, HS, WS, CROP = 2, 4, 72, 80, 64
 
 
 class _Names(object):
-    """Stands in for _lib.lib in a module: every call is made and its name noted."""
+    """Stands in for a library object (the engine's handle, a module's `lib`): every call is made and its name noted."""
 
     def __init__(self, real, names):
         self._real, self._names = real, names
@@ -179,11 +180,10 @@ class _Names(object):
         return w
 
 
-def _recorded(monkeypatch, fn):
-    from mvfnet_amd import preprocess, train_engine
+def _recorded(monkeypatch, eng, fn):
+    from mvfnet_amd import preprocess
     names = []
-    with monkeypatch.context() as mp:
-        mp.setattr(train_engine, "lib", _Names(train_engine.lib, names))
+    with monkeypatch.context() as mp, library_names(eng, lib=_Names(eng.lib, names)):
         mp.setattr(preprocess, "lib", _Names(preprocess.lib, names))
         fn()
     torch.cuda.synchronize()
@@ -233,7 +233,7 @@ def test_engine_step_equals_the_step_on_frames_augmented_beforehand(kind, monkey
         keep = x.clone()
         loss = eng.train_step(x, labels, lr=0.01).clone()
         out[run] = (loss, eng.flat_grads.clone(), eng.flat_params.clone(), [b_.clone() for b_ in m.buffers()])
-        names[run] = _recorded(monkeypatch, lambda: eng.train_step(x, labels, lr=0.01))      # a second step: the first one of a process sizes workspaces
+        names[run] = _recorded(monkeypatch, eng, lambda: eng.train_step(x, labels, lr=0.01))      # a second step: the first one of a process sizes workspaces
         assert torch.equal(x, keep)
         has = any(k[0] in ("randaug_out", "randaug_tmp", "randaug_ws", "randaug_table") for k in eng._bufs)
         assert has == (run == "A")                                  # off: nothing is allocated for the feature
@@ -286,7 +286,7 @@ def test_eval_does_not_augment_and_precise_bn_and_accumulation(monkeypatch):
     eng.input_pipeline, eng.input_window = P.FramePipeline(MEAN, STD, to_rgb=True, crop_size=CROP), None
     fr = torch.from_numpy(_frames(B * T, HS, WS, seed=17).reshape(B, T, HS, WS, 3)).cuda()
     labels = torch.tensor([[3], [111]], device="cuda")
-    names = _recorded(monkeypatch, lambda: eng.train_step(fr, labels, lr=0.01))
+    names = _recorded(monkeypatch, eng, lambda: eng.train_step(fr, labels, lr=0.01))
     assert names.count("mvf_frames_randaug_u8") == 1 and Counting.calls == 1
     # accumulation draws per micro-step
     eng.accumulate_step(fr, labels)
@@ -294,12 +294,12 @@ def test_eval_does_not_augment_and_precise_bn_and_accumulation(monkeypatch):
     eng.apply_accumulated(lr=0.01)
     assert Counting.calls == 3
     # precise_bn switches it off for its forwards and puts it back
-    names = _recorded(monkeypatch, lambda: eng.precise_bn([(fr, labels)] * 2, num_iters=2))
+    names = _recorded(monkeypatch, eng, lambda: eng.precise_bn([(fr, labels)] * 2, num_iters=2))
     assert "mvf_frames_randaug_u8" not in names and Counting.calls == 3 and eng.randaug is m.randaug
     # eval: the configured object does not reach the engine
     m.eval()
     assert eng.randaug is None
-    names = _recorded(monkeypatch, lambda: eng.forward(fr, labels))
+    names = _recorded(monkeypatch, eng, lambda: eng.forward(fr, labels))
     assert "mvf_frames_randaug_u8" not in names and Counting.calls == 3 and eng._randaug_table is None
     m.train()
     assert eng.randaug is m.randaug
@@ -324,7 +324,7 @@ def test_the_three_refusals(monkeypatch):
             def refused():
                 with pytest.raises(ValueError, match=what):
                     call()
-            assert _recorded(monkeypatch, refused) == [], what
+            assert _recorded(monkeypatch, eng, refused) == [], what
     # a gather table names its sources: not one row per frame of the batch
     eng.input_pipeline = P.GatherFramePipeline(MEAN, STD, to_rgb=True, crop_size=CROP)
     rows = eng.input_pipeline.center_window(B * T, HS, WS)

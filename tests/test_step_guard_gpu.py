@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import library_names
 from mvfnet_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -475,31 +476,14 @@ def test_runner_logs_the_count_and_checkpoints_carry_it(tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------ 10. never enabled
-class _NamesOf(object):
-    """Stands in for the library object (as launch_plan.RecordingLib does) and notes every entry point that is looked up."""
-
-    def __init__(self, real, names):
-        self.__dict__.update(_real=real, _names=names)
-
-    def __getattr__(self, name):
-        self._names.append(name)
-        return getattr(self._real, name)
-
-
 NEW_ENTRY_POINTS = {"mvf_sgd_step_guarded", "mvf_bn_stats_snapshot", "mvf_bn_stats_restore"}
 
 
 def _names_of_one_step(eng, imgs, labels):
-    import mvfnet_amd.train_engine as te
-    names = []
-    real = te.lib
-    te.lib = _NamesOf(real, names)
-    try:
+    with library_names(eng) as names:
         eng.forward(imgs, labels)
         eng.backward()
         eng.step()
-    finally:
-        te.lib = real
     return names
 
 

@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import trn_numpy as tn
+from helpers import NamesOf, library_names
 from mvfnet_amd import synth
 from mvfnet_amd.heads import relation as rel
 
@@ -538,17 +539,6 @@ def test_the_default_head_steps_as_it_did():
 
 
 # ------------------------------------------------------------------------------------------------ the loss dispatcher (heads/loss_calls.py)
-class _NamesOf(object):
-    """Stands in for the library object (as launch_plan.RecordingLib does) and notes every entry point that is looked up."""
-
-    def __init__(self, real, names):
-        self.__dict__.update(_real=real, _names=names)
-
-    def __getattr__(self, name):
-        self._names.append(name)
-        return getattr(self._real, name)
-
-
 HEAD_ENTRY_POINTS = {"mvf_head_train_fwd", "mvf_head_train_fwd_soft", "mvf_head_train_fwd_bce", "mvf_head_train_fwd_focal", "mvf_trn_head_fwd", "mvf_ce_loss",
                      "mvf_ce_loss_soft", "mvf_bce_loss", "mvf_focal_loss"}
 DISPATCH = {"default": (None, None, 0.0, ["mvf_head_train_fwd"]),
@@ -560,11 +550,10 @@ DISPATCH = {"default": (None, None, 0.0, ["mvf_head_train_fwd"]),
 
 @pytest.mark.parametrize("config", list(DISPATCH))
 def test_the_step_looks_its_head_entry_point_up_on_the_engines_library_object(config):
-    """One eager forward per head configuration with train_engine.lib replaced by a names-only stand-in: the step looks up exactly the head entry point(s) it
-    always called, on the object the engine module holds at call time -- which is what launch_plan.RecordingLib relies on to record the head -- and
+    """One eager forward per head configuration with the engine's library handle (eng.lib) replaced by a names-only stand-in: the step looks up exactly the
+    head entry point(s) it always called, on its own handle at call time -- which is what launch_plan.recording() relies on to record the head -- and
     heads/loss_calls.py looks nothing up through _lib.lib (replaced by a second stand-in for the duration)."""
     import mvfnet_amd._lib as L
-    import mvfnet_amd.train_engine as te
     from mvfnet_amd.heads import loss_calls
     kind, loss_cls, eps, want = DISPATCH[config]
     imgs, hot, labels = _clips()
@@ -573,13 +562,14 @@ def test_the_step_looks_its_head_entry_point_up_on_the_engines_library_object(co
     eng = m.train_engine(dtype=BF16)
     eng.use_plan, eng.label_smooth_eps = False, eps
     assert "lib" not in vars(loss_calls)
-    on_engine, on_module = [], []
-    real_te, real_l = te.lib, L.lib
-    te.lib, L.lib = _NamesOf(real_te, on_engine), _NamesOf(real_l, on_module)
+    on_module = []
+    real_l = L.lib
+    L.lib = NamesOf(real_l, on_module)
     try:
-        loss = eng.forward(imgs, hot.float() if loss_cls is not None else labels)
+        with library_names(eng) as on_engine:
+            loss = eng.forward(imgs, hot.float() if loss_cls is not None else labels)
     finally:
-        te.lib, L.lib = real_te, real_l
+        L.lib = real_l
     torch.cuda.synchronize()
     assert torch.isfinite(loss).all()
     assert [n for n in on_engine if n in HEAD_ENTRY_POINTS] == want, [n for n in on_engine if n in HEAD_ENTRY_POINTS]
