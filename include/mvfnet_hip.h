@@ -425,6 +425,32 @@ int mvf_bn_bwd_apply(const void* g, int g_pitch, const void* z, long m, int c, c
 int mvf_bn_apply_bits(const void* z, long m, int c, const float* scale, const float* shift, const void* residual,
                       const float* rscale, const float* rshift, int relu, void* out, unsigned char* sign_bits, int dtype,
                       void* stream);
+/* Stochastic depth (drop path, timm drop_path(x, p, training, scale_by_keep)) on the residual branch of a bottleneck, csrc/drop_path.hip:
+ * mvf_bn_apply_bits with the BatchNorm output scaled per ROW before the residual is added.  row_scale: m / rows_per_image fp32 values in device memory,
+ * image r / rows_per_image owns row r (the host draws them: mvfnet_amd/droppath.py; the kernels do not know whether a draw is per clip or per frame).
+ * In fp32, per element of row r and channel k, with s = row_scale[r / rows_per_image]:
+ *     u   = scale[k] * z + shift[k]                              formed exactly as mvf_bn_apply_bits forms it
+ *     v   = s * u                                                one product, rounded
+ *     res = residual  |  rscale[k] * residual + rshift[k]        as mvf_bn_apply_bits forms it; the residual is REQUIRED and never scaled
+ *     out = act(v + res)                                         one sum, rounded (never fused with the product); act: 0 none, 1 ReLU
+ * stored once in the storage type; sign_bits [m][c/4] (required) hold the signs of the STORED output in mvf_bn_apply_bits' layout.  With every s = 1.0f, out
+ * and sign_bits equal mvf_bn_apply_bits on the same operands bit for bit; with s = 0 and a finite z, out = act(res) exactly; IEEE arithmetic throughout (a
+ * non-finite z in a dropped row gives NaN, as 0 * inf does in torch).  The grid is mvf_bn_apply_bits' (its column plan at 4096 workgroups); no atomics, so
+ * results are bit-identical from run to run.  Nothing is added to the mvf_bn_last_launch record.
+ * Checked before any launch (MVF_EINVAL): a NULL operand (rscale / rshift may both be NULL), rows_per_image < 1, m % rows_per_image != 0, c % 4 != 0,
+ * an unknown dtype or act, and the alignment: z, residual, out, scale, shift, rscale, rshift 16 bytes, row_scale 4 bytes.  fp32 and bf16 storage; bf16 takes
+ * 16-byte lanes when c % 8 == 0 and sign_bits is 2-byte aligned, 8-byte lanes otherwise. */
+int mvf_bn_apply_bits_rowscale(const void* z, long m, int c, const float* scale, const float* shift, const void* residual, const float* rscale,
+                               const float* rshift, const float* row_scale, int rows_per_image, int act, void* out, unsigned char* sign_bits, int dtype,
+                               void* stream);
+/* The backward companion: the gradient into the scaled BatchNorm output, gm[r][k] = bit(r, k) ? s * g[r][k] : 0 with the sign bits mvf_bn_apply_bits_rowscale
+ * wrote and the same row_scale table -- one fp32 product per element, stored once ([m][c], pitch c); g rows are g_pitch >= c apart.  (The gradient of the
+ * identity path stays g gated by the bits, unscaled.)  With every s = 1.0f, gm equals the gm_out mvf_bn_bwd_reduce writes in mask mode 4, bit for bit.
+ * Checked before any launch (MVF_EINVAL): a NULL operand, rows_per_image < 1, m % rows_per_image != 0, c % 4 != 0, g_pitch < c or g_pitch % 4 != 0, an
+ * unknown dtype, and the alignment: g and gm_out 16 bytes, row_scale 4 bytes.  bf16 takes 16-byte lanes when c % 8 == 0, g_pitch % 8 == 0 and sign_bits is
+ * 2-byte aligned. */
+int mvf_gate_rowscale(const void* g, int g_pitch, const unsigned char* sign_bits, const float* row_scale, int rows_per_image, long m, int c, void* gm_out,
+                      int dtype, void* stream);
 int mvf_bn_bwd_apply_masked(const void* g, int g_pitch, const void* z, const void* ymask, long m, int c, const float* gamma,
                             const float* mean, const float* invstd, const float* scale, const float* shift,
                             const float* dgamma, const float* dbeta, int mask_mode, void* dz, int dtype, void* stream);

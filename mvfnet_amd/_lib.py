@@ -274,6 +274,10 @@ def _load():
     lib.mvf_bn_apply.argtypes = [vp, i64, i32, fp, fp, vp, fp, fp, i32, vp, i32, vp]
     lib.mvf_bn_apply_bits.restype = i32
     lib.mvf_bn_apply_bits.argtypes = [vp, i64, i32, fp, fp, vp, fp, fp, i32, vp, vp, i32, vp]
+    lib.mvf_bn_apply_bits_rowscale.restype = i32
+    lib.mvf_bn_apply_bits_rowscale.argtypes = [vp, i64, i32, fp, fp, vp, fp, fp, fp, i32, i32, vp, vp, i32, vp]
+    lib.mvf_gate_rowscale.restype = i32
+    lib.mvf_gate_rowscale.argtypes = [vp, i32, vp, fp, i32, i64, i32, vp, i32, vp]
     lib.mvf_bn_bwd_apply_masked.restype = i32
     lib.mvf_bn_bwd_apply_masked.argtypes = [vp, i32, vp, vp, i64, i32, fp, fp, fp, fp, fp, fp, fp, i32, vp, i32, vp]
     lib.mvf_bn_bwd_reduce.restype = i32

@@ -83,6 +83,10 @@ class Recognizer2D(nn.Module):
         self.distill = build_distill(distill_cfg)
         if self.distill is not None and hasattr(self.distill, "check_student"):
             self.distill.check_student(self, device=False)
+        # train_cfg=dict(drop_path=dict(type='DropPath', rate=0.05)): stochastic depth on the bottlenecks' residual branches, drawn per clip, likewise
+        from ..droppath import build_drop_path
+        drop_cfg = train_cfg.get("drop_path") if hasattr(train_cfg, "get") else getattr(train_cfg, "drop_path", None)
+        self.drop_path = build_drop_path(drop_cfg)
         self.in_channels = 3
         if self.module_cfg:
             # reference recognizer2d.py:45-59: weights are initialised/loaded BEFORE the MVF wrappers exist
@@ -160,13 +164,14 @@ class Recognizer2D(nn.Module):
         return self
 
     def _set_soft_options(self, eng, training):
-        """The ONE place train_cfg['blending'], train_cfg['erasing'], train_cfg['randaug'], train_cfg['distill'] and the head's label_smooth_eps reach the engine: only while the model trains.  Called
+        """The ONE place train_cfg['blending'], train_cfg['erasing'], train_cfg['randaug'], train_cfg['distill'], train_cfg['drop_path'] and the head's label_smooth_eps reach the engine: only while the model trains.  Called
         when the engine is created, whenever the mode changes (train() / eval()) and by forward_train.  engine.blending / engine.erasing / engine.randaug / engine.distill /
         engine.label_smooth_eps are plain attributes: whoever drives engine.train_step directly may also set them by hand, until the next of these calls."""
         eng.blending = self.blending if training else None
         eng.erasing = self.erasing if training else None
         eng.randaug = self.randaug if training else None
         eng.distill = self.distill if training else None       # train_cfg['distill'] (distill.py): the same rule
+        eng.drop_path = self.drop_path if training else None   # train_cfg['drop_path'] (droppath.py): the same rule
         eng.label_smooth_eps = float(getattr(self.cls_head, "label_smooth_eps", 0.0)) if training else 0.0
         # the head's loss (loss_cls) is no augmentation: it holds in either mode.  None = softmax cross-entropy.
         if getattr(self.cls_head, "loss_cls", None) is not None:

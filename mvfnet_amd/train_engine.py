@@ -181,6 +181,22 @@ class _BN(object):
                                     _p(rbn.shift if rbn else None), act, _p(out), _p(sb), self.eng.dt, _st()), "mvf_bn_apply")
         return (out, sb) if bits else out
 
+    def apply_rowscale(self, z, m, act, residual, row_scale, rows_per_image, rbn=None):
+        """Drop path: out = act(s * bn(z) + residual) with one fp32 scale per image (row_scale [m / rows_per_image], csrc/drop_path.hip) and the sign bits
+        of out; apply()'s buffers."""
+        out = self.eng.buf((id(self), "apply"), z.shape, z.dtype)
+        sb = self.eng.buf((id(self), "bits"), (m, self.c // 4), torch.uint8)
+        check(self.eng.lib.mvf_bn_apply_bits_rowscale(_p(z), m, self.c, _p(self.scale), _p(self.shift), _p(residual), _p(rbn.scale if rbn else None),
+                                                      _p(rbn.shift if rbn else None), _p(row_scale), rows_per_image, act, _p(out), _p(sb), self.eng.dt, _st()),
+              "mvf_bn_apply_bits_rowscale")
+        return out, sb
+
+    def gate_rowscale(self, g, g_pitch, bits, m, row_scale, rows_per_image):
+        """Drop path: gm = [out > 0] * s * g, the gradient into this BatchNorm's scaled output (mvf_gate_rowscale)."""
+        gm = self.eng.buf((id(self), "gm"), (m, self.c))
+        check(self.eng.lib.mvf_gate_rowscale(_p(g), g_pitch, _p(bits), _p(row_scale), rows_per_image, m, self.c, _p(gm), self.eng.dt, _st()), "mvf_gate_rowscale")
+        return gm
+
     def apply_colmeans(self, z, m, act, mean_out):
         """[r5] out = act(bn(z)) + the column means of what is stored into mean_out -- conv3's a_mean for the Gram form of bn3's statistics
         (_TConv.gram_stats) without a pass over a2."""
@@ -738,6 +754,8 @@ class _TBlock(object):
         2 every block)."""
         # ([r5] planes <= 256 -- with the Gram statistics (gram_fwd) layer3 would also drop its first conv3 pass -- measured WORSE, three alternations on one
         # box: C3 17.57-17.65 -> 17.99-18.09 ms, C4 30.07-30.16 -> 31.94-32.01: the apply epilogue on the 1024-wide GEMM costs more than the byte-bound pass)
+        if self.drop is not None:
+            return False           # a drop-path block takes the plain stored-z3 path (and through this answer neither z3_free, z3_free_ds, gram_fwd nor q_z3_free)
         f = eng.fuse_bn3_apply
         return f == 2 or (f == 1 and self.c3.cin <= 128)
 
@@ -774,6 +792,11 @@ class _TBlock(object):
         return eng.lib.mvf_conv1x1_bwd_fused_splits(m2, self.c3.cout, self.c3.cin) > 0
 
     above = None       # the block whose backward produces this block's output gradient (set by the engine / BlockTrainer over a chain)
+    # Drop path (droppath.py, csrc/drop_path.hip): None, or this step's fp32 device scale per image for the block's residual branch -- set by the engine before
+    # the step's first launch (TrainEngine._step_tensors, BlockTrainer.set_drop_scale).  A block with a scale stores z3, applies bn3 with
+    # mvf_bn_apply_bits_rowscale and takes bn3's backward on gm = [out > 0] * s * g (mvf_gate_rowscale) through the plain calls: no fused apply, no dz3-free
+    # form, no gated hand-down, no paired BatchNorm backward, no weight gradient inside the BatchNorm pass.  A block without one is not touched.
+    drop = None
 
     def q_policy(self, eng, m2):
         """eng.dzfree_q: 0 off, 1 planes <= dzfree_q_maxk (the GEMM costs 2 m c k flops against the sums pass's 4 m c bytes: half the pass at k = 128, even at
@@ -804,7 +827,7 @@ class _TBlock(object):
     def dzfree(self, eng, m2=None):
         """[r5] bn3's backward without the dz3 tensor (csrc/bn_dzfree.hip): plain blocks (no downsample branch) with a STORED z3 whose last conv
         is pointwise; eng.dzfree: 0 off, 1 planes >= 256 (where dz3 is the widest tensor and no fused pass exists), 2 every eligible block."""
-        if self.cd is not None or (self.z3_free(eng, m2) and not self.q_z3_free(eng, m2 or (1 << 16))):
+        if self.drop is not None or self.cd is not None or (self.z3_free(eng, m2) and not self.q_z3_free(eng, m2 or (1 << 16))):
             return False
         return self._dzfree_base(eng, m2)
 
@@ -836,6 +859,8 @@ class _TBlock(object):
     def forward(self, x, nt, h, w, c, eng):
         m = nt * h * w
         s = dict(x=x, h=h, w=w, c=c)
+        if self.drop is not None and (self.drop.numel() != nt or self.drop.dtype != torch.float32):
+            raise ValueError("drop path: a float32 scale per image is expected (%d images, got %d %s)" % (nt, self.drop.numel(), self.drop.dtype))
         # The downsample branch conv -> BN statistics only depends on the block input: it runs on the side stream (idle during the
         # forward pass) beside conv1 -> bn1 -> conv2 -> bn2 -> conv3 and is joined before bn3's apply adds the two branches.
         side = eng.side_stream() if (self.cd is not None and eng.overlap_downsample and eng.fuse_stats) else None
@@ -875,16 +900,20 @@ class _TBlock(object):
                 eng._wait(eng.main_stream(), side)                # the downsample branch (queued before conv1, see above)
             else:
                 zd, _, _ = self.cd.forward(x, nt, h, w, bn=self.bd)
-            if self.fuse_apply(eng):
+            if self.drop is not None:                             # drop path: the branch is scaled per image, the downsample branch never
+                out, bits = self.b3.apply_rowscale(z3, m2, 1, zd, self.drop, ho * wo, rbn=self.bd)
+            elif self.fuse_apply(eng):
                 out, bits = self.c3.forward_apply(a2, nt, ho, wo, self.b3, zd, self.bd)
             else:
                 out, bits = self.b3.apply(z3, m2, 1, residual=zd, rbn=self.bd, bits=True)
             s["zd"] = zd
+        elif self.drop is not None:
+            out, bits = self.b3.apply_rowscale(z3, m2, 1, x, self.drop, ho * wo)
         elif self.fuse_apply(eng):
             out, bits = self.c3.forward_apply(a2, nt, ho, wo, self.b3, x)
         else:
             out, bits = self.b3.apply(z3, m2, 1, residual=x, bits=True)
-        s.update(z1=z1, a1=a1, z2=z2, a2=a2, z3=z3, out=out, bits=bits, ho=ho, wo=wo, gram=gram)
+        s.update(z1=z1, a1=a1, z2=z2, a2=a2, z3=z3, out=out, bits=bits, ho=ho, wo=wo, gram=gram, drop=self.drop)
         self.saved = s
         return out, ho, wo, self.c3.cout
 
@@ -908,7 +937,14 @@ class _TBlock(object):
         dzd = resid_ds = None
         w3_done = wd_done = False        # [r4] weight gradient already taken inside the BatchNorm-backward pass
         q_first = s["z3"] is None and g_gated and sums_done == "s1"       # [r5] z3 neither stored nor needed (q_z3_free)
-        if self.cd is not None and s["z3"] is None:
+        if s["drop"] is not None:
+            # drop path: out = relu(s * bn3(z3) + identity), so bn3's output receives gm = [out > 0] * s * g as a tensor and its backward runs unmasked on it;
+            # the identity path below keeps (g, bits), and a downsample branch its own unpaired backward on them
+            assert not g_gated and s["z3"] is not None
+            gm = self.b3.gate_rowscale(g, self.c3.cout, bits, m2, s["drop"], ho * wo)
+            dz3 = self.b3.backward(gm, self.c3.cout, s["z3"], m2, eng, 0)
+            del gm
+        elif self.cd is not None and s["z3"] is None:
             # [r4] z3-free downsample block: each branch = sums pass + one-pass backward on the recomputed conv; neither dz3 nor dz_d exists
             pair = bool(eng.pair_ds_sums & 1)
             if pair:           # bn3's and bn_d's sums in ONE pass over g (csrc/pw_sums_pair.hip)
@@ -1872,6 +1908,14 @@ class BlockTrainer(_ParamStore):
         for lo, hi in zip(self.blks[:-1], self.blks[1:]):
             lo.above = hi
 
+    def set_drop_scale(self, scale, blocks=None):
+        """Drop path for the following forwards: `scale` = a float32 device tensor of one value per image (kept by reference: refill it in place for other
+        draws), or None to clear it; for every block, or for the block indices `blocks`."""
+        if scale is not None and (scale.dtype != torch.float32 or scale.dim() != 1 or not scale.is_cuda or not scale.is_contiguous()):
+            raise ValueError("BlockTrainer.set_drop_scale: a contiguous 1-D float32 device tensor (one scale per image) or None")
+        for i in (range(len(self.blks)) if blocks is None else blocks):
+            self.blks[i].drop = scale
+
     def forward(self, x_nchw):
         nt, c, h, w = x_nchw.shape
         self.nt = nt
@@ -1994,6 +2038,31 @@ class TrainEngine(_ParamStore):
         # mvf_head_train_fwd_focal in that place.  The struct's address is a frozen word of a recorded call (the recorder keeps the struct alive with the
         # plan), so the struct is never written after it is built: other settings are another struct, and every setting's value is part of the plan key.
         self.focal = None
+        # Stochastic depth (droppath.py: an object with drops(n_blocks) and draw(n_blocks, b, t) -> fp32 (n_blocks, b * t), the scale of every block's
+        # residual branch per image; None = off).  The table is drawn once per forward (under accumulation: per micro-step) and uploaded as the blend table
+        # is; the blocks it names (_TBlock.drop) take the stored-z3 path and the two kernels of csrc/drop_path.hip, every other block is not touched.  Part
+        # of the plan key, appended only when set: with None the key, the allocations and the launches are what they were.
+        self.drop_path = None
+        self._drop_blocks = False        # some block still carries a scale view from an earlier step
+
+    def _draw_drop_path(self, b, t):
+        """This step's drop-path table into its persistent device buffer (outside the region a launch plan records: a replayed plan sees each step's own
+        draws), and every block's view of it -- or None for the blocks that do not drop."""
+        if self.drop_path is None:
+            if self._drop_blocks:
+                for blk in self.blocks:
+                    blk.drop = None
+                self._drop_blocks = False
+            return
+        from .droppath import check_drop_table
+        n, nt = len(self.blocks), b * t
+        drops = tuple(self.drop_path.drops(n))
+        table = check_drop_table(self.drop_path.draw(n, b, t), n, nt)
+        (table_d,) = self._upload_table("drop_path_table", [table])
+        table_d = table_d.view(torch.float32).view(n, nt)
+        for i, blk in enumerate(self.blocks):
+            blk.drop = table_d[i] if drops[i] else None
+        self._drop_blocks = True
 
     def _pack_all(self, kind):
         """All forward (kind 0) or data-gradient (kind 1) weight packs in ONE launch (mvf_pack_conv_weights_batched); the job
@@ -2085,6 +2154,8 @@ class TrainEngine(_ParamStore):
             table = check_relation_table(table, self.trn["kind"], self.trn["t"])
             (table_d,) = self._upload_table("relation_table", [table])
             self._relation_table = (table_d, int(table.shape[0]))
+        if self.drop_path is not None or self._drop_blocks:
+            self._draw_drop_path(imgs.shape[0], imgs.shape[1])
         mask = None
         if self.dropout > 0.0:
             nt, cc = imgs.shape[0] * imgs.shape[1], self.fc_w.shape[1]
@@ -2511,6 +2582,7 @@ class TrainEngine(_ParamStore):
     focal = None             # (the class default of the instance attribute __init__ sets: None is no plan-key switch, see _switch_names)
     trn = relations = None   # (likewise: the relation head's settings and the explicit relation table)
     _shared_taps = False     # (likewise: __init__ sets it when an MVF block of the model has share=True)
+    drop_path, _drop_blocks = None, False      # (likewise: the drop-path object and "some block carries a scale view")
 
     def _plan_key(self, imgs, labels):
         """None = this step cannot run from a plan; else what a plan is valid for."""
@@ -2541,7 +2613,11 @@ class TrainEngine(_ParamStore):
                     # the focal family: the struct's address is a frozen word too, so its identity and every value it holds join the key
                     (("focal", self.focal[0].data_ptr() if self.focal[0] is not None else 0, C.addressof(self.focal[1])) + tuple(
                         repr(float(getattr(self.focal[1], k))) for k in ("gamma_pos", "gamma_neg", "margin", "alpha", "target_threshold")) + (
-                            int(self.focal[1].sum_classes),),) if self.focal is not None else ())
+                            int(self.focal[1].sum_classes),),) if self.focal is not None else ()) + (
+                    # drop path: which blocks take the stored-z3 path and the drop-path kernels (other launches), the unit and scale_by_keep; the scales
+                    # themselves travel through the persistent table
+                    (("drop_path", tuple(self.drop_path.drops(len(self.blocks))), str(getattr(self.drop_path, "unit", None)),
+                      bool(getattr(self.drop_path, "scale_by_keep", True))),) if self.drop_path is not None else ())
 
     def _record_step(self, imgs, labels, prepared):
         """One eager step with every library call and stream ordering recorded; returns (loss, Plan | None)."""
@@ -2973,7 +3049,7 @@ class TrainEngine(_ParamStore):
             bad = [key for key, (first, k, _) in zip(tab.keys, tab.slices) if not bool(torch.isfinite(tab.shadow[first:first + k]).all())]
             raise RuntimeError("precise_bn: non-finite running statistics on entry (%s); nothing was changed" % ", ".join(bad[:4]))
         nbt = self._nbt_flat.clone()
-        state = [(b, b.momentum) for b in bns], self.blending, self.dropout, self.erasing, self.randaug, self.distill
+        state = [(b, b.momentum) for b in bns], self.blending, self.dropout, self.erasing, self.randaug, self.distill, self.drop_path
         tab.acc.zero_()
         used, done, swapped = 0, False, False
         if self._guard is not None:
@@ -2987,6 +3063,7 @@ class TrainEngine(_ParamStore):
                 b.momentum = 1.0
             self.blending, self.dropout, self.erasing, self.randaug = None, 0.0, None, None
             self.distill = None                  # no teacher forward, no mvf_distill_loss: the calibration needs the student's batch statistics alone
+            self.drop_path = None                # no drop path: the statistics of the whole network, as at evaluation time (and no draw is consumed)
             for imgs, labels in itertools.islice(batches, num_iters):
                 self.forward(imgs, labels)
                 with on():
@@ -3005,7 +3082,7 @@ class TrainEngine(_ParamStore):
         finally:
             for b, m in state[0]:
                 b.momentum = m
-            self.blending, self.dropout, self.erasing, self.randaug, self.distill = state[1], state[2], state[3], state[4], state[5]
+            self.blending, self.dropout, self.erasing, self.randaug, self.distill, self.drop_path = state[1], state[2], state[3], state[4], state[5], state[6]
             side = getattr(self, "_side", None)
             if side is not None:
                 torch.cuda.current_stream().wait_stream(side)      # the forwards' data-gradient weight packs read the parameters there
